@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the U-Net hot path on MI355X:  voxels/s of a full train step (forward + loss + backward + Adam).
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg4|cfg2|cfg3|cfg5|cfg1]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg4|cfg2|cfg3|cfg5|cfg1] [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU over RCCL, either launched by the driver as  python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N ...  (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or -- when WORLD_SIZE is NOT set -- by this
@@ -13,9 +13,12 @@ Workloads (BASELINE.json `configs`) -- synthetic data x ~ U[0,1), 
   cfg4 (default, the north-star target): UNet3D(1,1,32), (4,1,128,128,128) per GPU, bf16 storage / fp32 accumulate
   cfg2: Unet(1,2,64), (16,1,512,512), fp32          cfg3: Siam_UNet(32,'max'), 2 x (16,1,512,512), bf16
   cfg5: MultiOutputUnet3D(1, 3 heads, 64, interp), (1,1,128,256,256), bf16      cfg1: Unet(1,1,32), (2,1,256,256), fp32
-One JSON line on rank 0 (contract in the task statement) with two extra objects:
-  roofline     -- the dominant kernel launch, timed live with HIP events inside the timed region
-  cpu_baseline -- the CPU oracle (a restatement of the reference's PyTorch-CPU path) on a bounded sample, host cores
+A plain run sets up, warms up, times K steps and prints one JSON line on rank 0 (metric, value, unit, higher_is_better, dtype,
+ms_per_step = wall milliseconds of one timed step).  --full adds what the headline does not need, at the cost of runs of its own:
+  roofline      -- the dominant kernel launch (found by a per-call profile of the last warm-up step), timed live with HIP events
+                   inside the timed region; step_roofline -- whole-step utilisation; fwd_only -- forward-only throughput
+  cpu_baseline  -- the CPU oracle (a restatement of the reference's PyTorch-CPU path) on a bounded sample, host cores
+--dump-outputs DIR: after the timed steps, what the last one handed its caller as DIR/<name>.npy (float32, <= 64 MB; dump_outputs).
 """
 import argparse
 import json
@@ -47,9 +50,11 @@ WORKLOADS = {
 }
 
 
-def make_step(wl, device, graph=False):
+def make_step(wl, device, graph=False, keep_outputs=False, from_seed=True):
     """Returns (model, step_fn, fwd_fn, voxels_per_step). The loss expressions are the reference trainers' own.
-    graph=True: the same step captured once in a hipGraph and replayed (bio_image_unet_amd/graph.py; single process)."""
+    graph=True: the same step captured once in a hipGraph and replayed (bio_image_unet_amd/graph.py; single process).
+    keep_outputs=True: every step leaves the model's outputs and the loss in ``step_fn.last`` (for a replayed graph: the captured tensors,
+    which every replay rewrites).  from_seed=True: every step starts from the seeded weights (below); False: steps train on from each other."""
     import bio_image_unet_amd as B
     from bio_image_unet_amd.losses import BCEDiceLoss
     from bio_image_unet_amd.optim import Adam
@@ -73,7 +78,15 @@ def make_step(wl, device, graph=False):
     else:
         y = (torch.rand((shape[0], wl["out"]) + tuple(shape[2:]), device=device) > 0.5).float()
 
+    last = {}
+
     def loss_of(outs):
+        loss = ref_loss(outs)
+        if keep_outputs:
+            last.update(outs=outs, loss=loss)
+        return loss
+
+    def ref_loss(outs):
         if wl["model"] == "Unet":            # unet/train.py:133-134 (indexes the batch axis with the channel index)
             oc = wl["out"]
             return sum(crit(outs[1][ch], y[ch]) for ch in range(oc)) / oc
@@ -87,12 +100,26 @@ def make_step(wl, device, graph=False):
     def fwd():
         return model(x, px) if px is not None else model(x)
 
+    # Every step starts from the seeded weights (restored in place, so a captured graph keeps its addresses).  Each forward is then the
+    # same bit for bit, and so are the BatchNorm statistics and -- to the summation order of the float atomics of the weight gradients,
+    # ~1e-8 -- the gradients and the Adam moments built from them: the last timed step computes the same in every run.  Trained on from
+    # step to step instead, Adam amplifies that order until two runs' outputs differ by their own magnitude.  (Restoring the moments and
+    # BatchNorm buffers as well is not needed for that, and costs 0.05-0.2 ms per cfg4 step.)
+    params = list(model.parameters())
+    seeded = [p.detach().clone() for p in params]
+
+    @torch.no_grad()
+    def reset():
+        torch._foreach_copy_(params, seeded)
+
     from bio_image_unet_amd.ddp import GradAverager
     avg = GradAverager(model)
     avg_ms = []                                    # host milliseconds every average() spent launching leftovers + waiting (per step)
     avg.wait_log = avg_ms
 
     def step():
+        if from_seed:
+            reset()
         outs = fwd()
         loss = loss_of(outs)
         opt.zero_grad(set_to_none=True)
@@ -112,8 +139,11 @@ def make_step(wl, device, graph=False):
         eager_step = step
 
         def step():                                  # noqa: F811
+            if from_seed:
+                reset()
             return gstep(ins, [])
         step.eager = eager_step
+    step.last = last
 
     nvox = 1
     for s in (shape[0],) + tuple(shape[2:]):
@@ -165,6 +195,43 @@ def call_cost(eng, api, label, executed=False):
         bwd = api.endswith("_bwd") or "_bwd_" in api          # backward of a 2x pool: x, dx in, dx out (+ the pooled gradient)
         return 0.0, float(node.xin.nvox * node.xin.c * (3 if bwd else 1) + node.y.nvox * node.y.c) * esz
     return 0.0, 0.0
+
+
+DUMP_MAX_ELEMS = 1 << 21        # per array (8 MB in float32); a dump holds at most 7 arrays (cfg5: loss, 3 heads, parameters, gradients, buffers)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, model, last):
+    """What the last timed step handed its caller, as ``dirname/<name>.npy`` in float32: ``loss``, the model's outputs (``prob`` / ``logits``,
+    or one file per head of MultiOutputUnet3D), and after the optimizer step ``params``, ``grads`` and ``buffers`` (every parameter, its
+    gradient and every floating-point buffer -- the BatchNorm running statistics -- flattened and concatenated in ``model.parameters()`` /
+    ``model.buffers()`` order).  An array of more than DUMP_MAX_ELEMS elements is written as a fixed sample: the elements at DUMP_MAX_ELEMS
+    sorted flat indices drawn by ``torch.randint`` from a CPU generator seeded with 0, the same for every run with the same arguments.
+    Inputs and weights are seeded and every step starts from those weights (make_step): two runs agree bit for bit in loss, outputs and
+    buffers, and in gradients and parameters to the summation order of the float atomics in the weight gradients."""
+    import numpy as np
+    outs = last["outs"]
+    arrays = {"loss": last["loss"]}
+    arrays.update(outs.items() if isinstance(outs, dict) else zip(("prob", "logits"), outs))
+    with torch.no_grad():
+        ps = list(model.parameters())
+        arrays["params"] = torch.cat([p.reshape(-1).float() for p in ps])
+        arrays["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for p in ps])
+        arrays["buffers"] = torch.cat([b.reshape(-1).float() for b in model.buffers() if b.is_floating_point()])
+        host = {}
+        for name, t in arrays.items():
+            a = t.detach().float()
+            if a.numel() > DUMP_MAX_ELEMS:
+                g = torch.Generator().manual_seed(0)
+                idx = torch.randint(a.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+                a = a.reshape(-1)[idx.to(a.device)]
+            host[name] = a.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def _cpu_model():
@@ -272,8 +339,17 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured hipGraph (N = 1 only)")
     ap.add_argument("--fp32-products", default="bf16x6", choices=["exact", "bf16x3", "bf16x6"],
                     help="fp32 workloads: how the 2-D 3x3 kernels multiply (default: bf16x6, the library's default -- fp32-grade split products)")
-    ap.add_argument("--breakdown", default=None, help="write the per-launch time table of one profiled step to this file")
+    ap.add_argument("--breakdown", default=None, help="with --full: write the per-launch time table of the profiled step to this file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32, <= 64 MB: see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (profiled warm-up step, dominant launch timed in the timed "
+                         "region), step_roofline, fwd_only and cpu_baseline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.breakdown and not args.full:
+        ap.error("--breakdown needs --full (the per-launch table comes from the profiled warm-up step)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
 
@@ -291,44 +367,46 @@ def main():
     if wl["dtype"] == "f32":
         import bio_image_unet_amd
         bio_image_unet_amd.set_fp32_products(args.fp32_products)
-    model, step, fwd, nvox, avg = make_step(wl, device, graph=args.graph and world == 1)
+    model, step, fwd, nvox, avg = make_step(wl, device, graph=args.graph and world == 1, keep_outputs=args.dump_outputs is not None)
 
     def barrier():
         if world > 1:
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    # ---- warm-up; the last warm-up step is profiled per C-ABI call to find the dominant launch ------------------------
-    for _ in range(max(args.warmup - 1, 0)):
+    # ---- warm-up; --full: the last warm-up step is profiled per C-ABI call to find the dominant launch ------------------
+    for _ in range(max(args.warmup - 1, 0) if args.full else args.warmup):
         step()
-    lib.prof = []
-    getattr(step, "eager", step)()              # (a replayed graph makes no C-ABI calls: the profiled step is the eager one)
-    torch.cuda.synchronize()
-    prof, lib.prof = lib.prof, None
-    eng = list(model._engines.values())[-1][-1]
-    agg = {}
-    for api, label, e0, e1 in prof:
-        agg.setdefault((api, label), []).append(e0.elapsed_time(e1))
-    rows = sorted(((sum(v), k) for k, v in agg.items()), reverse=True)
-    total_kernel_ms = sum(r[0] for r in rows)
-    dom_ms, dom_key = rows[0]
-    step_exec_flop = sum(call_cost(eng, api, label, executed=True)[0] * len(agg[(api, label)]) for api, label in agg)
-    if args.breakdown and rank == 0:
-        with open(args.breakdown, "w") as f:
-            f.write(f"# per-launch HIP-event times of one profiled step, workload {args.workload}; sum = {total_kernel_ms:.3f} ms\n")
-            f.write("# TFLOP/s (executed) and GB/s: the FLOPs the kernels of the call ISSUE and its algorithmic bytes (SURVEY 8d) -- hardware utilisation; "
-                    "'alg': the FLOPs of the reference ops the call stands for (larger for the folded decoder calls biu_foldt_*, biu_upconv_*: DESIGN.md 3.4); "
-                    "'roof': max(executed FLOP / MFMA peak, bytes / 8 TB/s) / time\n")
-            for ms, (api, label) in rows:
-                fl, by = call_cost(eng, api, label)
-                fx, _ = call_cost(eng, api, label, executed=True)
-                pk = MFMA_PEAK["bf16" if eng.tdtype == torch.bfloat16 else "f32"]
-                t_roof = max(fx / pk, by / HBM_PEAK) * 1e3
-                f.write(f"{ms:9.4f} ms  {api:26s} {label:22s} {fx / ms / 1e9 if ms else 0:9.1f} TFLOP/s {by / ms / 1e6 if ms else 0:9.1f} GB/s   "
-                        f"alg {fl / ms / 1e9 if ms else 0:7.1f}  roof {t_roof / ms if ms else 0:5.2f}\n")
+    if args.full:
+        lib.prof = []
+        getattr(step, "eager", step)()              # (a replayed graph makes no C-ABI calls: the profiled step is the eager one)
+        torch.cuda.synchronize()
+        prof, lib.prof = lib.prof, None
+        eng = list(model._engines.values())[-1][-1]
+        agg = {}
+        for api, label, e0, e1 in prof:
+            agg.setdefault((api, label), []).append(e0.elapsed_time(e1))
+        rows = sorted(((sum(v), k) for k, v in agg.items()), reverse=True)
+        total_kernel_ms = sum(r[0] for r in rows)
+        dom_ms, dom_key = rows[0]
+        step_exec_flop = sum(call_cost(eng, api, label, executed=True)[0] * len(agg[(api, label)]) for api, label in agg)
+        if args.breakdown and rank == 0:
+            with open(args.breakdown, "w") as f:
+                f.write(f"# per-launch HIP-event times of one profiled step, workload {args.workload}; sum = {total_kernel_ms:.3f} ms\n")
+                f.write("# TFLOP/s (executed) and GB/s: the FLOPs the kernels of the call ISSUE and its algorithmic bytes (SURVEY 8d) -- hardware utilisation; "
+                        "'alg': the FLOPs of the reference ops the call stands for (larger for the folded decoder calls biu_foldt_*, biu_upconv_*: DESIGN.md 3.4); "
+                        "'roof': max(executed FLOP / MFMA peak, bytes / 8 TB/s) / time\n")
+                for ms, (api, label) in rows:
+                    fl, by = call_cost(eng, api, label)
+                    fx, _ = call_cost(eng, api, label, executed=True)
+                    pk = MFMA_PEAK["bf16" if eng.tdtype == torch.bfloat16 else "f32"]
+                    t_roof = max(fx / pk, by / HBM_PEAK) * 1e3
+                    f.write(f"{ms:9.4f} ms  {api:26s} {label:22s} {fx / ms / 1e9 if ms else 0:9.1f} TFLOP/s {by / ms / 1e6 if ms else 0:9.1f} GB/s   "
+                            f"alg {fl / ms / 1e9 if ms else 0:7.1f}  roof {t_roof / ms if ms else 0:5.2f}\n")
 
     # ---- timed region --------------------------------------------------------------------------------------------------
-    lib.watch, lib.watched = dom_key, []
+    if args.full:
+        lib.watch, lib.watched = dom_key, []
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]     # per-step stamps on the compute stream (median)
     # The interpreter's cyclic garbage collector is paused inside the timed region, exactly as the package's Trainers pause it inside an
     # epoch's batch loop (workflow._EpochLoop._train_epoch): a generation-2 collection walks every object torch has imported and stalls
@@ -363,7 +441,9 @@ def main():
         print("bench: per-step ms " + " ".join(f"{v:.2f}" for v in per_step), file=sys.stderr)
     per_step.sort()
     median_ms = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
-    if hasattr(step, "eager"):                  # graph mode: the dominant launch is timed in eager steps after the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, step.last)
+    if args.full and hasattr(step, "eager"):    # graph mode: the dominant launch is timed in eager steps after the timed region
         for _ in range(3):
             step.eager()
         torch.cuda.synchronize()
@@ -386,57 +466,25 @@ def main():
         ranks_seen = int(one.item())
     ms_per_step = dt / args.steps * 1e3
 
-    # forward-only (eval-style use, no_grad; BN in train mode exactly as the reference's validation loop)
-    with torch.no_grad():
-        fwd()
-        barrier()
-        t1 = time.perf_counter()
-        nf = max(args.steps // 2, 1)
-        for _ in range(nf):
+    if args.full:
+        # forward-only (eval-style use, no_grad; BN in train mode exactly as the reference's validation loop)
+        with torch.no_grad():
             fwd()
-        barrier()
-        fwd_ms = (time.perf_counter() - t1) / nf * 1e3
+            barrier()
+            t1 = time.perf_counter()
+            nf = max(args.steps // 2, 1)
+            for _ in range(nf):
+                fwd()
+            barrier()
+            fwd_ms = (time.perf_counter() - t1) / nf * 1e3
 
     if rank != 0:
         if world > 1:
             torch.distributed.destroy_process_group()
         return
-    dom_launch_ms = sum(e0.elapsed_time(e1) for _, _, e0, e1 in watched) / max(len(watched), 1)
-    # utilisation figures are taken on the FLOPs the kernels of the call issue (`executed`); for the folded decoder ops the FLOPs of the
-    # reference ops they replace (SURVEY 8d's algorithmic convention, larger) are reported beside them as `algorithmic_equivalent`
-    fl_alg, by = call_cost(eng, *dom_key)
-    fl, _ = call_cost(eng, *dom_key, executed=True)
     dt_name = wl["dtype"]
     x3 = dt_name == "f32" and wl["model"] in ("Unet", "Siam_UNet") and args.fp32_products != "exact"
     nterms = {"bf16x3": 3, "bf16x6": 6}.get(args.fp32_products, 1)
-    mfma_peak = MFMA_PEAK["bf16"] / nterms if x3 else MFMA_PEAK[dt_name]
-    ai = fl / by if by else 0.0
-    ridge = mfma_peak / HBM_PEAK
-    if fl > 0 and ai >= ridge * 0.5:
-        roof = {"bound": "mfma", "achieved": fl / (dom_launch_ms * 1e-3) / 1e12, "peak": mfma_peak / 1e12, "unit": "TFLOP/s"}
-    else:
-        roof = {"bound": "hbm", "achieved": by / (dom_launch_ms * 1e-3) / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s"}
-    roof["frac"] = roof["achieved"] / roof["peak"]
-    if fl_alg != fl and fl > 0:
-        roof["algorithmic_equivalent"] = {"TFLOP_per_call": fl_alg / 1e12, "TFLOPps": fl_alg / (dom_launch_ms * 1e-3) / 1e12,
-                                          "note": "folded op (DESIGN.md 3.4): the kernels issue 8 parity classes x 2x2x2 coarse taps instead of 27 fine taps on the "
-                                                  "up-sampled channels; `achieved` / `frac` count the issued FLOPs, this entry the FLOPs of the reference ops "
-                                                  "(Conv3d on all concat channels + ConvTranspose3d) the call replaces -- not a utilisation figure"}
-    roof["traffic"] = None          # HBM bytes per launch from PMC counters (tools/pmc_traffic.py), when measured for this call
-    tr_file = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", f"pmc_traffic_{args.workload}.json")
-    if os.path.exists(tr_file):
-        tr = json.load(open(tr_file)).get(f"{dom_key[0]} @ {dom_key[1]}")
-        if tr:
-            roof["traffic"] = tr["traffic_bytes_per_call"]
-            roof["traffic_source"] = f"profiles/pmc_traffic_{args.workload}.json (rocprofv3 PMC, separate run; algorithmic bytes {by:.4g})"
-    roof["kernel"] = f"{dom_key[0]} @ {dom_key[1]}"
-    roof["launch_ms"] = dom_launch_ms
-    roof["launches_timed"] = len(watched)
-    roof["share_of_step_kernel_time"] = dom_ms / total_kernel_ms if total_kernel_ms else None
-
-    # whole-step roofline numbers of SURVEY.md 8d (cfg4: 1.316 MFLOP and 2915 B per voxel, fwd+bwd)
-    per_vox = {"cfg4": (1.316e6, 2915.0), "cfg2": (3 * 1467.8e3, 3 * 5596.0), "cfg3": (3 * 469e3, 3 * 1940.0),
-               "cfg5": (3 * 3243.7e3, 3 * 2179.0), "cfg1": (3 * 367.2e3, 3 * 2800.0)}[args.workload]
     vps_gpu = nvox / (ms_per_step * 1e-3)
     out = {
         "metric": "voxels/sec fwd+bwd", "value": vps_gpu * world, "unit": "voxels/s", "n_gpus": world, "steps": args.steps,
@@ -446,17 +494,51 @@ def main():
         "dtype": dt_name, "data": "synthetic", "host": "cyclic GC paused inside the timed region (as in the package's Trainers)" if gc_paused else "cyclic GC on",
         "config": {"workload": f"{args.workload}: {wl['model']}({', '.join(f'{k}={v}' for k, v in wl['ctor'].items() if k != 'output_heads')}) input {wl['shape']} per GPU, "
                                "train step = forward + reference loss + backward + Adam", "parallelism": f"dp{world}"},
-        "fwd_only": {"value": nvox / (fwd_ms * 1e-3) * world, "unit": "voxels/s", "ms": fwd_ms},
-        "step_roofline": {"hbm_frac_algorithmic": vps_gpu * per_vox[1] / HBM_PEAK, "algorithmic_GBps": vps_gpu * per_vox[1] / 1e9,
-                          "algorithmic_TFLOPps": vps_gpu * per_vox[0] / 1e12, "mfma_frac_algorithmic": vps_gpu * per_vox[0] / mfma_peak,
-                          "executed_TFLOPps": step_exec_flop / (ms_per_step * 1e-3) / 1e12, "mfma_frac": step_exec_flop / (ms_per_step * 1e-3) / mfma_peak,
-                          "note": "mfma_frac = FLOPs the step's kernels issue / time / peak (utilisation); *_algorithmic = SURVEY 8d's per-voxel figures of the "
-                                  "reference ops (what `value` x 1.316 MFLOP is), larger where decoder levels run folded",
-                          "kernel_time_ms_one_step": total_kernel_ms},
-        "roofline": roof,
     }
+    if args.full:
+        dom_launch_ms = sum(e0.elapsed_time(e1) for _, _, e0, e1 in watched) / max(len(watched), 1)
+        # utilisation figures are taken on the FLOPs the kernels of the call issue (`executed`); for the folded decoder ops the FLOPs of the
+        # reference ops they replace (SURVEY 8d's algorithmic convention, larger) are reported beside them as `algorithmic_equivalent`
+        fl_alg, by = call_cost(eng, *dom_key)
+        fl, _ = call_cost(eng, *dom_key, executed=True)
+        mfma_peak = MFMA_PEAK["bf16"] / nterms if x3 else MFMA_PEAK[dt_name]
+        ai = fl / by if by else 0.0
+        ridge = mfma_peak / HBM_PEAK
+        if fl > 0 and ai >= ridge * 0.5:
+            roof = {"bound": "mfma", "achieved": fl / (dom_launch_ms * 1e-3) / 1e12, "peak": mfma_peak / 1e12, "unit": "TFLOP/s"}
+        else:
+            roof = {"bound": "hbm", "achieved": by / (dom_launch_ms * 1e-3) / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s"}
+        roof["frac"] = roof["achieved"] / roof["peak"]
+        if fl_alg != fl and fl > 0:
+            roof["algorithmic_equivalent"] = {"TFLOP_per_call": fl_alg / 1e12, "TFLOPps": fl_alg / (dom_launch_ms * 1e-3) / 1e12,
+                                              "note": "folded op (DESIGN.md 3.4): the kernels issue 8 parity classes x 2x2x2 coarse taps instead of 27 fine taps on the "
+                                                      "up-sampled channels; `achieved` / `frac` count the issued FLOPs, this entry the FLOPs of the reference ops "
+                                                      "(Conv3d on all concat channels + ConvTranspose3d) the call replaces -- not a utilisation figure"}
+        roof["traffic"] = None          # HBM bytes per launch from PMC counters (tools/pmc_traffic.py), when measured for this call
+        tr_file = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", f"pmc_traffic_{args.workload}.json")
+        if os.path.exists(tr_file):
+            tr = json.load(open(tr_file)).get(f"{dom_key[0]} @ {dom_key[1]}")
+            if tr:
+                roof["traffic"] = tr["traffic_bytes_per_call"]
+                roof["traffic_source"] = f"profiles/pmc_traffic_{args.workload}.json (rocprofv3 PMC, separate run; algorithmic bytes {by:.4g})"
+        roof["kernel"] = f"{dom_key[0]} @ {dom_key[1]}"
+        roof["launch_ms"] = dom_launch_ms
+        roof["launches_timed"] = len(watched)
+        roof["share_of_step_kernel_time"] = dom_ms / total_kernel_ms if total_kernel_ms else None
+
+        # whole-step roofline numbers of SURVEY.md 8d (cfg4: 1.316 MFLOP and 2915 B per voxel, fwd+bwd)
+        per_vox = {"cfg4": (1.316e6, 2915.0), "cfg2": (3 * 1467.8e3, 3 * 5596.0), "cfg3": (3 * 469e3, 3 * 1940.0),
+                   "cfg5": (3 * 3243.7e3, 3 * 2179.0), "cfg1": (3 * 367.2e3, 3 * 2800.0)}[args.workload]
+        out["fwd_only"] = {"value": nvox / (fwd_ms * 1e-3) * world, "unit": "voxels/s", "ms": fwd_ms}
+        out["step_roofline"] = {"hbm_frac_algorithmic": vps_gpu * per_vox[1] / HBM_PEAK, "algorithmic_GBps": vps_gpu * per_vox[1] / 1e9,
+                                "algorithmic_TFLOPps": vps_gpu * per_vox[0] / 1e12, "mfma_frac_algorithmic": vps_gpu * per_vox[0] / mfma_peak,
+                                "executed_TFLOPps": step_exec_flop / (ms_per_step * 1e-3) / 1e12, "mfma_frac": step_exec_flop / (ms_per_step * 1e-3) / mfma_peak,
+                                "note": "mfma_frac = FLOPs the step's kernels issue / time / peak (utilisation); *_algorithmic = SURVEY 8d's per-voxel figures of the "
+                                        "reference ops (what `value` x 1.316 MFLOP is), larger where decoder levels run folded",
+                                "kernel_time_ms_one_step": total_kernel_ms}
+        out["roofline"] = roof
     if hasattr(step, "eager"):
-        out["graph"] = "step replayed from one captured hipGraph; roofline.launch_ms from eager steps after the timed region"
+        out["graph"] = "step replayed from one captured hipGraph" + ("; roofline.launch_ms from eager steps after the timed region" if args.full else "")
     if x3 and nterms == 3:
         out["arithmetic"] = ("fp32 tensors and accumulators; the products of the 3x3 convolutions (forward, data and weight gradient) are bf16x3: "
                              "operands split hi + lo in bf16, hi*hi + hi*lo + lo*hi on the bf16 MFMA, <= 2^-15 relative per product; "
@@ -478,7 +560,7 @@ def main():
                       "grad_copies_in_backward": avg.copies_in_backward,
                       "per_rank": {"columns": ["ms_per_step", "median_ms_per_step", "average_wait_ms_mean", "average_wait_ms_max"], "rows": per_rank},
                       "step_ms_min_max_over_ranks": [min(r_[0] for r_ in per_rank), max(r_[0] for r_ in per_rank)] if per_rank else None}
-    if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (rank 0's host cores, bounded sample)
+    if args.full and not args.no_cpu_baseline and world == 1:      # reported at N = 1 only (rank 0's host cores, bounded sample)
         out["cpu_baseline"] = cpu_baseline(args.workload)
     print(json.dumps(out), flush=True)
     if world > 1:

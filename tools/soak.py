@@ -19,7 +19,7 @@ else:
     runs = [("cfg4", False, 300), ("cfg1", False, 600), ("cfg1", True, 600), ("cfg3", True, 100), ("cfg2", False, 30), ("cfg5", False, 20)]
 for W, graph, n in runs:
     wl = bench.WORKLOADS[W]
-    model, step, fwd, nvox, _ = bench.make_step(wl, torch.device("cuda", 0), graph=graph)
+    model, step, fwd, nvox, _ = bench.make_step(wl, torch.device("cuda", 0), graph=graph, from_seed=False)   # steps train on
     for _ in range(5):
         step()
     torch.cuda.synchronize()

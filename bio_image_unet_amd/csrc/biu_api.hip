@@ -1,11 +1,81 @@
 // Public conv / conv-transpose entry points: validation + dispatch between the MFMA implicit-GEMM kernels
-// (biu_conv_mfma.hip) and the shape-generic direct kernels (biu_direct.hip).
+// (biu_conv_mfma.hip) and the shape-generic direct kernels (biu_direct.hip).  Also the library's one reader of the environment
+// (biu_env, biu_off: every switch, read once per process; INTEGRATION.md, "A/B and debug switches").
 #include "biu_common.h"
 #include "biu_internal.h"
 
-// Debug switches (read once): BIU_DISABLE=conv_fwd,conv_dgrad,conv_wgrad,convt_fwd,convt_dgrad,convt_wgrad routes the named op family to the direct kernels.
 #include <stdlib.h>
 #include <string.h>
+
+// Every token BIU_DISABLE takes: INTEGRATION.md's table (sidechain, prepack and capturefork are read by engine.py alone)
+static const char* const kOffTokens[] = {
+    "conv_fwd", "conv_dgrad", "conv_wgrad", "convt_fwd", "convt_dgrad", "convt_wgrad", "convt_all", "c1", "c1_mfma", "cat",
+    "fused_stats", "wgrad_bn", "dgrad_bnred", "pool_pair", "pool_pipe", "pool_bnred", "head_bnred", "ksplit", "m16", "m16x2", "rr16",
+    "wroll", "wroll16", "wroll2d", "upconv", "foldt", "foldall", "foldck8", "foldgemm", "croll", "froll", "prepack", "wsplitbn",
+    "capturefork", "sidechain",
+};
+constexpr int kNumOffTokens = sizeof(kOffTokens) / sizeof(kOffTokens[0]);
+static_assert(kNumOffTokens <= 64, "BiuEnv::off holds one bit per token");
+
+static int off_index(const char* tok, size_t n) {
+    for (int i = 0; i < kNumOffTokens; ++i)
+        if (strlen(kOffTokens[i]) == n && strncmp(kOffTokens[i], tok, n) == 0) return i;
+    return -1;
+}
+static void env_unknown(const char* var, const char* val, int n) {
+    fprintf(stderr, "[biu] %s: unknown %s '%.*s' ignored\n", var, strcmp(var, "BIU_DISABLE") == 0 ? "token" : "value", n, val);
+}
+static bool parse_int(const char* s, int* v) {
+    char* end = nullptr;
+    const long r = strtol(s, &end, 10);
+    if (end == s || *end) return false;
+    *v = (int)r;
+    return true;
+}
+
+const BiuEnv& biu_env() {
+    static const BiuEnv env = [] {
+        BiuEnv v{0, false, false, 0, 2, 128};
+        if (const char* p = getenv("BIU_DISABLE")) {
+            while (true) {
+                const size_t n = strcspn(p, ",");
+                const int i = off_index(p, n);
+                if (i >= 0) v.off |= 1ull << i;
+                else if (n > 0) env_unknown("BIU_DISABLE", p, (int)n);
+                if (!p[n]) break;
+                p += n + 1;
+            }
+        }
+        if (const char* e = getenv("BIU_ROLL"); e && *e) {
+            if (strcmp(e, "always") == 0) v.roll_always = true;
+            else env_unknown("BIU_ROLL", e, (int)strlen(e));
+        }
+        if (const char* e = getenv("BIU_FOLDT"); e && *e) {
+            int n = 0;
+            if (strcmp(e, "always") == 0) v.foldt_always = true;
+            else if (strncmp(e, "cmax:", 5) == 0 && parse_int(e + 5, &n) && n > 0) v.foldt_cmax = n;
+            else if (strcmp(e, "size") != 0) env_unknown("BIU_FOLDT", e, (int)strlen(e));
+        }
+        if (const char* e = getenv("BIU_FP32_PRODUCTS"); e && *e) {
+            if (strcmp(e, "exact") == 0) v.fp32_products = 0;
+            else if (strcmp(e, "bf16x3") == 0) v.fp32_products = 1;
+            else if (strcmp(e, "bf16x6") != 0) env_unknown("BIU_FP32_PRODUCTS", e, (int)strlen(e));
+        }
+        if (const char* e = getenv("BIU_FALL_MAXCA"); e && *e) {
+            int n = 0;
+            if (parse_int(e, &n)) v.fall_maxca = n;
+            else env_unknown("BIU_FALL_MAXCA", e, (int)strlen(e));
+        }
+        return v;
+    }();
+    return env;
+}
+
+bool biu_off(const char* token) {
+    const int i = off_index(token, strlen(token));
+    return i >= 0 && ((biu_env().off >> i) & 1);
+}
+
 // The any-shape kernels are a correctness tier: a large layer landing on them (odd channel counts, dilation != 1, a sample
 // beyond the 4 GB descriptor range, an unaligned slice) runs orders of magnitude below the MFMA path.  Say so, once per op.
 static void warn_slow_path(const char* op, const biu_act* x, const biu_act* y, int taps) {
@@ -16,11 +86,6 @@ static void warn_slow_path(const char* op, const biu_act* x, const biu_act* y, i
         fprintf(stderr, "[biu] %s: %d->%d channels on %lld voxels takes the any-shape kernel (%.1f GMAC): expect it to be slow; "
                         "the MFMA path needs channel counts that are multiples of 8 (>= 16), dilation 1, 16-byte aligned slices "
                         "and samples under 4 GB\n", op, x->c, y->c, (long long)nvox(y), macs * 1e-9);
-}
-
-static bool disabled(const char* what) {
-    const char* env = getenv("BIU_DISABLE");       // re-read per call: tests flip it inside one process
-    return env && strstr(env, what) != nullptr;
 }
 
 static bool conv_args_ok(const biu_act* x, const biu_act* y, int kd, int kh, int kw, int dil) {
@@ -71,7 +136,7 @@ extern "C" int biu_conv_fwd_stats(const biu_act* x, const biu_xform* xf, const f
                 "conv_fwd: x/y extents differ or unsupported kernel %dx%dx%d dil %d", kd, kh, kw, dilation);
     BIU_REQUIRE(w && bn_partial && bn_nblk, BIU_ERR_SHAPE, "conv_fwd_stats: null pointer");
     *bn_nblk = 0;
-    if (!disabled("c1") && !disabled("fused_stats") && biu_c1m_ok(x, y, kd, kh, kw, dilation, dtype)) {
+    if (!biu_off("c1") && !biu_off("fused_stats") && biu_c1m_ok(x, y, kd, kh, kw, dilation, dtype)) {
         const int nb = biu_c1m_fwd_rows(y, kd);                    // first layer on the matrix cores, statistics from its epilogue
         if ((size_t)nb * y->c * 2 <= bn_partial_floats) {
             int rc = biu_c1m_fwd(x, xf, w, bias, kd, y, bn_partial, (hipStream_t)stream);
@@ -80,7 +145,7 @@ extern "C" int biu_conv_fwd_stats(const biu_act* x, const biu_xform* xf, const f
         }
     }
     // (a launch split over the input channels cannot take its statistics from the epilogue: plain conv, then biu_bn_stats)
-    if (packed && !disabled("conv_fwd") && !disabled("fused_stats") && biu_mfma_conv_ok(x, y, kd, kh, kw, dilation, dtype) &&
+    if (packed && !biu_off("conv_fwd") && !biu_off("fused_stats") && biu_mfma_conv_ok(x, y, kd, kh, kw, dilation, dtype) &&
         !will_split(x->c, y, nullptr, kd, dtype, ws, ws_bytes)) {
         const int nb = biu_mfma_conv_stat_rows(y, kd, x, dtype);           // one partial row per workgroup column
         if ((size_t)nb * y->c * 2 <= bn_partial_floats) {
@@ -106,11 +171,11 @@ extern "C" int biu_conv_fwd(const biu_act* x, const biu_xform* xf, const float* 
     BIU_REQUIRE(conv_args_ok(x, y, kd, kh, kw, dilation), BIU_ERR_SHAPE,
                 "conv_fwd: x/y extents differ or unsupported kernel %dx%dx%d dil %d", kd, kh, kw, dilation);
     BIU_REQUIRE(w, BIU_ERR_SHAPE, "conv_fwd: null weight");
-    if (!disabled("c1") && biu_c1m_ok(x, y, kd, kh, kw, dilation, dtype))
+    if (!biu_off("c1") && biu_c1m_ok(x, y, kd, kh, kw, dilation, dtype))
         return biu_c1m_fwd(x, xf, w, bias, kd, y, nullptr, (hipStream_t)stream);
-    if (!disabled("c1") && biu_c1_conv_ok(x, y, kd, kh, kw, dilation, dtype))
+    if (!biu_off("c1") && biu_c1_conv_ok(x, y, kd, kh, kw, dilation, dtype))
         return biu_c1_conv_fwd(x, xf, w, bias, kd, y, dtype, (hipStream_t)stream);
-    if (packed && !disabled("conv_fwd") && biu_mfma_conv_ok(x, y, kd, kh, kw, dilation, dtype))
+    if (packed && !biu_off("conv_fwd") && biu_mfma_conv_ok(x, y, kd, kh, kw, dilation, dtype))
         return biu_mfma_conv(x, xf, packed, bias, kd, kh, kw, y, 0, nullptr, dtype, (hipStream_t)stream, nullptr, nullptr, ws, ws_bytes);
     warn_slow_path("conv_fwd", x, y, kd * kh * kw);
     return biu_conv_fwd_direct(x, xf, w, bias, kd, kh, kw, dilation, y, dtype, (hipStream_t)stream);
@@ -120,7 +185,7 @@ extern "C" int biu_conv_bwd_data(const biu_act* dy, const float* w, const void* 
                                  int dilation, const biu_act* dx, int accumulate, void* ws, size_t ws_bytes, int dtype, biu_stream stream) {
     BIU_REQUIRE(conv_args_ok(dy, dx, kd, kh, kw, dilation), BIU_ERR_SHAPE, "conv_bwd_data: dy/dx extents differ");
     BIU_REQUIRE(w, BIU_ERR_SHAPE, "conv_bwd_data: null weight");
-    if (packed && !disabled("conv_dgrad") && biu_mfma_conv_ok(dy, dx, kd, kh, kw, dilation, dtype))
+    if (packed && !biu_off("conv_dgrad") && biu_mfma_conv_ok(dy, dx, kd, kh, kw, dilation, dtype))
         return biu_mfma_conv(dy, nullptr, packed, nullptr, kd, kh, kw, dx, accumulate, nullptr, dtype, (hipStream_t)stream, nullptr, nullptr, ws, ws_bytes);
     warn_slow_path("conv_bwd_data", dx, dy, kd * kh * kw);
     return biu_conv_bwd_data_direct(dy, w, kd, kh, kw, dilation, dx, accumulate, dtype, (hipStream_t)stream);
@@ -143,7 +208,7 @@ extern "C" int biu_conv_bwd_data_bnred(const biu_act* dy, const float* w, const 
     BIU_REQUIRE(w && scale && shift && mean && invstd && partial && nblk, BIU_ERR_SHAPE, "conv_bwd_data_bnred: null pointer");
     const size_t es = dsize(dtype);
     const bool yok = ((uintptr_t)y_up->p % 16) == 0 && ((size_t)y_up->pitch * es) % 16 == 0;
-    if (packed && yok && !disabled("conv_dgrad") && !disabled("dgrad_bnred") && biu_mfma_conv_ok(dy, dx, kd, kh, kw, dilation, dtype) &&
+    if (packed && yok && !biu_off("conv_dgrad") && !biu_off("dgrad_bnred") && biu_mfma_conv_ok(dy, dx, kd, kh, kw, dilation, dtype) &&
         !will_split(dy->c, dx, nullptr, kd, dtype, ws, ws_bytes)) {
         const int nb = biu_mfma_conv_stat_rows(dx, kd, dy, dtype, true);     // one partial row per workgroup column (as the forward)
         if ((size_t)nb * dx->c * 2 <= partial_floats) {
@@ -167,7 +232,7 @@ extern "C" int biu_convt_bwd_data_bnred(const biu_act* dy, const float* w, const
     BIU_REQUIRE(scale && shift && mean && invstd && partial && nblk, BIU_ERR_SHAPE, "convt_bwd_data_bnred: null pointer");
     const size_t es = dsize(dtype);
     const bool yok = ((uintptr_t)y_up->p % 16) == 0 && ((size_t)y_up->pitch * es) % 16 == 0;
-    if (packed && yok && !disabled("convt_dgrad") && !disabled("dgrad_bnred") && biu_mfma_convt_ok(1, dx, dy, kd, dtype) &&
+    if (packed && yok && !biu_off("convt_dgrad") && !biu_off("dgrad_bnred") && biu_mfma_convt_ok(1, dx, dy, kd, dtype) &&
         biu_convt_all_ok(dx, dy, kd, dtype)) {
         const int nb = biu_convt_all_dgrad_rows(dx, dy, kd);           // one partial row per persistent block
         if ((size_t)nb * dx->c * 2 <= partial_floats) {
@@ -177,7 +242,7 @@ extern "C" int biu_convt_bwd_data_bnred(const biu_act* dy, const float* w, const
             return rc;
         }
     }
-    if (packed && yok && !disabled("convt_dgrad") && !disabled("dgrad_bnred") && biu_mfma_convt_ok(1, dx, dy, kd, dtype)) {
+    if (packed && yok && !biu_off("convt_dgrad") && !biu_off("dgrad_bnred") && biu_mfma_convt_ok(1, dx, dy, kd, dtype)) {
         const int nb = biu_mfma_convt_dgrad_rows(dx, kd);
         if ((size_t)nb * dx->c * 2 <= partial_floats) {
             BnRedFuse red{y_up, scale, shift, slope, mean, invstd};
@@ -205,17 +270,17 @@ extern "C" int biu_conv_bwd_weight(const biu_act* x, const biu_xform* xf, const 
                                    biu_stream stream) {
     BIU_REQUIRE(conv_args_ok(x, dy, kd, kh, kw, dilation), BIU_ERR_SHAPE, "conv_bwd_weight: x/dy extents differ");
     BIU_REQUIRE(dw, BIU_ERR_SHAPE, "conv_bwd_weight: null dw");
-    if (!disabled("c1") && biu_c1m_ok(x, dy, kd, kh, kw, dilation, dtype) && ws && ws_bytes >= biu_c1m_wgrad_workspace(dy->c, kd)) {
+    if (!biu_off("c1") && biu_c1m_ok(x, dy, kd, kh, kw, dilation, dtype) && ws && ws_bytes >= biu_c1m_wgrad_workspace(dy->c, kd)) {
         int rc = biu_c1m_wgrad(x, xf, dy, nullptr, kd, dw, ws, ws_bytes, (hipStream_t)stream);
         if (rc == BIU_OK && dbias) rc = biu_chan_sum(dy, dbias, dtype, (hipStream_t)stream);
         return rc;
     }
-    if (!disabled("c1") && biu_c1_conv_ok(x, dy, kd, kh, kw, dilation, dtype) && ws && ws_bytes >= biu_c1_wgrad_workspace(dy->c, kd)) {
+    if (!biu_off("c1") && biu_c1_conv_ok(x, dy, kd, kh, kw, dilation, dtype) && ws && ws_bytes >= biu_c1_wgrad_workspace(dy->c, kd)) {
         int rc = biu_c1_conv_wgrad(x, xf, dy, kd, dw, ws, ws_bytes, dtype, (hipStream_t)stream);
         if (rc == BIU_OK && dbias) rc = biu_chan_sum(dy, dbias, dtype, (hipStream_t)stream);
         return rc;
     }
-    if (!disabled("conv_wgrad") && biu_mfma_wgrad_ok(x, dy, kd, kh, kw, dilation, dtype)) {
+    if (!biu_off("conv_wgrad") && biu_mfma_wgrad_ok(x, dy, kd, kh, kw, dilation, dtype)) {
         BIU_REQUIRE(ws && ws_bytes >= biu_mfma_wgrad_workspace(x->c, dy->c, kd, kh, kw, dtype), BIU_ERR_WORKSPACE,
                     "conv_bwd_weight: workspace too small");
         return biu_mfma_wgrad(x, xf, dy, kd, kh, kw, dw, dbias, ws, ws_bytes, dtype, (hipStream_t)stream);
@@ -236,13 +301,13 @@ extern "C" int biu_conv_bwd_weight_bn(const biu_act* x, const biu_xform* xf, con
     const size_t es = dsize(dtype);
     const bool yok = ((uintptr_t)y->p % 16) == 0 && ((size_t)y->pitch * es) % 16 == 0 &&
                      (i64)y->d * y->h * y->w * y->pitch * (i64)es < (1LL << 32) - 65536;
-    if (!disabled("c1") && !disabled("wgrad_bn") && yok && biu_c1m_ok(x, da, kd, kh, kw, dilation, dtype) && ws &&
+    if (!biu_off("c1") && !biu_off("wgrad_bn") && yok && biu_c1m_ok(x, da, kd, kh, kw, dilation, dtype) && ws &&
         ws_bytes >= biu_c1m_wgrad_workspace(da->c, kd)) {
         // first layer: BatchNorm backward in the dy staging of the im2col weight gradient (da -> dy written back in the same pass)
         BnBwdFuse bn{y, scale, shift, slope, coefA, coefB, coefC};
         return biu_c1m_wgrad(x, xf, da, &bn, kd, dw, ws, ws_bytes, (hipStream_t)stream);
     }
-    if (!disabled("conv_wgrad") && !disabled("wgrad_bn") && yok && biu_mfma_wgrad_ok(x, da, kd, kh, kw, dilation, dtype)) {
+    if (!biu_off("conv_wgrad") && !biu_off("wgrad_bn") && yok && biu_mfma_wgrad_ok(x, da, kd, kh, kw, dilation, dtype)) {
         BIU_REQUIRE(ws && ws_bytes >= biu_mfma_wgrad_workspace(x->c, da->c, kd, kh, kw, dtype), BIU_ERR_WORKSPACE,
                     "conv_bwd_weight_bn: workspace too small");
         BnBwdFuse bn{y, scale, shift, slope, coefA, coefB, coefC};
@@ -259,7 +324,7 @@ extern "C" int biu_conv_bwd_weight_bn(const biu_act* x, const biu_xform* xf, con
 // holds it, the data gradient writes each output tile to its tensor.  MFMA shapes only (biu_conv_cat_ok says which).
 extern "C" int biu_conv_cat_ok(const biu_act* x0, const biu_act* x1, const biu_act* y, int kd, int kh, int kw, int dilation, int dtype) {
     if (!x0 || !x1 || !y || !valid_act(x0) || !valid_act(x1) || !valid_act(y) || !same_space(x0, y) || !same_space(x1, y)) return 0;
-    if (disabled("conv_fwd") || disabled("conv_dgrad") || disabled("conv_wgrad") || disabled("cat")) return 0;
+    if (biu_off("conv_fwd") || biu_off("conv_dgrad") || biu_off("conv_wgrad") || biu_off("cat")) return 0;
     return biu_mfma_conv_cat_ok(x0, x1, y, kd, kh, kw, dilation, dtype) ? 1 : 0;
 }
 extern "C" int biu_conv_fwd_cat(const biu_act* x0, const biu_xform* xf0, const biu_act* x1, const biu_xform* xf1, const float* w,
@@ -326,7 +391,7 @@ extern "C" int biu_convt_pack(int kind, const float* w, int cin, int cout, int k
 }
 // ---- nearest-neighbour up-sampling folded into the 3x3x3 convolution behind it (forward) ----------------------------------
 extern "C" int biu_upconv_ok(const biu_act* x, const biu_act* y, int dtype) {
-    return (x && y && !disabled("upconv") && biu_mfma_upconv_ok(x, y, dtype)) ? 1 : 0;
+    return (x && y && !biu_off("upconv") && biu_mfma_upconv_ok(x, y, dtype)) ? 1 : 0;
 }
 extern "C" size_t biu_upconv_packed_bytes(int kind, int cin, int cout, int dtype) { return biu_mfma_upconv_packed_bytes(kind, cin, cout, dtype); }
 extern "C" int biu_upconv_pack(int kind, const float* w, int cin, int cout, int dtype, void* packed, biu_stream stream) {
@@ -387,16 +452,10 @@ extern "C" int biu_foldt_ok(const biu_act* x_low, const biu_act* skip, const biu
     // BIU_FOLDT=always: wherever the kernels serve the level (the tests); BIU_FOLDT=cmax:N: exactly the levels whose coarse input has at
     // most N channels -- reproduces at test extents the pattern the size rule picks at a benchmark's extents (cfg4: cmax:128 = decode5 and
     // decode3 folded, decode1 through the 3-D ConvT + two-source kernels; tests/test_gpu_bench_dispatch.py)
-    static int always = -1, cmax = 0;
-    if (always < 0) {
-        const char* e = getenv("BIU_FOLDT");
-        const char* c = e ? strstr(e, "cmax:") : nullptr;
-        cmax = c ? atoi(c + 5) : 0;
-        always = (e && strstr(e, "always")) ? 1 : 0;
-    }
-    if (!(x_low && skip && y) || disabled("foldt") || !biu_mfma_foldt_ok(x_low, skip, y, dtype)) return 0;
-    if (cmax > 0) return x_low->c <= cmax ? 1 : 0;
-    return (always || biu_mfma_foldt_worth(x_low, y)) ? 1 : 0;
+    if (!(x_low && skip && y) || biu_off("foldt") || !biu_mfma_foldt_ok(x_low, skip, y, dtype)) return 0;
+    const BiuEnv& env = biu_env();
+    if (env.foldt_cmax > 0) return x_low->c <= env.foldt_cmax ? 1 : 0;
+    return (env.foldt_always || biu_mfma_foldt_worth(x_low, y)) ? 1 : 0;
 }
 extern "C" size_t biu_foldt_packed_bytes(int cin_low, int cskip, int cout, int dtype) { return biu_mfma_foldt_packed_bytes(cin_low, cskip, cout, dtype); }
 extern "C" int biu_foldt_pack(const float* w_conv, const float* b_conv, const float* w_t, const float* b_t, int cin_low, int cup, int cskip, int cout,
@@ -495,7 +554,7 @@ extern "C" int biu_convt_fwd(const biu_act* x, const biu_xform* xf, const float*
                              int kd, const biu_act* y, int dtype, biu_stream stream) {
     BIU_REQUIRE(valid_act(x) && valid_act(y) && w && biu_convt_shapes_ok(x, y, kd), BIU_ERR_SHAPE,
                 "convt_fwd: output must be 2x the input extent (kd=%d)", kd);
-    if (packed && !disabled("convt_fwd") && biu_mfma_convt_ok(0, x, y, kd, dtype)) {
+    if (packed && !biu_off("convt_fwd") && biu_mfma_convt_ok(0, x, y, kd, dtype)) {
         if (biu_convt_all_ok(x, y, kd, dtype)) return biu_convt_all_fwd(x, xf, packed, bias, kd, y, (hipStream_t)stream);     // all parities from one tile
         return biu_mfma_convt_fwd(x, xf, packed, bias, kd, y, dtype, (hipStream_t)stream);
     }
@@ -505,7 +564,7 @@ extern "C" int biu_convt_bwd_data(const biu_act* dy, const float* w, const void*
                                   int accumulate, int dtype, biu_stream stream) {
     BIU_REQUIRE(valid_act(dx) && valid_act(dy) && w && biu_convt_shapes_ok(dx, dy, kd), BIU_ERR_SHAPE,
                 "convt_bwd_data: dy must be 2x the dx extent (kd=%d)", kd);
-    if (packed && !disabled("convt_dgrad") && biu_mfma_convt_ok(1, dx, dy, kd, dtype)) {
+    if (packed && !biu_off("convt_dgrad") && biu_mfma_convt_ok(1, dx, dy, kd, dtype)) {
         if (biu_convt_all_ok(dx, dy, kd, dtype)) return biu_convt_all_dgrad(dy, packed, kd, dx, accumulate, (hipStream_t)stream);
         return biu_mfma_convt_dgrad(dy, packed, kd, dx, accumulate, dtype, (hipStream_t)stream);
     }
@@ -518,7 +577,7 @@ extern "C" int biu_convt_bwd_weight(const biu_act* x, const biu_xform* xf, const
                                     float* dbias, void* ws, size_t ws_bytes, int dtype, biu_stream stream) {
     BIU_REQUIRE(valid_act(x) && valid_act(dy) && dw && biu_convt_shapes_ok(x, dy, kd), BIU_ERR_SHAPE,
                 "convt_bwd_weight: dy must be 2x the x extent (kd=%d)", kd);
-    if (!disabled("convt_wgrad") && biu_mfma_convt_wgrad_ok(x, dy, kd, dtype)) {
+    if (!biu_off("convt_wgrad") && biu_mfma_convt_wgrad_ok(x, dy, kd, dtype)) {
         BIU_REQUIRE(ws && ws_bytes >= biu_mfma_wgrad_workspace(x->c, dy->c, kd, 2, 2, dtype), BIU_ERR_WORKSPACE,
                     "convt_bwd_weight: workspace too small");
         return biu_mfma_convt_wgrad(x, xf, dy, kd, dw, dbias, ws, ws_bytes, dtype, (hipStream_t)stream);

@@ -387,15 +387,10 @@ template <int KD, int HALF = 0> void bricks_of(C1Args& a) {
     a.nbricks = a.N * a.nbd * a.nbh * a.nbw;
 }
 
-bool off() {
-    static const bool v = [] { const char* e = getenv("BIU_DISABLE"); return e && strstr(e, "c1_mfma") != nullptr; }();
-    return v;
-}
-
 }  // namespace
 
 bool biu_c1m_ok(const biu_act* x, const biu_act* y, int kd, int kh, int kw, int dil, int dtype) {
-    if (off() || dtype != BIU_BF16 || x->c != 1 || dil != 1 || kh != 3 || kw != 3 || (kd != 1 && kd != 3)) return false;
+    if (biu_off("c1_mfma") || dtype != BIU_BF16 || x->c != 1 || dil != 1 || kh != 3 || kw != 3 || (kd != 1 && kd != 3)) return false;
     if (y->c % 16 != 0 || y->c < 16) return false;
     if ((uintptr_t)y->p % 16 || (y->pitch * 2) % 16 || (uintptr_t)x->p % 2) return false;
     return nvox(y) < (1LL << 31);

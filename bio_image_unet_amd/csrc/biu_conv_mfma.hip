@@ -74,12 +74,10 @@ struct f32x3_t { float v; };
 struct f32x6_t { float v; };
 template <> struct Frag<f32x3_t> : Frag<float> {};
 template <> struct Frag<f32x6_t> : Frag<float> {};
-// parts per value (0: not a split type), number of product terms, and the (a part, b part) of term t, small terms first
-template <typename T> struct SplitOf { static constexpr int parts = 0, terms = 0; };
-template <> struct SplitOf<f32x3_t> { static constexpr int parts = 2, terms = 3; };
-template <> struct SplitOf<f32x6_t> { static constexpr int parts = 3, terms = 6; };
-template <int XP> __device__ __forceinline__ constexpr int term_a(int t) { return XP == 2 ? (t == 0 ? 1 : 0) : (t == 0 ? 2 : t == 1 ? 0 : t == 2 ? 1 : t == 3 ? 1 : 0); }
-template <int XP> __device__ __forceinline__ constexpr int term_b(int t) { return XP == 2 ? (t == 1 ? 1 : 0) : (t == 0 ? 0 : t == 1 ? 2 : t == 2 ? 1 : t == 4 ? 1 : 0); }
+// parts per value (0: not a split type)
+template <typename T> struct SplitOf { static constexpr int parts = 0; };
+template <> struct SplitOf<f32x3_t> { static constexpr int parts = 2; };
+template <> struct SplitOf<f32x6_t> { static constexpr int parts = 3; };
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 template <int XP>
 __device__ __forceinline__ void split_bf16(const float (&f)[4], uint2 (&out)[XP]) {
@@ -206,35 +204,17 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_base_unifo
                  : "memory");
 }
 
+// Prefetch placement: the next item's n global loads are spread evenly over the ng MFMA slices: pf_lo(g, n, ng) is the first
+// piece slice g issues.
+constexpr int pf_lo(int g, int n, int ng) { return g >= ng ? n : (g * n) / ng; }
 // LDS a block may use for the activation tile + weight slabs (the transform vectors, partial sums come on top)
-#ifndef BIU_CONV_ILV
-#define BIU_CONV_ILV 1
-#endif
-// Prefetch placement: the next item's n global loads go out in the first BIU_PF_SPAN-th of the ng MFMA slices (1 = spread over all
-// of them, 2 = over the first half, ...): pf_lo(g, n, ng) is the first piece slice g issues.
-#ifndef BIU_PF_SPAN
-#define BIU_PF_SPAN 1
-#endif
-constexpr int pf_lo(int g, int n, int ng) {
-    const int span = (ng + BIU_PF_SPAN - 1) / BIU_PF_SPAN;
-    return g >= span ? n : (g * n) / span;
-}
-#ifndef BIU_TAIL_BRANCH
-#define BIU_TAIL_BRANCH 1
-#endif
-#ifndef BIU_TWO_PHASE_DIV
-#define BIU_TWO_PHASE_DIV 8
-#endif
-#ifndef BIU_WGRAD_RR
-#define BIU_WGRAD_RR 1
-#endif
 constexpr size_t conv_lds_budget(int nw) { return nw == 8 ? 142 * 1024 : 70 * 1024; }
 
 template <typename T, int KD, int KHW, int S, int TD, int TH, int TW, int NT, int CKP, bool RED, int NW>
 __global__ __launch_bounds__(NW * 64, 2) void k_conv_pipe(ConvArgs a) {
     using F = Frag<T>;
     constexpr int NTHR = NW * 64, NWAVE = NW;         // NW = 8: one block per CU; NW = 4: two (half the LDS each)
-    constexpr int XP = SplitOf<T>::parts, XT = SplitOf<T>::terms;
+    constexpr int XP = SplitOf<T>::parts;
     constexpr bool X3 = XP > 0;                               // fp32 tensors, split bf16 products: a chunk is 16 channels = planes [part][hf] of 8 bf16
     static_assert(!X3 || CKP == 4, "split-product chunks are 16 channels (4 fp32 pieces)");
     constexpr int PE = F::PE;
@@ -248,10 +228,7 @@ __global__ __launch_bounds__(NW * 64, 2) void k_conv_pipe(ConvArgs a) {
     constexpr int TILES = TD * TH * TW / 32;
     static_assert(TILES % NWAVE == 0, "brick must give a multiple of NW voxel tiles");
     constexpr int MT = TILES / NWAVE;
-#ifndef BIU_CONV_RH
-#define BIU_CONV_RH 1
-#endif
-    constexpr bool RH = BIU_CONV_RH && TW == 32 && S == 1 && KHW == 3 && MT >= 2 && TH % MT == 0;   // row-stacked fragment reuse
+    constexpr bool RH = TW == 32 && S == 1 && KHW == 3 && MT >= 2 && TH % MT == 0;   // row-stacked fragment reuse
     constexpr int TAPS = KD * KHW * KHW;
     constexpr int SPC = X3 ? XP : CKP / 2;                       // k-steps (weight fragments) per tap and chunk
     constexpr int ACT16 = X3 ? 2 * XP * PSV : CKP * PSV;         // activation tile, 16-byte units
@@ -687,36 +664,23 @@ __global__ __launch_bounds__(NW * 64, 2) void k_conv_pipe(ConvArgs a) {
         auto tapgroup = [&](int g0, int g1) {
             if constexpr (RH) window_h(g0, g1); else window(g0, g1);
         };
-        if constexpr (BIU_CONV_ILV) {
-            // ---- MFMA phase with the next item's global loads spread over its (kd, kh) tap groups: the address
-            //      unit takes the pieces one by one while the matrix cores run, instead of in a burst in front of them.
-            //      sched_barrier keeps the groups apart (a scheduler free to hoist LDS fragments across them spills).
-            constexpr int NG = KD * KHW;
-            issue_prep(have_next ? nbrick : brick, nch, have_next);
+        // ---- MFMA phase with the next item's global loads spread over its (kd, kh) tap groups: the address
+        //      unit takes the pieces one by one while the matrix cores run, instead of in a burst in front of them.
+        //      sched_barrier keeps the groups apart (a scheduler free to hoist LDS fragments across them spills).
+        constexpr int NG = KD * KHW;
+        issue_prep(have_next ? nbrick : brick, nch, have_next);
 #pragma unroll
-            for (int g = 0; g < NG; ++g) {
+        for (int g = 0; g < NG; ++g) {
 #pragma unroll
-                for (int j = pf_lo(g, NPA, NG); j < pf_lo(g + 1, NPA, NG); ++j) issue_piece(j);
-                if constexpr (!W1) {
+            for (int j = pf_lo(g, NPA, NG); j < pf_lo(g + 1, NPA, NG); ++j) issue_piece(j);
+            if constexpr (!W1) {
 #pragma unroll
-                    for (int j = pf_lo(g, NPW, NG); j < pf_lo(g + 1, NPW, NG); ++j) issue_wpiece(nch, have_next && !w_static, j);
-                }
-                tapgroup(g / KHW, g % KHW);
-                __builtin_amdgcn_sched_barrier(0);
+                for (int j = pf_lo(g, NPW, NG); j < pf_lo(g + 1, NPW, NG); ++j) issue_wpiece(nch, have_next && !w_static, j);
             }
-            DIAG_STAMP(1);
-        } else {
-            issue(have_next ? nbrick : brick, nch, have_next);
-            DIAG_STAMP(1);
-            // Only the innermost (kw, k-step) window is unrolled: a fully unrolled tap loop lets the scheduler hoist dozens
-            // of LDS fragments and spill -- and every spill reload carries an s_waitcnt vmcnt(0) that would serialise the
-            // prefetch loads issued above.
-#pragma unroll 1
-            for (int ta = 0; ta < KD; ++ta) {
-#pragma unroll 1
-                for (int tb = 0; tb < KHW; ++tb) tapgroup(ta, tb);
-            }
+            tapgroup(g / KHW, g % KHW);
+            __builtin_amdgcn_sched_barrier(0);
         }
+        DIAG_STAMP(1);
 
         DIAG_STAMP(2);
         // ---- brick finished: epilogue ----------------------------------------------------------------------------------
@@ -1334,12 +1298,6 @@ static inline i64 sample_bytes(const biu_act* t, size_t es) { return (i64)t->d *
 
 static bool chan_ok(int K, int Nn, int dtype) { return K >= 16 && K % ks_of(dtype) == 0 && Nn >= 16 && Nn % 8 == 0; }
 
-// 16-channel variant (k_conv16_pipe): eligible by channels alone, so the packed buffer carries its fragment image behind the regular one
-static bool m16_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("BIU_DISABLE"); v = (e && strstr(e, "m16")) ? 1 : 0; }
-    return v == 1;
-}
 // How the fp32 2-D 3x3 convolutions and ConvTranspose k2 -- forward, data gradient (reduction channels in chunks of 16) and weight gradient --
 // multiply (biu_set_fp32_products(mode), or BIU_FP32_PRODUCTS=exact|bf16x3|bf16x6 in the environment):
 //   2 = bf16x6 (DEFAULT): fp32-grade split products on the bf16 matrix pipe;  0 = exact: v_mfma_f32_32x32x2_f32;  1 = bf16x3 (opt-in, <= 2^-15 per product).
@@ -1350,10 +1308,7 @@ static bool g_x3_used = false;
 static std::mutex g_x3_mu;
 static int fp32_split_mode() {
     std::lock_guard<std::mutex> lock(g_x3_mu);
-    if (g_x3_mode < 0) {
-        const char* e = getenv("BIU_FP32_PRODUCTS");
-        g_x3_mode = (e && strstr(e, "bf16x3")) ? 1 : (e && strstr(e, "exact")) ? 0 : 2;
-    }
+    if (g_x3_mode < 0) g_x3_mode = biu_env().fp32_products;
     g_x3_used = true;
     return g_x3_mode;
 }
@@ -1376,12 +1331,11 @@ static int nks_of(int K, int kd, int dtype) { return x3_ok(K, kd, dtype) == 2 ? 
 static int m16_mtl(int K, int Nn, int dtype) {
     if (dtype != BIU_BF16 || K < 32 || K % 32 != 0) return 0;
     if (Nn == 16) return 1;
-    static int x2off = -1;
-    if (x2off < 0) { const char* e = getenv("BIU_DISABLE"); x2off = (e && strstr(e, "m16x2")) ? 1 : 0; }
-    if (!x2off && K == 32 && Nn >= 32 && Nn % 32 == 0) return 2;
+    if (!biu_off("m16x2") && K == 32 && Nn >= 32 && Nn % 32 == 0) return 2;
     return 0;
 }
 static bool m16_chan_ok(int K, int Nn, int dtype) { return m16_mtl(K, Nn, dtype) > 0; }
+// 16-channel variant (k_conv16_pipe): eligible by channels alone, so the packed buffer carries its fragment image behind the regular one
 static size_t m16_packed_bytes(int K, int Nn, int taps, int dtype) {
     const int mtl = m16_mtl(K, Nn, dtype);
     return mtl ? (size_t)((Nn + 16 * mtl - 1) / (16 * mtl)) * (K / 32) * taps * mtl * 1024 : 0;
@@ -1520,9 +1474,7 @@ static BrickDim conv3_brick(int kd, int nt, bool wide) {
 // Input-channel split of a 3x3(x3) fp32 launch (ConvArgs::ksplit): when bricks x channel tiles fill under half of the CUs and every
 // split still has >= 4 chunks of 8 channels.  1 = no split.  BIU_DISABLE=ksplit switches it off.
 int biu_mfma_conv_ksplit(int cin, const biu_act* y, int kd, int dtype) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("BIU_DISABLE"); off = (e && strstr(e, "ksplit")) ? 1 : 0; }
-    if (off || dtype != BIU_F32 || (kd != 1 && kd != 3)) return 1;
+    if (biu_off("ksplit") || dtype != BIU_F32 || (kd != 1 && kd != 3)) return 1;
     const int ntiles = (y->c + 31) / 32, nt = pick_nt(ntiles);
     const BrickDim b = conv3_brick(kd, nt, y->w % 32 == 0);
     const long blocks = (long)y->n * ((y->d + b.td - 1) / b.td) * ((y->h + b.th - 1) / b.th) * ((y->w + b.tw - 1) / b.tw) * (ntiles / nt);
@@ -1595,7 +1547,7 @@ int biu_mfma_convt_dgrad_rows(const biu_act* dx, int kd) {
 
 // the 16-row kernel takes a launch when the channels fit (m16_mtl), the input is one tensor and it is not switched off
 static bool m16_ok(const biu_act* x, const biu_act* y, int dtype) {
-    return x && !m16_disabled() && m16_chan_ok(x->c, y->c, dtype);
+    return x && !biu_off("m16") && m16_chan_ok(x->c, y->c, dtype);
 }
 static BrickDim m16_brick(int kd) { return kd == 3 ? BrickDim{4, 8, 16} : BrickDim{1, 32, 16}; }
 static int bricks_of(const biu_act* y, BrickDim b) {
@@ -2163,10 +2115,8 @@ static int launch_upconv(const ConvArgs& a, hipStream_t st) {
     // (a data-gradient chunk must lie in ONE parity class: a.Cin = channels per class there)
     // one output tile (decode5 of UNet3D(32)): 64-channel chunks -- half the items per brick, each with twice the MFMAs behind its two barriers;
     // the 98 KiB tile leaves room for one weight slab (decode5 forward call 1.217 -> 1.183 ms, same box; BIU_DISABLE=foldck8 for the A/B)
-    static int ck8 = -1;
-    if (ck8 < 0) { const char* e8 = getenv("BIU_DISABLE"); ck8 = (e8 && strstr(e8, "foldck8")) ? 0 : 1; }
     if constexpr (sizeof(T) == 2)
-        if (ck8 && nt == 1 && a.Cin % (8 * e) == 0) return launch_upconv_cfg<T, 1, 8>(a, ntiles, st);
+        if (!biu_off("foldck8") && nt == 1 && a.Cin % (8 * e) == 0) return launch_upconv_cfg<T, 1, 8>(a, ntiles, st);
     if (a.Cin % (4 * e) == 0) return nt == 1 ? launch_upconv_cfg<T, 1, 4>(a, ntiles, st) : launch_upconv_cfg<T, 2, 4>(a, ntiles, st);
     return nt == 1 ? launch_upconv_cfg<T, 1, 2>(a, ntiles, st) : launch_upconv_cfg<T, 2, 2>(a, ntiles, st);
 }
@@ -2502,9 +2452,7 @@ int biu_mfma_foldt_pack(const float* w_conv, const float* b_conv, const float* w
 // accumulating onto it with the BatchNorm statistics from its epilogue -- y is written twice and read once, rounded to the storage type twice
 // (three times and with a border pass in the brick form below).  BIU_DISABLE=froll keeps the brick form.
 static bool foldt_roll_ok(const biu_act* x_low, const biu_act* skip, const biu_act* y, int dtype) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("BIU_DISABLE"); off = (e && strstr(e, "froll")) ? 1 : 0; }
-    return !off && skip && biu_fold_roll_ok(x_low, y, dtype) && biu_conv_roll_ok(skip, y, dtype, false, 1, false);
+    return !biu_off("froll") && skip && biu_fold_roll_ok(x_low, y, dtype) && biu_conv_roll_ok(skip, y, dtype, false, 1, false);
 }
 int biu_mfma_foldt_form(const biu_act* x_low, const biu_act* skip, const biu_act* y, int dtype) { return foldt_roll_ok(x_low, skip, y, dtype) ? 1 : 0; }
 int biu_mfma_foldt_stat_rows(const biu_act* x_low, const biu_act* y, const biu_act* skip, int dtype) {
@@ -2621,7 +2569,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pipe(WgradArgs a) {
     constexpr int PPV = CT / PE;
     // X3 (T = f32x3_t): fp32 tensors, bf16x3 products -- the LDS tiles are TWO bf16 tiles each (hi plane, lo plane: split_bf16x3 while
     // committing), read through the bf16 kernels' transposing fragment reads; three MFMAs per (A, B) fragment pair
-    constexpr int XP = SplitOf<T>::parts, XT = SplitOf<T>::terms;      // (bf16x6: three planes, six MFMAs per fragment pair)
+    constexpr int XP = SplitOf<T>::parts;                  // (bf16x6: three planes, six MFMAs per fragment pair)
     constexpr bool X3 = XP > 0;
     constexpr bool BFM = sizeof(T) == 2 || X3;            // bf16 fragments (32x32x16) out of LDS
     constexpr int LES = BFM ? 2 : 4;                       // bytes per element of an LDS tile
@@ -2716,7 +2664,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pipe(WgradArgs a) {
     // plane it reads ONE new fragment per row instead of three.  The ninth pair (2, 2) has no wave of its own: its three taps are
     // the fourth slot of waves 0, 1, 2 (read per row like before).  2 + 2 (+ 2) transposed reads per row instead of 2 + 6 (+ 2):
     // the weight gradient's MFMAs are fed from LDS with little reuse, and LDS traffic is energy the power-limited kernel pays for.
-    constexpr bool RR = BIU_WGRAD_RR && sizeof(T) == 2 && KD == 3 && KHW == 3 && S == 1 && KSPLIT == 1 && NI == 1 && TW == 16 && IPW == 4 && WPQ == 8;
+    constexpr bool RR = sizeof(T) == 2 && KD == 3 && KHW == 3 && S == 1 && KSPLIT == 1 && NI == 1 && TW == 16 && IPW == 4 && WPQ == 8;
     int tapoff[IPW], tapid[IPW];
 #pragma unroll
     for (int t = 0; t < IPW; ++t) {
@@ -2981,10 +2929,11 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pipe(WgradArgs a) {
             WSTAMP(0);
             using FragR = typename std::conditional<BFM, bf16x8, float>::type;
             FragR fa[2][NI * NPL], fb[2][IPW * NPL];                  // split products: fa[.. * parts + part], part 0 = hi; their B fragments live in mfma_phase_split (fb unused)
+            // a second copy of the phase only where it removes >= 1/8 of the slots: 27 taps on 32; the 2-D kernels' 9 on 10 stay branch-free
+            constexpr bool TWO_PHASES = IPW > 1 && (IPW * WPQ - TAPS) * 8 >= IPW * WPQ;
             // 2-D fp32 kernels: 9 taps on 2 x 5 slots leave one empty; a second copy of the phase spills there, a wave-uniform branch around
             // the last slot's reads and 64-cycle MFMA does not (cfg2 weight gradients 96 -> 104-112 TFLOP/s)
-            constexpr bool TWO_PHASES_ = IPW > 1 && (IPW * WPQ - TAPS) * BIU_TWO_PHASE_DIV >= IPW * WPQ;
-            constexpr bool TAIL_BRANCH = BIU_TAIL_BRANCH && sizeof(T) == 4 && !TWO_PHASES_ && IPW > 1 && IPW * WPQ > TAPS;   // (bf16 2-D: measured neutral)
+            constexpr bool TAIL_BRANCH = sizeof(T) == 4 && !TWO_PHASES && IPW > 1 && IPW * WPQ > TAPS;   // (bf16 2-D: measured neutral)
             auto load_frags = [&](auto ntap_c, int kg, FragR (&af)[NI * NPL], FragR (&bfr)[IPW * NPL]) {
                 constexpr int NTAP = decltype(ntap_c)::value;
                 const int q0 = kg * KUNIT;
@@ -3138,10 +3087,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pipe(WgradArgs a) {
             auto mfma_phase = [&](auto ntap_c) {
             constexpr int NTAP = decltype(ntap_c)::value;
             if constexpr (FALL) { mfma_phase_all(); return; }
-#ifndef BIU_WGRAD_SPLIT_STEPPED
-#define BIU_WGRAD_SPLIT_STEPPED 1
-#endif
-            if constexpr (X3 && BIU_WGRAD_SPLIT_STEPPED) { mfma_phase_split(ntap_c); return; }
+            if constexpr (X3) { mfma_phase_split(ntap_c); return; }
             load_frags(ntap_c, wq * KPW, fa[0], fb[0]);
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
@@ -3158,28 +3104,14 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pipe(WgradArgs a) {
                 for (int kk = 0; kk < KPG; ++kk) {
                     const int idx = g * KPG + kk;
                     if (idx + 1 < KPW) load_frags(ntap_c, wq * KPW + idx + 1, fa[(idx + 1) & 1], fb[(idx + 1) & 1]);
-                    if constexpr (X3) {
-                        // lo * hi, hi * lo, hi * hi: term-major, so IPW * NI independent accumulators separate the dependent MFMAs
-#pragma unroll
-                        for (int term = 0; term < XT; ++term)
-#pragma unroll
-                            for (int t2 = 0; t2 < NTAP; ++t2)
-#pragma unroll
-                                for (int ni = 0; ni < NI; ++ni) {
-                                    if (TAIL_BRANCH && t2 == IPW - 1 && !last_tap_live) continue;
-                                    acc[t2][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[idx & 1][ni * NPL + term_a<X3 ? XP : 2>(term)], fb[idx & 1][t2 * NPL + term_b<X3 ? XP : 2>(term)],
-                                                                                         acc[t2][ni], 0, 0, 0);
-                                }
-                    } else {
 #pragma unroll
                     for (int t2 = 0; t2 < NTAP; ++t2)
 #pragma unroll
                         for (int ni = 0; ni < NI; ++ni) {
                             if (TAIL_BRANCH && t2 == IPW - 1 && !last_tap_live) continue;
-                            if constexpr (sizeof(T) == 2) acc[t2][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[idx & 1][ni], fb[idx & 1][t2], acc[t2][ni], 0, 0, 0);
+                            if constexpr (BFM) acc[t2][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[idx & 1][ni], fb[idx & 1][t2], acc[t2][ni], 0, 0, 0);
                             else acc[t2][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[idx & 1][ni], fb[idx & 1][t2], acc[t2][ni], 0, 0, 0);
                         }
-                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -3229,8 +3161,6 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_pipe(WgradArgs a) {
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
-            // (a second copy of the phase only where it removes >= 1/8 of the slots: 27 taps on 32; the 2-D kernels' 9 on 10 stay branch-free)
-            constexpr bool TWO_PHASES = IPW > 1 && (IPW * WPQ - TAPS) * BIU_TWO_PHASE_DIV >= IPW * WPQ;
             if constexpr (RR) {
                 using Full = std::integral_constant<int, TD * TH>;
                 using Half = std::integral_constant<int, TD * TH / 2>;
@@ -3846,19 +3776,8 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_roll(WgradArgs a) {
     }
 }
 
-static bool wroll_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("BIU_DISABLE"); v = (e && strstr(e, "wroll")) ? 1 : 0; }
-    return v == 1;
-}
-
 // Worth it when a column is long enough to amortise its prologue (two exposed fetch latencies per column) and there are enough columns
 // to give every block of a (plain tile, tapped tile) pair at least one.
-static bool wroll2d_disabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("BIU_DISABLE"); v = (e && strstr(e, "wroll2d")) ? 1 : 0; }
-    return v == 1;
-}
 static bool wroll_fits(const WgradArgs& a) {
     const int ncols = a.N * ((a.GH + WR_TH - 1) / WR_TH) * ((a.GW + WR_TW - 1) / WR_TW);
     return a.GD >= 8 && ncols >= 8;
@@ -3873,9 +3792,7 @@ static bool wroll2d_fits(const WgradArgs& a, i64 bytesA, i64 bytesB, i64 bytesY)
 
 static int launch_wgrad_roll(WgradArgs a, hipStream_t st, bool k2d = false) {
     if (k2d) { a.GD = a.BD = a.N; a.N = 1; }
-    static int a16off = -1;
-    if (a16off < 0) { const char* e = getenv("BIU_DISABLE"); a16off = (e && strstr(e, "wroll16")) ? 1 : 0; }
-    const bool a16 = !k2d && a.CA == 16 && !a16off;      // 16-channel plain operand: both planes of a step share the tile's 32 rows
+    const bool a16 = !k2d && a.CA == 16 && !biu_off("wroll16");      // 16-channel plain operand: both planes of a step share the tile's 32 rows
     a.nbd = 1;
     a.nbh = (a.GH + WR_TH - 1) / WR_TH;
     a.nbw = (a.GW + WR_TW - 1) / WR_TW;
@@ -4061,9 +3978,7 @@ int biu_mfma_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* dy, int
     // Small volumes with several input-channel tiles: the fused form runs as TWO launches (the first tile's blocks turn da into dy, the others
     // read the finished dy), each a fraction of the chip at these sizes (4 x 16^3: 32 + 96 blocks).  A separate BatchNorm-backward pass over a
     // tensor that lives in L2 costs less than the second launch's latency: 128 -> 256 @ 4 x 16^3 102 -> ~70 us.  (BIU_DISABLE=wsplitbn: fused)
-    static int split_off = -1;
-    if (split_off < 0) { const char* e = getenv("BIU_DISABLE"); split_off = (e && strstr(e, "wsplitbn")) ? 1 : 0; }
-    if (bn && !split_off && dtype == BIU_BF16 && kd == 3 && x->c + (x1 ? x1->c : 0) > 32 && nvox(dy) <= 4 * 32 * 32 * 32) {
+    if (bn && !biu_off("wsplitbn") && dtype == BIU_BF16 && kd == 3 && x->c + (x1 ? x1->c : 0) > 32 && nvox(dy) <= 4 * 32 * 32 * 32) {
         rc_ = biu_bn_bwd_apply(dy, bn->y, bn->scale, bn->shift, bn->slope, bn->cA, bn->cB, bn->cC, dy, dtype, (biu_stream)st);
         if (rc_ != BIU_OK) return rc_;
         bn = nullptr;
@@ -4096,16 +4011,14 @@ int biu_mfma_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* dy, int
     const size_t need = wgrad_acc_bytes(a.CA, a.CB, taps);
     BIU_REQUIRE(ws_bytes >= need + (dbias ? biu_chan_sum_workspace(dy->c) : 0), BIU_ERR_WORKSPACE, "wgrad_mfma: workspace %zu too small", ws_bytes);
     if (int zr = zero_ws(ws, need, nullptr, 0, st)) return zr;
-    static int rr16_off = -1;
-    if (rr16_off < 0) { const char* e = getenv("BIU_DISABLE"); rr16_off = (e && strstr(e, "rr16")) ? 1 : 0; }
-    if (dtype == BIU_BF16 && kd == 3 && a.CB == 16 && !x1 && !rr16_off) rc = launch_wgrad<bf16_t, 3, 3, 1, 4, 8, 16, 1, 1, true>(a, st);   // paired taps
-    else if (dtype == BIU_BF16 && kd == 3 && !wroll_disabled() && wroll_fits(a)) rc = launch_wgrad_roll(a, st);      // rolling window + LDS-DMA
-    else if (dtype == BIU_BF16 && kd == 1 && !wroll_disabled() && !wroll2d_disabled() &&
+    if (dtype == BIU_BF16 && kd == 3 && a.CB == 16 && !x1 && !biu_off("rr16")) rc = launch_wgrad<bf16_t, 3, 3, 1, 4, 8, 16, 1, 1, true>(a, st);   // paired taps
+    else if (dtype == BIU_BF16 && kd == 3 && !biu_off("wroll") && wroll_fits(a)) rc = launch_wgrad_roll(a, st);      // rolling window + LDS-DMA
+    else if (dtype == BIU_BF16 && kd == 1 && !biu_off("wroll") && !biu_off("wroll2d") &&
              wroll2d_fits(a, (i64)nvox(dy) * dy->pitch * 2, (i64)nvox(x) * x->pitch * 2 > (x1 ? (i64)nvox(x1) * x1->pitch * 2 : 0) ? (i64)nvox(x) * x->pitch * 2 : (i64)nvox(x1) * x1->pitch * 2,
                           bn ? (i64)nvox(bn->y) * bn->y->pitch * 2 : 0))
         rc = launch_wgrad_roll(a, st, true);                                                                                 // batch of images as the depth axis
     else if (dtype == BIU_BF16) rc = (kd == 3) ? launch_wgrad<bf16_t, 3, 3, 1, 4, 8, 16, 1>(a, st) : launch_wgrad<bf16_t, 1, 3, 1, 1, 16, 32, 4>(a, st);
-    else if (kd == 1 && fp32_split_mode() == 2) rc = launch_wgrad<f32x6_t, 1, 3, 1, 1, 16, 16, BIU_WGRAD_SPLIT_STEPPED ? 4 : 2>(a, st);  // fp32 tensors, bf16x6 products
+    else if (kd == 1 && fp32_split_mode() == 2) rc = launch_wgrad<f32x6_t, 1, 3, 1, 1, 16, 16, 4>(a, st);  // fp32 tensors, bf16x6 products
     else if (kd == 1 && fp32_split_mode() == 1) rc = launch_wgrad<f32x3_t, 1, 3, 1, 1, 16, 16, 4>(a, st);  // fp32 tensors, bf16x3 products
     else rc = (kd == 3) ? launch_wgrad<float, 3, 3, 1, 4, 4, 16, 1>(a, st) : launch_wgrad<float, 1, 3, 1, 1, 16, 16, 4>(a, st);
     if (rc != BIU_OK) return rc;
@@ -4168,11 +4081,8 @@ int biu_mfma_upconv_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* 
     BIU_REQUIRE(ws_bytes >= 8 * slice, BIU_ERR_WORKSPACE, "upconv_wgrad: workspace %zu too small (need %zu)", ws_bytes, 8 * slice);
     if (int zr = zero_ws(ws, 8 * slice, nullptr, 0, st)) return zr;
     a.fold_slice_f = slice / sizeof(float);
-    static int fall_off = -1;
-    if (fall_off < 0) { const char* e = getenv("BIU_DISABLE"); fall_off = (e && strstr(e, "foldall")) ? 1 : 0; }
-    static int fall_ca = -1;                               // (BIU_FALL_MAXCA moves the rule below for A/B runs)
-    if (fall_ca < 0) { const char* e = getenv("BIU_FALL_MAXCA"); fall_ca = e ? atoi(e) : 128; }
-    if (dtype == BIU_BF16 && a.CA <= fall_ca && bn == nullptr && !fall_off) {
+    // (BIU_FALL_MAXCA moves the channel limit for A/B runs)
+    if (dtype == BIU_BF16 && a.CA <= biu_env().fall_maxca && bn == nullptr && !biu_off("foldall")) {
         // all eight parity classes in one launch: wave = class, the coarse operand staged once per 2 x 4 x 16 brick (k_wgrad_pipe<..., FALL>);
         // plain dy only (no registers left for the y pieces of a fused BatchNorm backward).  Same-box: decode5 (dy 32 ch) 608 -> 410 us,
         // cfg4 step 12.69 -> 12.46 ms; with decode3 (dy 64 ch: two tiles, operands staged per tile) 12.30 ms; round 4, with the 32^3 level

@@ -121,34 +121,14 @@ __device__ __forceinline__ void rl_lrelu_affine8(float (&f)[8], const float* sc,
     }
 }
 
-// MFMA with the weight operand pinned to the accumulation-register file (BIU_ROLL_ASM): past 256 registers hipcc parks long-lived values in
-// AGPRs and copies them back (4 x v_accvgpr_read + a hazard s_nop) in front of EVERY use -- two VALU instructions per MFMA for weights that
-// could be read where they lie.  The asm form reads them in place; the hazards the compiler no longer sees are covered explicitly (results
-// are read by VALU only after the s_nop block in front of pack_pieces; a dependent MFMA on the same accumulator needs no wait states).
-#ifndef BIU_ROLL_ASM
-#define BIU_ROLL_ASM 0
-#endif
-#ifndef BIU_ROLL_SGB
-#define BIU_ROLL_SGB 0
-#endif
 #ifndef BIU_ROLL_ABL
 #define BIU_ROLL_ABL 0            // timing ablations (results are WRONG): bit 0 = no fetch inside the steps, bit 1 = no output stores / sums
 #endif
 __device__ __forceinline__ void rl_mfma32(floatx16& acc, const uint4& w, const uint4& b) {
-#if BIU_ROLL_ASM
-    const v4u_t wv = {w.x, w.y, w.z, w.w}, bv = {b.x, b.y, b.z, b.w};
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(wv), "v"(bv));
-#else
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-#endif
 }
 __device__ __forceinline__ void rl_mfma16(floatx4m& acc, const uint4& w, const uint4& b) {
-#if BIU_ROLL_ASM
-    const v4u_t wv = {w.x, w.y, w.z, w.w}, bv = {b.x, b.y, b.z, b.w};
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(wv), "v"(bv));
-#else
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-#endif
 }
 
 #ifdef BIU_DIAG
@@ -743,9 +723,6 @@ __global__ __launch_bounds__(256, 1) void k_conv_roll(RollArgs a) {
                     });
                 });
             });
-#if BIU_ROLL_ASM
-            asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");            // MFMA results -> VALU reads: wait states the compiler cannot count for an asm MFMA
-#endif
             pack_pieces(cur, park);                                     // the accumulators are free for the next step; its slots store `park`
             RL_STAMP(2);
             load_frags(frb[0], (s + 1) * PS - 1, 0);    // group 0 of the next step reads a plane that has been visible for a step
@@ -1191,15 +1168,7 @@ int roll_num_cus() {
 }
 
 // 0: off, 1: the size rule, 2: wherever the kernel serves the shapes (BIU_ROLL=always: the tests)
-int roll_mode() {
-    static int v = -1;
-    if (v < 0) {
-        const char* d = getenv("BIU_DISABLE");
-        const char* e = getenv("BIU_ROLL");
-        v = (d && strstr(d, "croll")) ? 0 : ((e && strstr(e, "always")) ? 2 : 1);
-    }
-    return v;
-}
+int roll_mode() { return biu_off("croll") ? 0 : biu_env().roll_always ? 2 : 1; }
 
 struct RollPlan { int ok, m, ps, la, nbh, nbw, nseg, seg, grid, cols; size_t lds; };
 

@@ -374,8 +374,7 @@ bool shapes_ok(const biu_act* lo, const biu_act* hi, int kd, int dtype) {
 }  // namespace
 
 bool biu_convt_all_ok(const biu_act* lo, const biu_act* hi, int kd, int dtype) {
-    static const bool off = [] { const char* e = getenv("BIU_DISABLE"); return e && strstr(e, "convt_all") != nullptr; }();
-    return !off && shapes_ok(lo, hi, kd, dtype);
+    return !biu_off("convt_all") && shapes_ok(lo, hi, kd, dtype);
 }
 
 int biu_convt_all_fwd(const biu_act* x, const biu_xform* xf, const void* packed, const float* bias, int kd, const biu_act* y, hipStream_t st) {

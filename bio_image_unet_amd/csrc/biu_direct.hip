@@ -1074,7 +1074,7 @@ extern "C" int biu_maxpool_bwd_bnred(const biu_act* x, const biu_xform* xf, cons
     int pd = pool_window(x, dout, "maxpool_bwd_bnred");
     if (!pd) return BIU_ERR_SHAPE;
     hipStream_t st = (hipStream_t)stream;
-    if (!getenv("BIU_NO_POOL_BNRED") && biu_rowvec_ok(x, dtype) && biu_rowvec_ok(dout, dtype) && biu_rowvec_ok(dx, dtype) &&
+    if (!biu_off("pool_bnred") && biu_rowvec_ok(x, dtype) && biu_rowvec_ok(dout, dtype) && biu_rowvec_ok(dx, dtype) &&
         x->c / 4 <= 256 && (size_t)(256 / (x->c / 4)) * x->c * 2 * sizeof(float) <= 64 * 1024)
         return biu_maxpool_bwd_bnred_rv(x, xf, dout, dx, pd, accumulate, mean, invstd, partial, partial_floats, nblk, dtype, st);
     int rc = biu_maxpool_bwd(x, xf, dout, dx, accumulate, dtype, stream);
@@ -1243,7 +1243,7 @@ extern "C" int biu_head_bwd_bnred(const biu_act* x, const biu_xform* xf, const f
                     cout <= HEAD_MAX_COUT, BIU_ERR_SHAPE, "head_bwd_bnred: bad arguments");
     BIU_REQUIRE(xf && xf->scale && xf->shift && mean && invstd && partial && nblk, BIU_ERR_SHAPE, "head_bwd_bnred: null vector");
     BIU_REQUIRE(partial_floats >= (size_t)BIU_BN_MAX_PARTIALS * x->c * 2, BIU_ERR_WORKSPACE, "head_bwd_bnred: partial buffer too small");
-    if (!getenv("BIU_NO_HEAD_BNRED") && biu_head_bwd_bnred_ok(x, dx, cout, dtype) && ws && ws_bytes >= biu_head_bwd_fused_workspace(x->c))
+    if (!biu_off("head_bnred") && biu_head_bwd_bnred_ok(x, dx, cout, dtype) && ws && ws_bytes >= biu_head_bwd_fused_workspace(x->c))
         return biu_head_bwd_bnred_fused(x, xf, w, cout, dlogits, dx, dw, dbias, ws, mean, invstd, partial, nblk, dtype, (hipStream_t)stream);
     int rc = biu_head_bwd(x, xf, w, cout, dlogits, dx, dw, dbias, ws, ws_bytes, dtype, stream);
     if (rc != BIU_OK) return rc;

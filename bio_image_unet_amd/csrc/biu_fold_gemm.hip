@@ -223,9 +223,7 @@ __global__ __launch_bounds__(256) void k_fold_chain_wt(const float* __restrict__
 // floats of scratch the two GEMM layouts take (W_conv's up channels as [k][co][c], W_T as [q][ci][c])
 size_t biu_fold_gemm_layout_floats(int cin_low, int cup, int cout) { return (size_t)27 * cout * cup + (size_t)8 * cin_low * cup; }
 bool biu_fold_gemm_ok(int cin_low, int cup, int cout) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("BIU_DISABLE"); off = (e && strstr(e, "foldgemm")) ? 1 : 0; }
-    return !off && cin_low % 4 == 0 && cup % 4 == 0 && cout % 4 == 0;
+    return !biu_off("foldgemm") && cin_low % 4 == 0 && cup % 4 == 0 && cout % 4 == 0;
 }
 int biu_fold_gemm_layouts(const float* w_conv, int ccat, int cup, int cout, const float* w_t, int cin_low, float* layouts, hipStream_t st) {
     const long n = (long)biu_fold_gemm_layout_floats(cin_low, cup, cout);

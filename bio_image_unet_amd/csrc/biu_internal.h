@@ -2,6 +2,19 @@
 #pragma once
 #include "biu_common.h"
 
+// biu_api.hip: everything the library takes from the environment, parsed once per process on first use ("A/B and
+// debug switches").  biu_off(token): `token` is one whole entry of BIU_DISABLE's comma-separated list.
+struct BiuEnv {
+    unsigned long long off;   // bit i: BIU_DISABLE names the i-th token of the library's token table
+    bool roll_always;         // BIU_ROLL=always: the rolling-window kernels wherever they serve the shapes
+    bool foldt_always;        // BIU_FOLDT=always: every decoder level the folded kernels serve
+    int foldt_cmax;           // BIU_FOLDT=cmax:N: exactly the levels whose coarse input has at most N channels (0: the size rule)
+    int fp32_products;        // BIU_FP32_PRODUCTS: 0 exact, 1 bf16x3, 2 bf16x6 (default)
+    int fall_maxca;           // BIU_FALL_MAXCA: channel limit of the one-launch folded weight gradient (default 128)
+};
+const BiuEnv& biu_env();
+bool biu_off(const char* token);
+
 // biu_direct.hip (C linkage, hidden: these cross translation units of the library, they are not part of include/biu.h)
 #define BIU_HIDDEN __attribute__((visibility("hidden")))
 extern "C" BIU_HIDDEN int biu_conv_fwd_direct(const biu_act* x, const biu_xform* xf, const float* w, const float* bias, int kd,

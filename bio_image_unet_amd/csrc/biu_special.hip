@@ -352,9 +352,7 @@ static int c1_wgrad_t(const biu_act* x, const biu_xform* xf, const biu_act* dy, 
             hipLaunchKernelGGL((k_conv_c1_wgrad<T, 32, KD, TPW>), dim3(nblk), dim3(64 * ((TAPS + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
         } else if (rem >= 16) {
             constexpr int TPW = 7; chunk = 16;
-            static const bool tpw4 = [] { const char* e = getenv("BIU_C1_TPW"); return e && e[0] == '4'; }();       // experiment switch
-            if (dy->w % 4 == 0 && tpw4) hipLaunchKernelGGL((k_conv_c1_wgrad4<T, 16, KD, 4>), dim3(nblk), dim3(64 * ((TAPS + 3) / 4)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
-            else if (dy->w % 4 == 0) hipLaunchKernelGGL((k_conv_c1_wgrad4<T, 16, KD, TPW>), dim3(nblk), dim3(64 * ((TAPS + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
+            if (dy->w % 4 == 0) hipLaunchKernelGGL((k_conv_c1_wgrad4<T, 16, KD, TPW>), dim3(nblk), dim3(64 * ((TAPS + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
             else hipLaunchKernelGGL((k_conv_c1_wgrad<T, 16, KD, TPW>), dim3(nblk), dim3(64 * ((TAPS + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
         } else {
             constexpr int TPW = 9; chunk = 8;
@@ -1126,9 +1124,8 @@ __global__ __launch_bounds__(TPB, sizeof(T) * PE >= 16 ? 2 : 4) void k_maxpool_b
 }
 // lanes per pooled voxel = 2 * C / PE must fit a wave and divide the block: C / PE a power of two <= 32
 static bool pool_pair_ok(int C, int PE) {
-    static const bool off = [] { const char* e = getenv("BIU_DISABLE"); return e && strstr(e, "pool_pair") != nullptr; }();
     const int cg = C / PE;
-    return !off && C % PE == 0 && cg >= 1 && cg <= 32 && (cg & (cg - 1)) == 0;      // (callers: bf16 only -- the fp32 one-lane kernel already runs at 5 TB/s)
+    return !biu_off("pool_pair") && C % PE == 0 && cg >= 1 && cg <= 32 && (cg & (cg - 1)) == 0;      // (callers: bf16 only -- the fp32 one-lane kernel already runs at 5 TB/s)
 }
 static RowPlan pool_pair_plan(const biu_act* x, const biu_act* dout, int PE, i64 max_blocks) {
     RowPlan p;
@@ -1151,8 +1148,7 @@ static int pool_rv_launch(const biu_act* x, const biu_xform* xf, const biu_act* 
 }
 int biu_xform_apply_rv(const biu_act* x, const biu_xform* xf, const biu_act* out, int dtype, hipStream_t st) { return pool_rv_launch<0>(x, xf, out, nullptr, 1, 0, dtype, st); }
 int biu_maxpool_fwd_rv(const biu_act* x, const biu_xform* xf, const biu_act* out, int pd, int dtype, hipStream_t st) {
-    static const bool off = [] { const char* e = getenv("BIU_DISABLE"); return e && strstr(e, "pool_pipe") != nullptr; }();
-    if (off) return pool_rv_launch<1>(x, xf, out, nullptr, pd, 0, dtype, st);
+    if (biu_off("pool_pipe")) return pool_rv_launch<1>(x, xf, out, nullptr, pd, 0, dtype, st);
     BIU_DISPATCH_DTYPE(dtype, {
         constexpr int PE = 16 / sizeof(T);
         RowPlan p = row_plan(nvox(out), x->c, PE);

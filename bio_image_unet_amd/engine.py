@@ -36,10 +36,18 @@ def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _disabled(token: str, env: Optional[str] = None) -> bool:
+    """Is `token` one whole entry of BIU_DISABLE's comma-separated list (`env`: that list instead of the environment's)?  The library
+    matches its own tokens the same way ("A/B and debug switches")."""
+    return token in (os.environ.get("BIU_DISABLE", "") if env is None else env).split(",")
+
+
 # Under stream capture the side stream forks off the capturing stream (wait_event on an event recorded there) and is joined again by the waits
 # the eager path makes anyway (the decoder's first use of the composed weights; the hand-over of the deferred gradients), so the captured graph
 # holds the same two branches.  BIU_DISABLE=capturefork keeps a captured step single-stream.
-_NO_CAPTURE_FORK = os.environ.get("BIU_DISABLE", "").find("capturefork") >= 0
+_NO_CAPTURE_FORK = _disabled("capturefork")
+_NO_SIDE_CHAIN = _disabled("sidechain")      # the chain rule of the folded weight gradients in line (chain_stream)
+_NO_PREPACK = _disabled("prepack")           # composed weights packed where the decoder needs them (_prepack_folds)
 # voxels up to which a 3-D block's weight gradient runs on the side stream beside its data gradient (BIU_SIDE_WGRAD_VOX=0: never)
 _SIDE_WGRAD_VOX = int(os.environ.get("BIU_SIDE_WGRAD_VOX", str(4 * 32 ** 3)))
 
@@ -976,7 +984,6 @@ class Engine:
         self._live = None            # weakref to the token of the autograd node that still needs this engine's buffers
         self._side = None            # side stream of the composed-weight packing of the folded decoder levels (_prepack_folds) and of their chain rule
         self._deferred = []
-        self._no_side_chain = os.environ.get("BIU_DISABLE", "").find("sidechain") >= 0
         self._fold_ev = None
 
     def busy(self) -> bool:
@@ -1174,7 +1181,7 @@ class Engine:
         parameters only: packed at the START of the forward on a side stream, they run beside the encoder instead of in front of the decoder
         (the decoder's first use waits on the event).  Not under stream capture (a captured step packs in line)."""
         self._fold_ev = None
-        if os.environ.get("BIU_DISABLE", "").find("prepack") >= 0 or (torch.cuda.is_current_stream_capturing() and _NO_CAPTURE_FORK):
+        if _NO_PREPACK or (torch.cuda.is_current_stream_capturing() and _NO_CAPTURE_FORK):
             return
         stale = [n for n in self.nodes if isinstance(n, ConvBlockNode) and n.foldt is not None and n.foldt_ver != n._foldt_version()]
         if not stale:
@@ -1218,7 +1225,7 @@ class Engine:
     def chain_stream(self):
         """Side stream for work only the optimizer waits for (the chain rule of the folded decoder levels), or None: under stream capture, while a
         trace hook compares intermediate results, or with BIU_DISABLE=sidechain."""
-        if self.trace or self._no_side_chain or (torch.cuda.is_current_stream_capturing() and _NO_CAPTURE_FORK):
+        if self.trace or _NO_SIDE_CHAIN or (torch.cuda.is_current_stream_capturing() and _NO_CAPTURE_FORK):
             return None
         if self._side is None:
             self._side = torch.cuda.Stream(device=self.device)

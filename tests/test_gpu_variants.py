@@ -1,7 +1,9 @@
 """The kernel variants a launch can take must agree with the kernels they replace: the 16-row MFMA kernel (BIU_DISABLE=m16 falls back to
-the 32-row one), the paired-tap weight gradient of a 16-channel input (BIU_DISABLE=rr16), the rolling-window weight gradient (BIU_DISABLE=wroll), the one-launch folded weight gradient (BIU_DISABLE=foldall), the input-channel split of small fp32 launches (BIU_DISABLE=ksplit) and the opt-in bf16x3 products of the fp32 2-D kernels
-(BIU_FP32_PRODUCTS=bf16x3) against the exact fp32 MFMA.  The switches are read once per process, so
-each side runs in its own subprocess (tests/variant_probe.py)."""
+the 32-row one, m16x2 only its two-tile form), the paired-tap weight gradient of a 16-channel input (BIU_DISABLE=rr16), the rolling-window
+weight gradient (BIU_DISABLE=wroll; wroll16 / wroll2d one form of it each), the one-launch folded weight gradient (BIU_DISABLE=foldall), the
+input-channel split of small fp32 launches (BIU_DISABLE=ksplit) and the opt-in bf16x3 products of the fp32 2-D kernels
+(BIU_FP32_PRODUCTS=bf16x3) against the exact fp32 MFMA.  BIU_DISABLE names whole tokens (m16x2 does not switch off m16).  The switches
+are read once per process, so each side runs in its own subprocess (tests/variant_probe.py)."""
 import os
 import subprocess
 import sys

@@ -1,6 +1,6 @@
 """CPU-side checks (no GPU): the C-ABI library loads and exports every symbol of include/biu.h, the model classes carry
-the reference's state_dict schema, the product refuses CPU tensors loudly, losses equal the oracle's, and the gradient
-averager works across two gloo ranks."""
+the reference's state_dict schema, the product refuses CPU tensors loudly, losses equal the oracle's, the gradient
+averager works across two gloo ranks, and the environment switches are read in one place and matched as whole tokens."""
 import os
 import re
 import subprocess
@@ -44,6 +44,81 @@ def test_fp32_product_mode_switch_validates_its_argument():
     with pytest.raises(ValueError):
         B.set_fp32_products("tf32")
     B.set_fp32_products("exact")
+
+
+CSRC = os.path.join(ROOT, "bio_image_unet_amd", "csrc")
+
+
+def _csrc():
+    return {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h"))}
+
+
+def test_disable_tokens_match_the_documented_table():
+    """INTEGRATION.md's BIU_DISABLE table and the library's token table name the same tokens, and every token the library or the engine
+    tests is in that table."""
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    rows = doc.split("| value | effect |", 1)[1].split("\n\n", 1)[0].splitlines()[2:]
+    documented = {t for r in rows for t in re.findall(r"`([a-z0-9_]+)`", r.split("|")[1])}
+    lib_src = _csrc()["biu_api.hip"]
+    table = re.search(r"kOffTokens\[\] = \{(.*?)\};", lib_src, re.S).group(1)
+    library = set(re.findall(r'"([a-z0-9_]+)"', table))
+    assert documented and library
+    assert not documented - library, f"documented but unknown to the library: {sorted(documented - library)}"
+    assert not library - documented, f"known to the library but not documented: {sorted(library - documented)}"
+    used = {t for s in _csrc().values() for t in re.findall(r'biu_off\("([a-z0-9_]+)"\)', s)}
+    used |= set(re.findall(r'_disabled\("([a-z0-9_]+)"\)', open(os.path.join(ROOT, "bio_image_unet_amd", "engine.py")).read()))
+    assert used and not used - library, f"tested but not in the token table: {sorted(used - library)}"
+
+
+def test_environment_is_read_in_one_function():
+    """getenv( occurs under csrc/ only inside biu_env() (biu_api.hip)."""
+    for f, s in _csrc().items():
+        hits = [m.start() for m in re.finditer(r"\bgetenv\(", s)]
+        if f != "biu_api.hip":
+            assert not hits, f"{f} reads the environment"
+            continue
+        start = s.index("const BiuEnv& biu_env() {")
+        depth, end = 0, None
+        for i in range(s.index("{", start), len(s)):
+            depth += {"{": 1, "}": -1}.get(s[i], 0)
+            if depth == 0:
+                end = i
+                break
+        assert hits and all(start < h < end for h in hits), "getenv outside biu_env()"
+
+
+_FOLDT_PROBE = r"""
+import ctypes as C, sys
+sys.path.insert(0, sys.argv[1])
+import bio_image_unet_amd._lib as L
+def act(addr, n, d, h, w, c):
+    a = L.biu_act(); a.p, a.n, a.d, a.h, a.w, a.c, a.pitch = addr, n, d, h, w, c, c
+    return a
+# descriptors of a decoder level (never dereferenced: biu_foldt_ok checks shapes and alignment on the host only)
+x_low, skip, y = act(1 << 20, 2, 8, 16, 16, 64), act(2 << 20, 2, 16, 32, 32, 32), act(3 << 20, 2, 16, 32, 32, 32)
+print("FOLDT", L.lib.biu_foldt_ok(C.byref(x_low), C.byref(skip), C.byref(y), L.BIU_BF16))
+"""
+
+
+@pytest.mark.parametrize("disable,folded", [("foldt", 0), ("foldtx", 1), ("m16,foldt", 0)])
+def test_disable_matches_whole_tokens(disable, folded):
+    """BIU_DISABLE=foldtx does not switch the fold off; it is named once on stderr (a child process: the library reads it once)."""
+    env = dict(os.environ, BIU_FOLDT="always", BIU_DISABLE=disable)
+    r = subprocess.run([sys.executable, "-c", _FOLDT_PROBE, ROOT], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert f"FOLDT {folded}" in r.stdout
+    warned = [ln for ln in r.stderr.splitlines() if ln.startswith("[biu]")]
+    if disable == "foldtx":
+        assert len(warned) == 1 and "foldtx" in warned[0], r.stderr
+    else:
+        assert not warned, r.stderr
+
+
+def test_engine_disable_helper_matches_whole_tokens():
+    from bio_image_unet_amd.engine import _disabled
+    assert _disabled("sidechain", "sidechain,prepack") and _disabled("prepack", "sidechain,prepack")
+    assert not _disabled("sidechain", "sidechainx") and not _disabled("prepack", "sidechainx")
+    assert not _disabled("sidechain", "")
 
 
 @pytest.mark.parametrize("case", ["unet2d_f4", "unet2d_f4_o2_dil2", "unet3d_f4", "siam_f4_concat", "siam_f4_max", "mo3d_f4_interp", "mo3d_f4_convT"])

@@ -1,10 +1,11 @@
 """GPU diagnostic: per-parameter gradient error of the HIP engine against the oracle.
 
-  fp32: HIP vs the fp64 oracle under several BIU_DISABLE settings (which kernel family moves the error?)
+  fp32: HIP vs the fp64 oracle under several BIU_DISABLE settings (which kernel family moves the error?); the library reads the
+        switches once per process, so every HIP run is a child process of this script
   bf16: HIP vs the bf16-storage emulation of the oracle (same rounding points) and vs fp64
 Usage: python tools/diag_grad.py [unet2d|unet3d] > gpurun_out/diag_grad.txt
 """
-import os, sys
+import os, subprocess, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bio_image_unet_amd as B
@@ -43,6 +44,19 @@ def hip(dtype):
     return logits.detach().cpu(), {k: p.grad.cpu() for k, p in m.named_parameters()}
 
 
+if len(sys.argv) > 4 and sys.argv[2] == "--hip":      # child: one HIP run under this process's BIU_DISABLE
+    torch.save(hip(sys.argv[3]), sys.argv[4])
+    sys.exit(0)
+
+
+def hip_child(dtype, dis):
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "hip.pt")
+        subprocess.run([sys.executable, os.path.abspath(__file__), kind, "--hip", dtype, out], check=True, timeout=600,
+                       env=dict(os.environ, BIU_DISABLE=dis))
+        return torch.load(out)
+
+
 def errs(g, truth):
     gs = max(float(v.abs().max()) for v in truth.values())
     out = {}
@@ -65,13 +79,11 @@ l32, g32 = oracle(torch.float32, False)
 show("CPU fp32 oracle vs fp64", errs(g32, gt))
 for dis in ["", "fused_stats", "dgrad_bnred", "wgrad_bn", "conv_fwd", "conv_dgrad", "conv_wgrad", "convt_fwd,convt_dgrad,convt_wgrad",
             "conv_fwd,conv_dgrad", "fused_stats,dgrad_bnred,wgrad_bn"]:
-    os.environ["BIU_DISABLE"] = dis
-    lh, gh = hip("f32")
+    lh, gh = hip_child("f32", dis)
     print(f"[fp32 BIU_DISABLE='{dis}'] logits err {float((lh.double() - lt).abs().max() / lt.abs().max()):.2e}")
     show("   HIP fp32 vs fp64", errs(gh, gt))
-os.environ["BIU_DISABLE"] = ""
 le, ge = oracle(torch.float32, True)
-lh, gh = hip("bf16")
+lh, gh = hip_child("bf16", "")
 print(f"[bf16] logits: HIP vs emulation {float((lh - le).abs().max() / le.abs().max()):.2e}; emulation vs fp64 {float((le.double() - lt).abs().max() / lt.abs().max()):.2e}")
 print(f"[bf16] masks differ from emulation at {int(((lh > 0) != (le > 0)).sum())} of {lh.numel()} voxels")
 show("   HIP bf16 vs emulation", errs(gh, ge), 10)

@@ -35,7 +35,7 @@ static bool parse_int(const char* s, int* v) {
 
 const BiuEnv& biu_env() {
     static const BiuEnv env = [] {
-        BiuEnv v{0, false, false, 0, 2, 128};
+        BiuEnv v{0, false, false, 0, 2, 0, 128};
         if (const char* p = getenv("BIU_DISABLE")) {
             while (true) {
                 const size_t n = strcspn(p, ",");
@@ -60,6 +60,11 @@ const BiuEnv& biu_env() {
             if (strcmp(e, "exact") == 0) v.fp32_products = 0;
             else if (strcmp(e, "bf16x3") == 0) v.fp32_products = 1;
             else if (strcmp(e, "bf16x6") != 0) env_unknown("BIU_FP32_PRODUCTS", e, (int)strlen(e));
+        }
+        if (const char* e = getenv("BIU_FP32_PRODUCTS_3D"); e && *e) {
+            if (strcmp(e, "bf16x3") == 0) v.fp32_products_3d = 1;
+            else if (strcmp(e, "bf16x6") == 0) v.fp32_products_3d = 2;
+            else if (strcmp(e, "exact") != 0) env_unknown("BIU_FP32_PRODUCTS_3D", e, (int)strlen(e));
         }
         if (const char* e = getenv("BIU_FALL_MAXCA"); e && *e) {
             int n = 0;
@@ -243,7 +248,7 @@ extern "C" int biu_convt_bwd_data_bnred(const biu_act* dy, const float* w, const
         }
     }
     if (packed && yok && !biu_off("convt_dgrad") && !biu_off("dgrad_bnred") && biu_mfma_convt_ok(1, dx, dy, kd, dtype)) {
-        const int nb = biu_mfma_convt_dgrad_rows(dx, kd);
+        const int nb = biu_mfma_convt_dgrad_rows(dx, kd, dy->c, dtype);
         if ((size_t)nb * dx->c * 2 <= partial_floats) {
             BnRedFuse red{y_up, scale, shift, slope, mean, invstd};
             int rc = biu_mfma_convt_dgrad(dy, packed, kd, dx, 0, dtype, (hipStream_t)stream, partial, &red);
@@ -343,7 +348,7 @@ extern "C" int biu_conv_fwd_cat(const biu_act* x0, const biu_xform* xf0, const b
     }
     if (bn_partial) {
         BIU_REQUIRE(bn_nblk, BIU_ERR_SHAPE, "conv_fwd_cat: null bn_nblk");
-        const int nb = biu_mfma_conv_stat_rows(y, kd);
+        const int nb = dtype == BIU_F32 ? biu_mfma_conv_stat_rows(y, kd, x0, dtype, false, x0->c + x1->c) : biu_mfma_conv_stat_rows(y, kd);
         BIU_REQUIRE((size_t)nb * y->c * 2 <= bn_partial_floats, BIU_ERR_WORKSPACE, "conv_fwd_cat: partial buffer too small");
         int rc = biu_mfma_conv(x0, xf0, packed, bias, kd, kh, kw, y, 0, bn_partial, dtype, (hipStream_t)stream, nullptr, &cat);
         if (rc == BIU_OK) *bn_nblk = nb;

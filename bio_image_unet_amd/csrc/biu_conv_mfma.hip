@@ -1320,8 +1320,49 @@ int biu_mfma_set_fp32_products(int mode) {
     g_x3_mode = mode;
     return BIU_OK;
 }
+// The same choice for the fp32 3-D kernels (kd = 2 | 3: 3x3x3 conv, ConvTranspose3d k2 s2), on a latch of its own (biu_set_fp32_products_3d,
+// BIU_FP32_PRODUCTS_3D): default 0 = exact, 1 / 2 opt-in.  Size queries latch it as launches do: they fix the packed image.
+static int g_x3_mode_3d = -1;
+static bool g_x3_used_3d = false;
+static std::mutex g_x3_mu_3d;
+static int fp32_split_mode_3d() {
+    std::lock_guard<std::mutex> lock(g_x3_mu_3d);
+    if (g_x3_mode_3d < 0) g_x3_mode_3d = biu_env().fp32_products_3d;
+    g_x3_used_3d = true;
+    return g_x3_mode_3d;
+}
+int biu_mfma_set_fp32_products_3d(int mode) {
+    std::lock_guard<std::mutex> lock(g_x3_mu_3d);
+    if (mode < 0 || mode > 2) return biu_fail(BIU_ERR_UNSUPPORTED, "set_fp32_products_3d: mode %d (0 = exact fp32 MFMA, 1 = bf16x3, 2 = bf16x6)", mode);
+    if (g_x3_used_3d && g_x3_mode_3d != mode)
+        return biu_fail(BIU_ERR_UNSUPPORTED, "set_fp32_products_3d: fp32 3-D kernels already ran in another mode (set it before the first forward)");
+    g_x3_mode_3d = mode;
+    return BIU_OK;
+}
+// product mode of the fp32 kernels of depth kd: the 2-D mode for kd == 1, the 3-D mode for kd = 2 | 3 (0 = exact; the weight gradients, which
+// pack nothing, ask this alone)
+static int x3_mode_of(int kd, int dtype) {
+    if (dtype != BIU_F32) return 0;
+    if (kd == 1) return fp32_split_mode();
+    return (kd == 2 || kd == 3) ? fp32_split_mode_3d() : 0;
+}
+// Widest reduction (Cin of the launch: its 3 x Cin transform floats share LDS with the tile) a 3x3x3 split launch takes: halo tile of
+// split3_brick + one 27-tap slab + epilogue partials of one output tile must fit the 160 KiB of the block (mirrors launch_cfg_r)
+constexpr int split3_kmax(int xp, int td, int th, int tw) {
+    return (int)(((size_t)160 * 1024 - ((size_t)2 * xp * cpad_planes((td + 2) * (th + 2) * (tw + 2), 4) + (size_t)27 * xp * 64) * 16 -
+                  (size_t)32 * (2 * 8 + 4) * sizeof(float)) / 12) / 16 * 16;
+}
+constexpr int kSplit3KmaxX6 = split3_kmax(3, 4, 4, 16), kSplit3KmaxX3 = split3_kmax(2, 4, 8, 16);     // 1328, 3056
 // split mode of a launch with K reduction channels (0: the exact fp32 kernels take it)
-static int x3_ok(int K, int kd, int dtype) { return (dtype == BIU_F32 && kd == 1 && K >= 16 && K % 16 == 0) ? fp32_split_mode() : 0; }
+static int x3_ok(int K, int kd, int dtype) {
+    if (dtype != BIU_F32 || K < 16 || K % 16 != 0) return 0;
+    const int m = x3_mode_of(kd, dtype);
+    if (kd == 3 && K > (m == 2 ? kSplit3KmaxX6 : kSplit3KmaxX3)) return 0;
+    return m;
+}
+// ... of a ConvTranspose data gradient (stride-2 gather of the fine tensor): in 3-D the halo of a 256-voxel brick is 2048 fine voxels -- 192 KiB
+// at bf16x6 (no fit), 128 KiB at bf16x3 (fits, but spills 48 B/lane) -- so that launch and its packed image stay exact there
+static int x3_convt_dg(int K, int kd, int dtype) { return kd == 2 ? 0 : x3_ok(K, kd, dtype); }
 // k-steps (packed weight fragments per tap and row tile) of a layer with K reduction channels
 static int nks_of(int K, int kd, int dtype) { return x3_ok(K, kd, dtype) == 2 ? K / 16 * 3 : K / (dtype == BIU_BF16 ? 16 : 8); }
 // 16-row tiles per block column of the 16x16x32 kernel for a layer with K reduction and Nn output channels (0: the layer does not take it):
@@ -1471,12 +1512,18 @@ static BrickDim conv3_brick(int kd, int nt, bool wide) {
     return wide ? BrickDim{1, 16, 32} : BrickDim{1, 32, 16};
 }
 
+// fp32 3x3x3 as split bf16 products (NT = 1: one 27-tap weight slab of three bf16 parts is already 81 KiB): the brick per mode, picked so that
+// halo tile + slab fit the 142 KiB of one 8-wave block's DMA-fed slab (no weight registers, no scratch) -- bf16x6: 4x4x16 (6x6x18 halo at 96 B
+// = 61 KiB + 81 KiB), bf16x3: 4x8x16 (6x10x18 at 64 B = 68 KiB + 54 KiB)
+static BrickDim split3_brick(int xm) { return xm == 2 ? BrickDim{4, 4, 16} : BrickDim{4, 8, 16}; }
+
 // Input-channel split of a 3x3(x3) fp32 launch (ConvArgs::ksplit): when bricks x channel tiles fill under half of the CUs and every
 // split still has >= 4 chunks of 8 channels.  1 = no split.  BIU_DISABLE=ksplit switches it off.
 int biu_mfma_conv_ksplit(int cin, const biu_act* y, int kd, int dtype) {
     if (biu_off("ksplit") || dtype != BIU_F32 || (kd != 1 && kd != 3)) return 1;
-    const int ntiles = (y->c + 31) / 32, nt = pick_nt(ntiles);
-    const BrickDim b = conv3_brick(kd, nt, y->w % 32 == 0);
+    const int xm3 = kd == 3 ? x3_ok(cin, kd, dtype) : 0;
+    const int ntiles = (y->c + 31) / 32, nt = xm3 ? 1 : pick_nt(ntiles);
+    const BrickDim b = xm3 ? split3_brick(xm3) : conv3_brick(kd, nt, y->w % 32 == 0);
     const long blocks = (long)y->n * ((y->d + b.td - 1) / b.td) * ((y->h + b.th - 1) / b.th) * ((y->w + b.tw - 1) / b.tw) * (ntiles / nt);
     const int nchunks = x3_ok(cin, kd, dtype) ? cin / 16 : cin / 8;
     int ks = 1;
@@ -1530,6 +1577,13 @@ static int launch_conv_xs(const ConvArgs& a, hipStream_t st) {
     return wide ? launch_cfg<TS, 1, 3, 1, 1, 16, 32, 2, 4>(a, ntiles, nz, st) : launch_cfg<TS, 1, 3, 1, 1, 32, 16, 2, 4>(a, ntiles, nz, st);
 }
 static int launch_conv_x3(const ConvArgs& a, int mode, hipStream_t st) { return mode == 2 ? launch_conv_xs<f32x6_t>(a, st) : launch_conv_xs<f32x3_t>(a, st); }
+// fp32 3x3x3 as split bf16 products: one output tile per block, split3_brick (biu_mfma_conv_stat_rows mirrors the grid)
+static int launch_conv_x3_3d(const ConvArgs& a, int mode, hipStream_t st) {
+    const int ntiles = (a.Cout + 31) / 32, nz = a.ksplit > 1 ? a.ksplit : 1;
+    if (mode == 2) return launch_cfg<f32x6_t, 3, 3, 1, 4, 4, 16, 1, 4>(a, ntiles, nz, st);
+    return launch_cfg<f32x3_t, 3, 3, 1, 4, 8, 16, 1, 4>(a, ntiles, nz, st);
+}
+static int launch_conv_split(const ConvArgs& a, int kd, int mode, hipStream_t st) { return kd == 3 ? launch_conv_x3_3d(a, mode, st) : launch_conv_x3(a, mode, st); }
 
 // number of bricks of a ConvTranspose data-gradient launch on the coarse tensor dx
 int biu_mfma_convt_dgrad_bricks(const biu_act* dx, int kd) {
@@ -1538,7 +1592,8 @@ int biu_mfma_convt_dgrad_bricks(const biu_act* dx, int kd) {
 }
 
 // partial rows its fused BatchNorm-backward sums occupy: one per workgroup column (must mirror launch_cfg_r's grid computation)
-int biu_mfma_convt_dgrad_rows(const biu_act* dx, int kd) {
+int biu_mfma_convt_dgrad_rows(const biu_act* dx, int kd, int cdy, int dtype) {
+    (void)cdy; (void)dtype;                               // (a 3-D split data gradient would change the grid: x3_convt_dg keeps kd = 2 exact)
     const int ntiles = (dx->c + 31) / 32, gy = ntiles / pick_nt(ntiles);
     int g = grid_per_column(num_cus(), gy);
     const int nbricks = biu_mfma_convt_dgrad_bricks(dx, kd);
@@ -1558,16 +1613,28 @@ static int m16_grid_x(int cols) { return grid_per_column(num_cus(), cols); }    
 
 // number of bricks of a 3x3(x3) launch writing y (= BatchNorm-backward partial rows of the data-gradient kernels).  x (the tensor the
 // launch reads) and dtype select the kernel; without them the count is an upper bound over the kernels that could run (buffer sizing).
-int biu_mfma_conv_bricks(const biu_act* y, int kd, const biu_act* x, int dtype) {
+int biu_mfma_conv_bricks(const biu_act* y, int kd, const biu_act* x, int dtype, int cin) {
     const int ntiles = (y->c + 31) / 32;
     const int reg = bricks_of(y, conv3_brick(kd, pick_nt(ntiles), y->w % 32 == 0));
-    if (x) return m16_ok(x, y, dtype) ? bricks_of(y, m16_brick(kd)) : reg;
+    if (x) {
+        if (const int xm = kd == 3 ? x3_ok(cin >= 0 ? cin : x->c, kd, dtype) : 0) return bricks_of(y, split3_brick(xm));
+        return m16_ok(x, y, dtype) ? bricks_of(y, m16_brick(kd)) : reg;
+    }
     const int m16 = (y->c == 16 || y->c % 32 == 0) ? bricks_of(y, m16_brick(kd)) : 0;
-    return reg > m16 ? reg : m16;
+    const int x3 = kd == 3 ? bricks_of(y, split3_brick(2)) : 0;          // (the smaller brick of the split-product kernels)
+    const int mx = reg > m16 ? reg : m16;
+    return mx > x3 ? mx : x3;
 }
 // number of workgroup columns of that launch (= BatchNorm statistics partial rows of the forward kernels: one per block);
 // must mirror launch_cfg_r's / launch_conv16's grid computation
-int biu_mfma_conv_stat_rows(const biu_act* y, int kd, const biu_act* x, int dtype, bool red) {
+int biu_mfma_conv_stat_rows(const biu_act* y, int kd, const biu_act* x, int dtype, bool red, int cin) {
+    if (x && kd == 3) {
+        if (const int xm = x3_ok(cin >= 0 ? cin : x->c, kd, dtype)) {          // launch_conv_x3_3d: NT = 1, split3_brick
+            const int g = grid_per_column(num_cus(), (y->c + 31) / 32);
+            const int nbricks = bricks_of(y, split3_brick(xm));
+            return g > nbricks ? nbricks : g;
+        }
+    }
     if (x && kd == 3 && biu_conv_roll_ok(x, y, dtype, false, 0, red)) return biu_conv_roll_rows(x, y, dtype);
     if (m16_ok(x, y, dtype)) {
         const int g = m16_grid_x(y->c / (16 * m16_mtl(x->c, y->c, dtype)));
@@ -1577,7 +1644,7 @@ int biu_mfma_conv_stat_rows(const biu_act* y, int kd, const biu_act* x, int dtyp
     const int ntiles = (y->c + 31) / 32;
     const int nt = pick_nt(ntiles);
     int g = grid_per_column(num_cus(), ntiles / nt);
-    const int nbricks = biu_mfma_conv_bricks(y, kd, x ? x : y, x ? dtype : -1);
+    const int nbricks = biu_mfma_conv_bricks(y, kd, x ? x : y, x ? dtype : -1, cin);
     return g > nbricks ? nbricks : g;
 }
 
@@ -1703,7 +1770,7 @@ int biu_mfma_conv(const biu_act* x, const biu_xform* xf, const void* packed, con
                 b.ksplit = ks;
                 b.y = ws; b.y_zstride = sl0; b.accumulate = 0;
                 if (y1t) { b.y1 = ws + (size_t)ks * sl0; b.y1_zstride = sl1; b.accumulate1 = 0; }
-                rc = x3_ok(b.Cin, kd, dtype) ? launch_conv_x3(b, x3_ok(b.Cin, kd, dtype), st) : launch_conv<float>(b, kd, st);
+                rc = x3_ok(b.Cin, kd, dtype) ? launch_conv_split(b, kd, x3_ok(b.Cin, kd, dtype), st) : launch_conv<float>(b, kd, st);
                 if (rc == BIU_OK) {
                     hipLaunchKernelGGL(k_split_reduce, dim3(grid_for((i64)nvox(y) * y->c, 256, 2048)), dim3(256), 0, st, (const float*)ws, sl0 / sizeof(float),
                                        ks, (float*)y->p, (long)nvox(y), y->c, y->pitch, accumulate);
@@ -1734,7 +1801,7 @@ int biu_mfma_conv(const biu_act* x, const biu_xform* xf, const void* packed, con
         }
     }
     if (dtype == BIU_BF16) return launch_conv<bf16_t>(a, kd, st);
-    if (x3_ok(a.Cin, kd, dtype)) return launch_conv_x3(a, x3_ok(a.Cin, kd, dtype), st);
+    if (x3_ok(a.Cin, kd, dtype)) return launch_conv_split(a, kd, x3_ok(a.Cin, kd, dtype), st);
     return launch_conv<float>(a, kd, st);
 }
 
@@ -1788,7 +1855,7 @@ size_t biu_mfma_convt_packed_bytes(int kind, int cin, int cout, int kd, int dtyp
     if (kd != 1 && kd != 2) return 0;
     const int K = kind == 0 ? cin : cout, Nn = kind == 0 ? cout : cin;
     if (!chan_ok(K, Nn, dtype)) return 0;
-    const size_t ntiles = (Nn + 31) / 32, nKS = nks_of(K, kd, dtype);
+    const size_t ntiles = (Nn + 31) / 32, nKS = kind == 1 && x3_convt_dg(K, kd, dtype) != x3_ok(K, kd, dtype) ? K / 8 : nks_of(K, kd, dtype);
     return ntiles * nKS * (size_t)(kd * 4) * 1024;
 }
 
@@ -1796,7 +1863,7 @@ int biu_mfma_convt_pack(int kind, const float* w, int cin, int cout, int kd, int
     const size_t total = biu_mfma_convt_packed_bytes(kind, cin, cout, kd, dtype) / 16;
     BIU_REQUIRE(total > 0, BIU_ERR_UNSUPPORTED, "convt_pack: shape is served by the direct kernels");
     BIU_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(k_pack_convt<T>, dim3(grid_for((i64)total, 256, 4096)), dim3(256), 0, st, w, cin, cout,
-                                                 kd * 4, kind, (uint4*)packed, x3_ok(kind == 0 ? cin : cout, kd, dtype)));
+                                                 kd * 4, kind, (uint4*)packed, kind == 0 ? x3_ok(cin, kd, dtype) : x3_convt_dg(cout, kd, dtype)));
     BIU_CHECK_LAUNCH("pack_convt");
     return BIU_OK;
 }
@@ -1815,8 +1882,12 @@ __global__ void k_pack_batch(const biu_pack_job* __restrict__ jobs, int x3_on) {
     uint4* __restrict__ out = (uint4*)j.packed;
     const int cin = j.cin, cout = j.cout, kind = j.kind;
     const int Kc = kind == 0 ? cin : cout, Nc = kind == 0 ? cout : cin;
-    const bool split_img = sizeof(T) == 4 && (x3_on & 1) && j.kd == 1 && Kc % 16 == 0;      // == x3_ok(): the split-product image of a 2-D layer (3x3 conv or ConvTranspose k2)
-    const int xmode = (x3_on & 4) ? 2 : 1;
+    // == x3_ok() / x3_convt_dg(): the split-product image of a 2-D layer (flags bits 0, 2) or a 3-D layer (bits 3, 4; 3x3x3 conv or ConvTranspose3d k2)
+    const int xm2 = (x3_on & 1) ? ((x3_on & 4) ? 2 : 1) : 0, xm3 = (x3_on & 8) ? ((x3_on & 16) ? 2 : 1) : 0;
+    int xmode = j.kd == 1 ? xm2 : ((j.kd == 2 || j.kd == 3) ? xm3 : 0);
+    if (j.transposed && kind == 1 && j.kd == 2) xmode = 0;
+    if (!j.transposed && j.kd == 3 && Kc > (xmode == 2 ? kSplit3KmaxX6 : kSplit3KmaxX3)) xmode = 0;
+    const bool split_img = sizeof(T) == 4 && xmode != 0 && Kc >= 16 && Kc % 16 == 0;
     const int nKS = (split_img && xmode == 2) ? Kc / 16 * 3 : Kc / (2 * PE), ntiles = (Nc + 31) / 32;
     const int taps = j.transposed ? j.kd * 4 : j.kd * j.kh * j.kw;
     const size_t total = (size_t)ntiles * nKS * taps * 64;
@@ -1878,9 +1949,10 @@ __global__ void k_pack_batch(const biu_pack_job* __restrict__ jobs, int x3_on) {
 }
 int biu_mfma_pack_batch(const biu_pack_job* jobs_device, int n, int dtype, hipStream_t st) {
     if (n <= 0) return BIU_OK;
-    // flags: bit 0 = split-product images (fp32), bit 2 = ... of the six-term form; bit 1 = two-tile images of the 16-row kernel (bf16; m16_mtl's switch)
-    const int xm = dtype == BIU_F32 ? fp32_split_mode() : 0;
-    const int flags = (xm ? 1 : 0) | (xm == 2 ? 4 : 0) | ((dtype == BIU_BF16 && m16_mtl(32, 32, BIU_BF16) == 2) ? 2 : 0);
+    // flags: bit 0 = split-product images of the 2-D layers (fp32), bit 2 = ... of the six-term form, bits 3 / 4 = the same for the 3-D layers;
+    // bit 1 = two-tile images of the 16-row kernel (bf16; m16_mtl's switch)
+    const int xm = dtype == BIU_F32 ? fp32_split_mode() : 0, xm3 = dtype == BIU_F32 ? fp32_split_mode_3d() : 0;
+    const int flags = (xm ? 1 : 0) | (xm == 2 ? 4 : 0) | (xm3 ? 8 : 0) | (xm3 == 2 ? 16 : 0) | ((dtype == BIU_BF16 && m16_mtl(32, 32, BIU_BF16) == 2) ? 2 : 0);
     BIU_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(k_pack_batch<T>, dim3(256, n), dim3(256), 0, st, jobs_device, flags));
     BIU_CHECK_LAUNCH("pack_batch");
     return BIU_OK;
@@ -1958,8 +2030,12 @@ int biu_mfma_convt_fwd(const biu_act* x, const biu_xform* xf, const void* packed
     a.diag = nullptr;
     a.nbd = a.nbh = a.nbw = 0;
     if (dtype == BIU_BF16) return launch_convt_fwd<bf16_t>(a, kd, st);
-    if (const int xm = x3_ok(a.Cin, kd, dtype)) {       // 2-D, fp32 tensors, split bf16 products: 16-channel chunks
+    if (const int xm = x3_ok(a.Cin, kd, dtype)) {       // fp32 tensors, split bf16 products: 16-channel chunks
         const int ntiles = (a.Cout + 31) / 32;
+        if (kd == 2) {                                   // 3-D: the one-tap GEMMs of the exact kernel's 4x8x16 bricks, 8 parity slices
+            if (xm == 2) return pick_nt(ntiles) == 1 ? launch_cfg<f32x6_t, 1, 1, 1, 4, 8, 16, 1, 4>(a, ntiles, 8, st) : launch_cfg<f32x6_t, 1, 1, 1, 4, 8, 16, 2, 4>(a, ntiles, 8, st);
+            return pick_nt(ntiles) == 1 ? launch_cfg<f32x3_t, 1, 1, 1, 4, 8, 16, 1, 4>(a, ntiles, 8, st) : launch_cfg<f32x3_t, 1, 1, 1, 4, 8, 16, 2, 4>(a, ntiles, 8, st);
+        }
         if (xm == 2) return pick_nt(ntiles) == 1 ? launch_cfg<f32x6_t, 1, 1, 1, 1, 32, 16, 1, 4>(a, ntiles, 4, st) : launch_cfg<f32x6_t, 1, 1, 1, 1, 32, 16, 2, 4>(a, ntiles, 4, st);
         return pick_nt(ntiles) == 1 ? launch_cfg<f32x3_t, 1, 1, 1, 1, 32, 16, 1, 4>(a, ntiles, 4, st) : launch_cfg<f32x3_t, 1, 1, 1, 1, 32, 16, 2, 4>(a, ntiles, 4, st);
     }
@@ -1988,13 +2064,13 @@ int biu_mfma_convt_dgrad(const biu_act* dy, const void* packed, int kd, const bi
     a.ID = dy->d; a.IH = dy->h; a.IW = dy->w;
     a.osd = a.osh = a.osw = 1;
     a.Cin = dy->c; a.Cout = dx->c;
-    a.nKS = nks_of(dy->c, kd, dtype);
+    a.nKS = x3_convt_dg(dy->c, kd, dtype) == x3_ok(dy->c, kd, dtype) ? nks_of(dy->c, kd, dtype) : dy->c / ks_of(dtype);
     a.wz_stride = 0;
     a.accumulate = accumulate;
     a.diag = nullptr;
     a.nbd = a.nbh = a.nbw = 0;
     if (dtype == BIU_BF16) return launch_convt_dgrad<bf16_t>(a, kd, st);
-    if (const int xm = x3_ok(a.Cin, kd, dtype)) {
+    if (const int xm = x3_convt_dg(a.Cin, kd, dtype)) {
         const int ntiles = (a.Cout + 31) / 32;
         if (xm == 2) return pick_nt(ntiles) == 1 ? launch_cfg<f32x6_t, 1, 2, 2, 1, 16, 16, 1, 4>(a, ntiles, 1, st) : launch_cfg<f32x6_t, 1, 2, 2, 1, 16, 16, 2, 4>(a, ntiles, 1, st);
         return pick_nt(ntiles) == 1 ? launch_cfg<f32x3_t, 1, 2, 2, 1, 16, 16, 1, 4>(a, ntiles, 1, st) : launch_cfg<f32x3_t, 1, 2, 2, 1, 16, 16, 2, 4>(a, ntiles, 1, st);
@@ -2029,7 +2105,7 @@ __device__ __forceinline__ float fold_nearest_weight(const float* __restrict__ w
 // packed image of the 8 folded kernels: out[parity = blockIdx.y][ntile][kstep][tap t][lane], fragment layout of k_pack_weights
 // (wf != nullptr: explicit folded weights [p][co][ci][t] -- the composed ones of a ConvTranspose decoder -- instead of the tap sums of w)
 template <typename T>
-__global__ void k_pack_upconv(const float* __restrict__ w, int cin, int cout, int nKS, int ntiles, uint4* __restrict__ out, const float* __restrict__ wf = nullptr) {
+__global__ void k_pack_upconv(const float* __restrict__ w, int cin, int cout, int nKS, int ntiles, uint4* __restrict__ out, const float* __restrict__ wf, int x3) {
     using F = Frag<T>;
     constexpr int PE = F::PE;
     const int p = (int)blockIdx.y;
@@ -2042,6 +2118,15 @@ __global__ void k_pack_upconv(const float* __restrict__ w, int cin, int cout, in
         const int ks = (int)(r % nKS);
         const int nt = (int)(r / nKS);
         const int co = nt * 32 + (lane & 31);
+        if constexpr (sizeof(T) == 4) {
+            if (x3) {                                      // split-product image (x3_weight_piece), reduction k = ci
+                out[idx] = x3_weight_piece(x3, ks, lane >> 5, [&](int ci) -> float {
+                    if (co >= cout || ci >= cin) return 0.f;
+                    return wf ? wf[(((size_t)p * cout + co) * cin + ci) * 8 + t] : fold_nearest_weight(w, cin, co, ci, p, t);
+                });
+                continue;
+            }
+        }
         float f[PE];
 #pragma unroll
         for (int e = 0; e < PE; ++e) {
@@ -2055,7 +2140,7 @@ __global__ void k_pack_upconv(const float* __restrict__ w, int cin, int cout, in
 // packed image of the folded DATA GRADIENT: rows = input channels ci, reduction index kv = p * Cout + co over the 8 parity classes,
 // tap s = the coarse offset u - p + s it reads: W'[p][co][ci][t = 1 - s per axis].  out[ntile(ci)][kstep(kv)][tap s][lane]
 template <typename T>
-__global__ void k_pack_upconv_dgrad(const float* __restrict__ w, int cin, int cout, int nKSv, int ntiles, uint4* __restrict__ out, const float* __restrict__ wf = nullptr) {
+__global__ void k_pack_upconv_dgrad(const float* __restrict__ w, int cin, int cout, int nKSv, int ntiles, uint4* __restrict__ out, const float* __restrict__ wf, int x3) {
     using F = Frag<T>;
     constexpr int PE = F::PE;
     const size_t total = (size_t)ntiles * nKSv * 8 * 64;
@@ -2066,6 +2151,16 @@ __global__ void k_pack_upconv_dgrad(const float* __restrict__ w, int cin, int co
         const int ks = (int)(r % nKSv);
         const int nt = (int)(r / nKSv);
         const int ci = nt * 32 + (lane & 31);
+        if constexpr (sizeof(T) == 4) {
+            if (x3) {                                      // split-product image, reduction k = kv (a 16-channel chunk lies in one class)
+                out[idx] = x3_weight_piece(x3, ks, lane >> 5, [&](int kv) -> float {
+                    const int p = kv / cout, co = kv - p * cout;
+                    if (ci >= cin || p >= 8) return 0.f;
+                    return wf ? wf[(((size_t)p * cout + co) * cin + ci) * 8 + (7 - sidx)] : fold_nearest_weight(w, cin, co, ci, p, 7 - sidx);
+                });
+                continue;
+            }
+        }
         float f[PE];
 #pragma unroll
         for (int e = 0; e < PE; ++e) {
@@ -2082,26 +2177,30 @@ bool biu_mfma_upconv_ok(const biu_act* x, const biu_act* y, int dtype) {
     if (y->n != x->n || y->d != 2 * x->d || y->h != 2 * x->h || y->w != 2 * x->w) return false;
     return chan_ok(x->c, y->c, dtype) && ptrs_ok(x, y, dtype);
 }
+// The folded kernels take the 3-D product mode (x3_ok with kd = 2): forward reduction K = Cin, data gradient K = Cout per parity class
+static int x3_upconv(int K, int dtype) { return x3_ok(K, 2, dtype); }
+static int upconv_nks(int K, int dtype) { return x3_upconv(K, dtype) == 2 ? K / 16 * 3 : K / ks_of(dtype); }
 static size_t upconv_slice16(int cin, int cout, int dtype) {                 // packed fragments (16 B) per parity class
-    return (size_t)((cout + 31) / 32) * (cin / ks_of(dtype)) * 8 * 64;
+    return (size_t)((cout + 31) / 32) * upconv_nks(cin, dtype) * 8 * 64;
 }
 // kind 0: forward image (8 parity slices);  kind 1: data-gradient image (reduction over 8 x Cout)
 size_t biu_mfma_upconv_packed_bytes(int kind, int cin, int cout, int dtype) {
     if ((dtype != BIU_BF16 && dtype != BIU_F32) || (kind != 0 && kind != 1)) return 0;
+    if (dtype == BIU_F32) fp32_split_mode_3d();           // (latched like every 3-D size query, whatever the channels)
     if (kind == 0) return chan_ok(cin, cout, dtype) ? 8 * upconv_slice16(cin, cout, dtype) * 16 : 0;
     if (!chan_ok(cout, cin, dtype)) return 0;
-    return (size_t)((cin + 31) / 32) * (8 * cout / ks_of(dtype)) * 8 * 64 * 16;
+    return (size_t)((cin + 31) / 32) * (8 * upconv_nks(cout, dtype)) * 8 * 64 * 16;
 }
 int biu_mfma_upconv_pack(int kind, const float* w, int cin, int cout, int dtype, void* packed, hipStream_t st, const float* wf) {
     if (kind == 0) {
         const size_t slice = upconv_slice16(cin, cout, dtype);
-        const int ntiles = (cout + 31) / 32, nKS = cin / ks_of(dtype);
+        const int ntiles = (cout + 31) / 32, nKS = upconv_nks(cin, dtype);
         BIU_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(k_pack_upconv<T>, dim3(grid_for((i64)slice, 256, 512), 8), dim3(256), 0, st, w, cin, cout, nKS, ntiles,
-                                                     (uint4*)packed, wf));
+                                                     (uint4*)packed, wf, x3_upconv(cin, dtype)));
     } else {
-        const int ntiles = (cin + 31) / 32, nKSv = 8 * cout / ks_of(dtype);
+        const int ntiles = (cin + 31) / 32, nKSv = 8 * upconv_nks(cout, dtype);
         BIU_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(k_pack_upconv_dgrad<T>, dim3(grid_for((i64)ntiles * nKSv * 8 * 64, 256, 4096)), dim3(256), 0, st, w, cin,
-                                                     cout, nKSv, ntiles, (uint4*)packed, wf));
+                                                     cout, nKSv, ntiles, (uint4*)packed, wf, x3_upconv(cout, dtype)));
     }
     BIU_CHECK_LAUNCH("upconv_pack");
     return BIU_OK;
@@ -2119,6 +2218,13 @@ static int launch_upconv(const ConvArgs& a, hipStream_t st) {
         if (!biu_off("foldck8") && nt == 1 && a.Cin % (8 * e) == 0) return launch_upconv_cfg<T, 1, 8>(a, ntiles, st);
     if (a.Cin % (4 * e) == 0) return nt == 1 ? launch_upconv_cfg<T, 1, 4>(a, ntiles, st) : launch_upconv_cfg<T, 2, 4>(a, ntiles, st);
     return nt == 1 ? launch_upconv_cfg<T, 1, 2>(a, ntiles, st) : launch_upconv_cfg<T, 2, 2>(a, ntiles, st);
+}
+// fp32, split products (x3_upconv): the same 4x8x16 bricks and grid, 16-channel chunks (bf16x6: 5x9x17 halo at 96 B = 72 KiB + 24 KiB slab per tile)
+static int launch_upconv_f32(const ConvArgs& a, int xm, hipStream_t st) {
+    const int ntiles = (a.Cout + 31) / 32, nt = pick_nt(ntiles);
+    if (xm == 2) return nt == 1 ? launch_upconv_cfg<f32x6_t, 1, 4>(a, ntiles, st) : launch_upconv_cfg<f32x6_t, 2, 4>(a, ntiles, st);
+    if (xm == 1) return nt == 1 ? launch_upconv_cfg<f32x3_t, 1, 4>(a, ntiles, st) : launch_upconv_cfg<f32x3_t, 2, 4>(a, ntiles, st);
+    return launch_upconv<float>(a, st);
 }
 // BatchNorm-statistics rows of a folded launch: one per block and parity class (must mirror launch_cfg_r's grid computation)
 int biu_mfma_upconv_stat_rows(const biu_act* x, const biu_act* y) {
@@ -2147,7 +2253,7 @@ int biu_mfma_upconv_fwd(const biu_act* x, const biu_xform* xf, const void* packe
     a.OD = y->d; a.OH = y->h; a.OW = y->w;
     a.osd = a.osh = a.osw = 2;
     a.Cin = x->c; a.Cout = y->c;
-    a.nKS = x->c / ks_of(dtype);
+    a.nKS = upconv_nks(x->c, dtype);
     a.wz_stride = (int)upconv_slice16(x->c, y->c, dtype);
     a.accumulate = accumulate;
 #ifdef BIU_DIAG
@@ -2158,7 +2264,7 @@ int biu_mfma_upconv_fwd(const biu_act* x, const biu_xform* xf, const void* packe
     a.nbd = a.nbh = a.nbw = 0;
     a.fold = 1;
     if (dtype == BIU_BF16) return launch_upconv<bf16_t>(a, st);
-    return launch_upconv<float>(a, st);
+    return launch_upconv_f32(a, x3_upconv(x->c, dtype), st);
 }
 // data gradient of the folded up-conv: dx[u] (+)= sum_p sum_s W'[p][1 - s]^T . dy[2 (u - p + s) + p]   (dy fine, dx coarse)
 // BatchNorm-backward partial rows of the folded data gradient with the fused reduction (one per block; mirrors launch_cfg_r)
@@ -2189,14 +2295,14 @@ int biu_mfma_upconv_dgrad(const biu_act* dy, const void* packed, const biu_act* 
     a.GD = a.OD = a.ID = dx->d; a.GH = a.OH = a.IH = dx->h; a.GW = a.OW = a.IW = dx->w;      // (input extents: those of a parity sub-lattice of dy)
     a.osd = a.osh = a.osw = 1;
     a.Cin = dy->c; a.Cout = dx->c;
-    a.nKS = 8 * dy->c / ks_of(dtype);
+    a.nKS = 8 * upconv_nks(dy->c, dtype);
     a.wz_stride = 0;
     a.accumulate = accumulate;
     a.diag = nullptr;
     a.nbd = a.nbh = a.nbw = 0;
     a.fold = 2;
     if (dtype == BIU_BF16) return launch_upconv<bf16_t>(a, st);
-    return launch_upconv<float>(a, st);
+    return launch_upconv_f32(a, x3_upconv(dy->c, dtype), st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -4018,8 +4124,12 @@ int biu_mfma_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* dy, int
                           bn ? (i64)nvox(bn->y) * bn->y->pitch * 2 : 0))
         rc = launch_wgrad_roll(a, st, true);                                                                                 // batch of images as the depth axis
     else if (dtype == BIU_BF16) rc = (kd == 3) ? launch_wgrad<bf16_t, 3, 3, 1, 4, 8, 16, 1>(a, st) : launch_wgrad<bf16_t, 1, 3, 1, 1, 16, 32, 4>(a, st);
-    else if (kd == 1 && fp32_split_mode() == 2) rc = launch_wgrad<f32x6_t, 1, 3, 1, 1, 16, 16, 4>(a, st);  // fp32 tensors, bf16x6 products
-    else if (kd == 1 && fp32_split_mode() == 1) rc = launch_wgrad<f32x3_t, 1, 3, 1, 1, 16, 16, 4>(a, st);  // fp32 tensors, bf16x3 products
+    else if (kd == 1 && x3_mode_of(kd, dtype) == 2) rc = launch_wgrad<f32x6_t, 1, 3, 1, 1, 16, 16, 4>(a, st);  // fp32 tensors, bf16x6 products
+    else if (kd == 1 && x3_mode_of(kd, dtype) == 1) rc = launch_wgrad<f32x3_t, 1, 3, 1, 1, 16, 16, 4>(a, st);  // fp32 tensors, bf16x3 products
+    // 3-D: a 2x4x16 brick (4x6x18 halo) in both modes -- bf16x6 tiles are 6 B per element (A + B 105 KiB); bf16x3 on the exact kernel's
+    // 4x4x16 spills (108 B/lane), on 2x4x16 it does not
+    else if (kd == 3 && x3_mode_of(kd, dtype) == 2) rc = launch_wgrad<f32x6_t, 3, 3, 1, 2, 4, 16, 1>(a, st);
+    else if (kd == 3 && x3_mode_of(kd, dtype) == 1) rc = launch_wgrad<f32x3_t, 3, 3, 1, 2, 4, 16, 1>(a, st);
     else rc = (kd == 3) ? launch_wgrad<float, 3, 3, 1, 4, 4, 16, 1>(a, st) : launch_wgrad<float, 1, 3, 1, 1, 16, 16, 4>(a, st);
     if (rc != BIU_OK) return rc;
     hipLaunchKernelGGL(k_wgrad_finalize, dim3(grid_for((i64)a.CA * a.CB * taps, 256, 2048)), dim3(256), 0, st, (const float*)ws,
@@ -4096,7 +4206,10 @@ int biu_mfma_upconv_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* 
         a.ws = (float*)((char*)ws + (size_t)p * slice);
         a.fold_par = p;
         // two 32-wide tiles of dy's channels per block when it has them: twice the MFMA work per staged tile of the coarse operand
-        if (a.CA > 32) rc = dtype == BIU_BF16 ? launch_wgrad<bf16_t, 2, 2, 1, 4, 8, 16, 1, 2>(a, st) : launch_wgrad<float, 2, 2, 1, 4, 4, 16, 1, 2>(a, st);
+        // fp32 split products: one dy tile per block (a second one would not fit beside bf16x6 tiles: (425 + 2 x 256) x 192 B)
+        if (x3_mode_of(2, dtype) == 2) rc = launch_wgrad<f32x6_t, 2, 2, 1, 4, 4, 16, 1>(a, st);
+        else if (x3_mode_of(2, dtype) == 1) rc = launch_wgrad<f32x3_t, 2, 2, 1, 4, 4, 16, 1>(a, st);
+        else if (a.CA > 32) rc = dtype == BIU_BF16 ? launch_wgrad<bf16_t, 2, 2, 1, 4, 8, 16, 1, 2>(a, st) : launch_wgrad<float, 2, 2, 1, 4, 4, 16, 1, 2>(a, st);
         else rc = dtype == BIU_BF16 ? launch_wgrad<bf16_t, 2, 2, 1, 4, 8, 16, 1>(a, st) : launch_wgrad<float, 2, 2, 1, 4, 4, 16, 1>(a, st);
         if (rc != BIU_OK) return rc;
     }
@@ -4382,8 +4495,11 @@ int biu_mfma_convt_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* d
         if (wide) rc = (kd == 2) ? launch_wgrad<bf16_t, 2, 2, 2, 2, 4, 16, 2, 2>(a, st) : launch_wgrad<bf16_t, 1, 2, 2, 1, 8, 16, 4, 2>(a, st);
         else rc = (kd == 2) ? launch_wgrad<bf16_t, 2, 2, 2, 2, 4, 16, 2>(a, st) : launch_wgrad<bf16_t, 1, 2, 2, 1, 8, 16, 4>(a, st);
     } else {
-        if (kd == 1 && fp32_split_mode() == 2) rc = wide ? launch_wgrad<f32x6_t, 1, 2, 2, 1, 8, 16, 4, 2>(a, st) : launch_wgrad<f32x6_t, 1, 2, 2, 1, 8, 16, 4>(a, st);
-        else if (kd == 1 && fp32_split_mode() == 1) rc = wide ? launch_wgrad<f32x3_t, 1, 2, 2, 1, 8, 16, 4, 2>(a, st) : launch_wgrad<f32x3_t, 1, 2, 2, 1, 8, 16, 4>(a, st);
+        if (kd == 1 && x3_mode_of(kd, dtype) == 2) rc = wide ? launch_wgrad<f32x6_t, 1, 2, 2, 1, 8, 16, 4, 2>(a, st) : launch_wgrad<f32x6_t, 1, 2, 2, 1, 8, 16, 4>(a, st);
+        else if (kd == 1 && x3_mode_of(kd, dtype) == 1) rc = wide ? launch_wgrad<f32x3_t, 1, 2, 2, 1, 8, 16, 4, 2>(a, st) : launch_wgrad<f32x3_t, 1, 2, 2, 1, 8, 16, 4>(a, st);
+        // 3-D: the fine tile is 8 x the brick -- bf16x6 takes 1x4x16 (576 voxels x 192 B = 108 KiB), bf16x3 the exact kernel's 2x4x16
+        else if (kd == 2 && x3_mode_of(kd, dtype) == 2) rc = launch_wgrad<f32x6_t, 2, 2, 2, 1, 4, 16, 2>(a, st);
+        else if (kd == 2 && x3_mode_of(kd, dtype) == 1) rc = launch_wgrad<f32x3_t, 2, 2, 2, 2, 4, 16, 2>(a, st);
         else if (wide && kd == 1) rc = launch_wgrad<float, 1, 2, 2, 1, 8, 16, 4, 2>(a, st);      // (the fp32 3-D tiles leave no LDS for a second A tile)
         else rc = (kd == 2) ? launch_wgrad<float, 2, 2, 2, 2, 4, 16, 2>(a, st) : launch_wgrad<float, 1, 2, 2, 1, 8, 16, 4>(a, st);
     }

@@ -10,6 +10,7 @@ struct BiuEnv {
     bool foldt_always;        // BIU_FOLDT=always: every decoder level the folded kernels serve
     int foldt_cmax;           // BIU_FOLDT=cmax:N: exactly the levels whose coarse input has at most N channels (0: the size rule)
     int fp32_products;        // BIU_FP32_PRODUCTS: 0 exact, 1 bf16x3, 2 bf16x6 (default)
+    int fp32_products_3d;     // BIU_FP32_PRODUCTS_3D: the same for the 3-D kernels, 0 exact (default)
     int fall_maxca;           // BIU_FALL_MAXCA: channel limit of the one-launch folded weight gradient (default 128)
 };
 const BiuEnv& biu_env();
@@ -67,12 +68,14 @@ int biu_fold_gemm_chain(const float* G, size_t slice_f, const float* layouts, in
                         const float* b_t, const float* Sk, hipStream_t st);
 size_t biu_mfma_conv_split_bytes(int cin, const biu_act* y, const biu_act* y1, int kd, int dtype);   // 0: the launch is not split
 int biu_mfma_convt_dgrad_bricks(const biu_act* dx, int kd);
-int biu_mfma_convt_dgrad_rows(const biu_act* dx, int kd);
+int biu_mfma_convt_dgrad_rows(const biu_act* dx, int kd, int cdy, int dtype);     // cdy: dy's channels
 int biu_mfma_pack_batch(const biu_pack_job* jobs_device, int n, int dtype, hipStream_t st);
 int biu_mfma_set_fp32_products(int mode);
+int biu_mfma_set_fp32_products_3d(int mode);
 int biu_mfma_conv_ksplit(int cin, const biu_act* y, int kd, int dtype);
-int biu_mfma_conv_stat_rows(const biu_act* y, int kd, const biu_act* x = nullptr, int dtype = -1, bool red = false);
-int biu_mfma_conv_bricks(const biu_act* y, int kd, const biu_act* x = nullptr, int dtype = -1);
+// cin: reduction channels of the launch when they differ from x->c (two-source input)
+int biu_mfma_conv_stat_rows(const biu_act* y, int kd, const biu_act* x = nullptr, int dtype = -1, bool red = false, int cin = -1);
+int biu_mfma_conv_bricks(const biu_act* y, int kd, const biu_act* x = nullptr, int dtype = -1, int cin = -1);
 size_t biu_mfma_wgrad_workspace(int cin, int cout, int kd, int kh, int kw, int dtype);
 bool biu_mfma_wgrad_ok(const biu_act* x, const biu_act* dy, int kd, int kh, int kw, int dilation, int dtype);
 struct BnBwdFuse {            // BatchNorm(+LeakyReLU) backward fused into the weight-gradient loader

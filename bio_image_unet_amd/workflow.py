@@ -202,7 +202,13 @@ class Trainer3D(_EpochLoop):
     def __init__(self, dataset, num_epochs, network=UNet3D, use_interpolation=False, batch_size=4, lr=1e-3,
                  in_channels=1, out_channels=1, channel_weights=None, n_filter=64, dilation=1, val_split=0.2,
                  save_dir="./", save_name="model.pt", save_iter=False, load_weights=False, loss_function="BCEDice",
-                 loss_params=(0.5, 0.5), time_loss_weight=0.1, device: Union[torch.device, str] = "auto"):
+                 loss_params=(0.5, 0.5), time_loss_weight=0.1, device: Union[torch.device, str] = "auto",
+                 fp32_products: Optional[str] = None):
+        """``fp32_products`` (not in the reference): ``"exact"`` | ``"bf16x3"`` | ``"bf16x6"`` -- how the fp32 3-D kernels of this trainer
+        multiply (``bio_image_unet_amd.set_fp32_products_3d``; process-wide, default ``"exact"``); ``None`` leaves the process mode alone."""
+        if fp32_products is not None:
+            from . import set_fp32_products_3d
+            set_fp32_products_3d(fp32_products)
         self.device = _pick_device(device)
         self.network = network
         self.model = network(n_filter=n_filter, in_channels=in_channels, out_channels=out_channels,
@@ -330,7 +336,10 @@ class TrainerMo3d:
     def __init__(self, dataset, output_heads, num_epochs, network=MultiOutputUnet3D, use_interpolation=False, batch_size=4,
                  lr=1e-3, in_channels=1, n_filter=64, dilation=1, val_split=0.2, save_dir="./", save_name="model.pt",
                  save_iter=False, load_weights=False, loss_function="BCEDice", loss_params=(0.5, 0.5), time_loss_weight=0.1,
-                 device: Union[torch.device, str] = "auto"):
+                 device: Union[torch.device, str] = "auto", fp32_products: Optional[str] = None):
+        if fp32_products is not None:                 # see Trainer3D
+            from . import set_fp32_products_3d
+            set_fp32_products_3d(fp32_products)
         self.device = _pick_device(device)
         self.network = network
         self.model = network(n_filter=n_filter, in_channels=in_channels, output_heads=output_heads,

@@ -74,6 +74,16 @@ int  biu_version(void);
  * Replaces: torch.backends.cudnn.allow_tf32 / torch.set_float32_matmul_precision as used around unet/train.py:70-139. */
 int  biu_set_fp32_products(int mode);
 
+/* The same choice for the fp32 3-D kernels (kd = 2 | 3): 3x3x3 convolution (forward, data gradient, weight gradient, the fused BatchNorm and
+ * two-source forms), ConvTranspose3d k2 s2 and the skip half of the folded decoder level (biu_foldt_*).  Modes as above, but the default is
+ * 0 "exact"; 1 "bf16x3" and 2 "bf16x6" are opt-in; the folded up-sampling kernels (biu_upconv_*, both halves of biu_foldt_*) follow it too.
+ * Stay exact: launches with fewer than 16 or a non-multiple of 16 reduction channels, 3x3x3 launches wider than LDS allows (more than 1328
+ * reduction channels at bf16x6, 3056 at bf16x3), and the ConvTranspose3d data gradient.
+ * Latched on its own, independently of biu_set_fp32_products: fixed by the first 3-D fp32 convolution, weight packing or packed-size /
+ * workspace query (the packed weights differ), after which another mode is refused with BIU_ERR_UNSUPPORTED.
+ * BIU_FP32_PRODUCTS_3D=exact|bf16x3|bf16x6 in the environment selects the mode when this function was never called. */
+int  biu_set_fp32_products_3d(int mode);
+
 /* ------------------------------------------------------------------------------------------------
  * 3x3 / 3x3x3 "same" convolution, stride 1, padding = dilation            [K1, K2 of SURVEY 2b]
  * replaces nn.Conv2d / nn.Conv3d inside the conv block: unet/unet.py:56, unet3d/unet3d.py:54,

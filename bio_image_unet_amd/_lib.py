@@ -98,6 +98,8 @@ SIGNATURES = {
     "biu_head_dlogits": (_I, [_P, _P, _P, _I, _I, _I, C.c_longlong, _P, _I, _I, _P]),
     "biu_trilinear_up_fwd": (_I, [_A, _X, _A, _I, _P]),
     "biu_trilinear_up_bwd": (_I, [_A, _A, _I, _I, _P]),
+    "biu_bilinear_up_fwd": (_I, [_A, _X, _A, _I, _P]),
+    "biu_bilinear_up_bwd": (_I, [_A, _A, _I, _I, _P]),
     "biu_xcorr_fwd": (_I, [_A, _X, _A, _X, _A, _I, _P]),
     "biu_xcorr_bwd": (_I, [_A, _X, _A, _X, _A, _A, _A, _I, _I, _P]),
     "biu_conv_cat_ok": (_I, [_A, _A, _A, _I, _I, _I, _I, _I]),

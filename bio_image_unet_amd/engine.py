@@ -74,6 +74,17 @@ class Buf:
         self.lazy[(c0, c)] = lazy
         return Act(self, c0, c, [(c0, c)])
 
+    def span(self, c0: int, c: int) -> "Act":
+        """One Act over the consecutive slices that tile channels [c0, c0 + c): the prefix ``[x_r_0 | ... | x_r_{j-1}]`` of a nested
+        U-Net row buffer, read as one (pitched) part of a concatenation.  Each slice keeps its own producer, transform and gradient flag."""
+        keys = sorted(k for k in self.leaves if c0 <= k[0] < c0 + c)
+        cov = c0
+        for k0, kc in keys:
+            assert k0 == cov, "span has a hole"
+            cov += kc
+        assert cov == c0 + c, "span does not end on a slice boundary"
+        return Act(self, c0, c, keys)
+
     def full(self) -> "Act":
         keys = sorted(self.leaves)
         cov = 0
@@ -150,6 +161,20 @@ class Act:
         flags = [self.buf.leaves[k] for k in self.leaves]
         assert all(flags) or not any(flags), "partially written concat gradient"
         return flags[0]
+
+    def g_accumulate(self) -> int:
+        """Accumulate flag for a kernel that writes this Act's whole gradient.  A span whose slices were written only in part (the
+        deep-supervision heads of a nested U-Net reach x0_1 ... x0_3 before the prefix [x0_0 ... x0_3] is written) has its unwritten
+        slices' gradients zero-filled first, so that the whole span accumulates."""
+        flags = [self.buf.leaves[k] for k in self.leaves]
+        if all(flags) or not any(flags):
+            return int(flags[0])
+        g = self.buf.grad()
+        for k, f in zip(self.leaves, flags):
+            if not f:
+                g[..., k[0]:k[0] + k[1]].zero_()
+                self.buf.leaves[k] = True
+        return 1
 
     def mark_g(self):
         for k in self.leaves:
@@ -572,7 +597,7 @@ class ConvBlockNode(Node):
         if cat:
             packed = eng.pack(self.pk_b, 1, self.conv.weight, self.xin.c, cout, self.kd, self.kh, self.kw)
             check(lib.biu_conv_bwd_data_cat(y.g(), _ptr(self.conv.weight.data), packed, self.kd, self.kh, self.kw, self.dil,
-                                            cat[0].g(), int(cat[0].g_written()), cat[1].g(), int(cat[1].g_written()), _ptr(eng.ws), eng.ws_bytes, eng.dtype, st),
+                                            cat[0].g(), cat[0].g_accumulate(), cat[1].g(), cat[1].g_accumulate(), _ptr(eng.ws), eng.ws_bytes, eng.dtype, st),
                   "conv_bwd_data_cat")
             cat[0].mark_g()
             cat[1].mark_g()
@@ -673,10 +698,11 @@ class ConvTNode(Node):
 
 
 class ResampleNode(Node):
-    """MaxPool(2,2) / nearest x0.5 / nearest x2: output is materialised *activated* data (identity transform)."""
+    """MaxPool(2,2) / nearest x0.5 / nearest x2 / trilinear x2 / bilinear x2 (align_corners=True): output is materialised *activated*
+    data (identity transform)."""
 
     def __init__(self, eng, kind: str, xin: Act, yout: Act):
-        assert kind in ("maxpool", "down", "up", "trilinear")
+        assert kind in ("maxpool", "down", "up", "trilinear", "bilinear")
         self.kind, self.xin, self.y = kind, xin, yout
         self.only_for_backward = False       # an up-sampling whose only reader folds it into its forward: needed by that reader's backward alone
         self.skip = False                    # ... and whose reader folds its backward too: the up-sampled tensor is never needed
@@ -686,7 +712,7 @@ class ResampleNode(Node):
         if self.skip or (self.only_for_backward and not eng.grad_mode):
             return
         f = {"maxpool": lib.biu_maxpool_fwd, "down": lib.biu_nearest_down_fwd, "up": lib.biu_nearest_up_fwd,
-             "trilinear": lib.biu_trilinear_up_fwd}[self.kind]
+             "trilinear": lib.biu_trilinear_up_fwd, "bilinear": lib.biu_bilinear_up_fwd}[self.kind]
         check(f(self.xin.a(), self.xin.xf(), self.y.a(), eng.dtype, _stream()), self.kind + "_fwd")
 
     def bwd(self, eng):
@@ -709,6 +735,8 @@ class ResampleNode(Node):
             check(lib.biu_nearest_down_bwd(self.y.g(), self.xin.g(), acc, eng.dtype, st), "nearest_down_bwd")
         elif self.kind == "trilinear":
             check(lib.biu_trilinear_up_bwd(self.y.g(), self.xin.g(), acc, eng.dtype, st), "trilinear_up_bwd")
+        elif self.kind == "bilinear":
+            check(lib.biu_bilinear_up_bwd(self.y.g(), self.xin.g(), acc, eng.dtype, st), "bilinear_up_bwd")
         else:
             check(lib.biu_nearest_up_bwd(self.y.g(), self.xin.g(), acc, eng.dtype, st), "nearest_up_bwd")
         self.xin.mark_g()
@@ -758,7 +786,9 @@ class XCorrNode(Node):
 
 
 class CopyNode(Node):
-    """out = T(x) into another slice (Siam concat of the two pooled bottlenecks, 'control' join)."""
+    """out = T(x) into another slice (Siam concat of the two pooled bottlenecks, 'control' join; the prefix of a nested U-Net
+    concatenation the two-source kernels do not serve).  The source may be lazy: its gradient twin holds d loss / d T(x), which is
+    exactly what the copy's gradient is, so the backward adds it unchanged."""
 
     def __init__(self, eng, xin: Act, out: Act):
         self.xin, self.y = xin, out
@@ -770,8 +800,7 @@ class CopyNode(Node):
     def bwd(self, eng):
         if not self.y.g_written() or not eng.wants_grad(self.xin):
             return
-        assert not self.xin.is_lazy(), "CopyNode backward expects an identity transform"
-        check(lib.biu_act_add(self.y.g(), self.xin.g(), int(self.xin.g_written()), eng.dtype, _stream()), "act_add")
+        check(lib.biu_act_add(self.y.g(), self.xin.g(), self.xin.g_accumulate(), eng.dtype, _stream()), "act_add")
         self.xin.mark_g()
 
 
@@ -1273,10 +1302,19 @@ class Engine:
         return self.grads
 
     def _backward_heads(self, head_grads):
-        """head_grads[i] = None or (g_logits, g_act, activated output) of head i."""
+        """head_grads[i] = None or (g_logits, g_act, activated output) of head i.  Heads are grouped by the trunk they read (the
+        deep-supervision heads of a nested U-Net sit on x0_1 ... x0_L); each group runs one backward."""
         live = [(h, g) for h, g in zip(self.heads, head_grads) if g is not None]
         if not live:
             return
+        groups: Dict[int, list] = {}
+        for h, g in live:
+            groups.setdefault(id(h.xin), []).append((h, g))
+        for grp in groups.values():
+            self._backward_head_group(grp)
+
+    def _backward_head_group(self, live):
+        """The live heads of one trunk."""
         if len(live) == 1:
             h, (gl, ga, a) = live[0]
             h.bwd_with(self, h.dlogits(self, gl, ga, a))
@@ -1289,10 +1327,11 @@ class Engine:
         shp = live[0][0].out_shape(self)
         dl = torch.empty((shp[0], cout) + tuple(shp[2:]), dtype=torch.float32, device=self.device)
         key = tuple(id(h) for h, _ in live)
-        if getattr(self, "_stack_key", None) != key:
-            self._stack_key = key
-            self._stack_w = torch.empty((cout, x.c), dtype=torch.float32, device=self.device)
-        w, o = self._stack_w, 0
+        if not hasattr(self, "_stack_w"):
+            self._stack_w = {}
+        if key not in self._stack_w:
+            self._stack_w[key] = torch.empty((cout, x.c), dtype=torch.float32, device=self.device)
+        w, o = self._stack_w[key], 0
         for h, (gl, ga, a) in live:
             w[o:o + h.cout].copy_(h.conv.weight.data.reshape(h.cout, x.c))          # (cout x cin floats: tiny)
             h.dlogits(self, gl, ga, a, dst=dl, ctot=cout, c0=o)

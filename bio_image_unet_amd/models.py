@@ -10,9 +10,12 @@ Reference classes mirrored here:
   UNet3D ............... unet3d/unet3d.py:6-99
   Siam_UNet ............ siam_unet/siam_unet.py:7-148
   MultiOutputUnet3D .... multi_output_unet3d/multi_output_unet3d.py:7-170
+  MultiOutputUnet ...... multi_output_unet/multi_output_unet.py:6-134
+  MultiOutputNestedUNet, MultiOutputNestedUNet_3Levels .. multi_output_unet/multi_output_nested_unet.py:33-240
 """
 from __future__ import annotations
 
+import ctypes as C
 import logging
 from collections import OrderedDict
 from typing import Dict, Optional
@@ -215,7 +218,10 @@ class Unet(_HipNet):
             eng.add(E.ConvBlockNode(eng, b1, cat, a))
             t = eng.new_act(spaces[4 - lvl], b2[0].out_channels, lazy=True)
             eng.add(E.ConvBlockNode(eng, b2, a, t))
-        head = E.HeadNode(eng, self.final[0], t, "sigmoid", want_logits=True, want_act=True)
+        self._build_heads(eng, t)
+
+    def _build_heads(self, eng, d8):
+        head = E.HeadNode(eng, self.final[0], d8, "sigmoid", want_logits=True, want_act=True)
         eng.add(head)
         eng.heads.append(head)
 
@@ -246,6 +252,32 @@ class Unet(_HipNet):
         eng = self._engine_for(x)
         logits, prob = E.run(eng, [x], [(0, "logits"), (0, "act")])
         return prob, logits
+
+
+class MultiOutputUnet(Unet):
+    """``MultiOutputUnet(in_channels=1, output_heads=None, n_filter=32, **kwargs)`` (multi_output_unet/multi_output_unet.py:6-134): the
+    ``Unet`` body with dilation 1 and one 1x1 head per entry of ``output_heads`` -> dict of activated outputs.  ``**kwargs`` are swallowed
+    (the reference trainer passes ``dilation=`` and ``deep_supervision=``); ``deep_supervision`` stays False."""
+
+    def __init__(self, in_channels=1, output_heads: Optional[Dict[str, dict]] = None, n_filter=32, **kwargs):
+        super().__init__(in_channels=in_channels, out_channels=1, n_filter=n_filter, dilation=1)
+        del self._modules["final"]
+        self.output_heads = output_heads or {"default": {"channels": 1, "activation": "sigmoid"}}
+        self.deep_supervision = False
+        self.output_layers = nn.ModuleDict()
+        for name, cfg in self.output_heads.items():
+            self.output_layers[name] = nn.Conv2d(n_filter, cfg["channels"], kernel_size=1, padding=0)
+
+    def _build_heads(self, eng, d8):
+        for name, cfg in self.output_heads.items():
+            head = E.HeadNode(eng, self.output_layers[name], d8, cfg.get("activation"), want_logits=False, want_act=True)
+            eng.add(head)
+            eng.heads.append(head)
+
+    def forward(self, x):
+        eng = self._engine_for(x)
+        outs = E.run(eng, [x], [(i, "act") for i in range(len(self.output_heads))])
+        return {name: o for name, o in zip(self.output_heads, outs)}
 
 
 class Siam_UNet(Unet):
@@ -619,3 +651,162 @@ class AttentionUnet(Unet):
         head = E.HeadNode(eng, self.final[0], t, "sigmoid", want_logits=True, want_act=True)
         eng.add(head)
         eng.heads.append(head)
+
+
+# ------------------------------------------------------------------------------------------------------
+# nested U-Net++ (multi_output_unet/multi_output_nested_unet.py)
+# ------------------------------------------------------------------------------------------------------
+class VGGBlock(nn.Module):
+    """Parameter container of the reference's ``VGGBlock`` (multi_output_nested_unet.py:33-55): same child names and registration order
+    (``relu, conv1, bn1, conv2, bn2, dropout``), so the state_dict keys are ``conv1.weight``, ``bn1.running_mean``, ..."""
+
+    def __init__(self, in_channels, middle_channels, out_channels, dropout=0.0, dilation=1):
+        super().__init__()
+        self.relu = nn.LeakyReLU(negative_slope=0.1, inplace=True)
+        self.conv1 = nn.Conv2d(in_channels, middle_channels, kernel_size=3, padding=dilation, dilation=dilation)
+        self.bn1 = nn.BatchNorm2d(middle_channels)
+        self.conv2 = nn.Conv2d(middle_channels, out_channels, kernel_size=3, padding=dilation, dilation=dilation)
+        self.bn2 = nn.BatchNorm2d(out_channels)
+        self.dropout = nn.Dropout2d(dropout)
+
+    def halves(self):
+        """The two conv -> BatchNorm -> LeakyReLU -> Dropout stages in the (conv, bn, act, dropout) form ``ConvBlockNode`` reads."""
+        return (self.conv1, self.bn1, self.relu, self.dropout), (self.conv2, self.bn2, self.relu, self.dropout)
+
+
+class _NestedUNet(_HipNet):
+    """U-Net++ with ``levels`` pooling steps.  Node x_r_j (row r = resolution, column j) is ``conv{r}_{j}``; for j >= 1 it reads
+    ``cat([x_r_0, ..., x_r_{j-1}, up(x_{r+1}_{j-1})])``.
+
+    Engine layout: the nodes x_r_0 ... x_r_{L-1-r} of row r that later nodes of the row concatenate share one row buffer, each producer
+    writing its own channel slice, so ``[x_r_0 | ... | x_r_{j-1}]`` is one pitched prefix view (``Buf.span``).  Node x_r_j reads
+    (prefix, U) through the two-source convolution kernels, with U the dense bilinear up-sampling; where those kernels refuse the shapes
+    (narrow rows), the node gets a concatenation buffer of its own that a copy node (prefix) and the up-sampling (U) fill."""
+    nd = 2
+    levels = 4
+
+    def _make(self, in_channels, output_heads, n_filter, deep_supervision, dilation, train_mode):
+        L = self.levels
+        self.output_heads = output_heads or {"default": {"channels": 1, "activation": "sigmoid"}}
+        self.deep_supervision = deep_supervision
+        self.train_mode = train_mode
+        self.dilation = dilation if dilation is not False else (1,) * (L + 1)
+        nb = [n_filter << r for r in range(L + 1)]
+        # registration order of the reference: pool, up, then the blocks column by column, then the heads
+        self.pool = nn.MaxPool2d(2, 2)
+        self.up = nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True)
+        for r in range(L + 1):
+            setattr(self, f"conv{r}_0", VGGBlock(in_channels if r == 0 else nb[r - 1], nb[r], nb[r], dilation=self.dilation[r]))
+        for j in range(1, L + 1):
+            for r in range(L + 1 - j):
+                setattr(self, f"conv{r}_{j}", VGGBlock(nb[r] * j + nb[r + 1], nb[r], nb[r]))
+        self.output_layers = nn.ModuleDict()
+        for name, cfg in self.output_heads.items():
+            for key in ([f"{name}_{l}" for l in range(1, L + 1)] if deep_supervision else [name]):
+                self.output_layers[key] = nn.Conv2d(nb[0], cfg["channels"], kernel_size=1)
+
+    def _block(self, eng, blk: VGGBlock, xin, yout):
+        h1, h2 = blk.halves()
+        mid = eng.new_act(yout.space, blk.conv1.out_channels, lazy=True)
+        eng.add(E.ConvBlockNode(eng, h1, xin, mid))
+        eng.add(E.ConvBlockNode(eng, h2, mid, yout))
+
+    def _build(self, eng, xshape):
+        L = self.levels
+        space, cin = self._space(xshape)
+        assert cin == self.conv0_0.conv1.in_channels, f"expected {self.conv0_0.conv1.in_channels} input channels, got {cin}"
+        n, d, h, w = space
+        if h % (1 << L) or w % (1 << L):
+            # the reference fails in torch.cat at the first level whose pooled extent is odd
+            raise RuntimeError(f"Sizes of tensors must match except in dimension 1 (input extents must be divisible by {1 << L})")
+        sp = [space]
+        for _ in range(L):
+            sp.append(_half(sp[-1]))
+        nb = [getattr(self, f"conv{r}_0").conv2.out_channels for r in range(L + 1)]
+        rows = [eng.new_buf(n, 1, sp[r][2], sp[r][3], (L - r) * nb[r]) if r < L else None for r in range(L + 1)]
+        xs = {}
+
+        def node(r, j):       # the output Act of x_r_j: a slice of its row buffer when a later node of the row concatenates it
+            if (r, j) not in xs:
+                xs[(r, j)] = rows[r].slice(j * nb[r], nb[r], lazy=True) if j < L - r else eng.new_act(sp[r], nb[r], lazy=True)
+            return xs[(r, j)]
+
+        eng.cat_paths = {}      # "conv{r}_{j}" -> "two-source" | "copy": how each concatenation of this graph is served
+        t = eng.new_input(space, cin)
+        for k in range(L + 1):
+            if k > 0:
+                pooled = eng.new_act(sp[k], nb[k - 1], lazy=False)
+                eng.add(E.ResampleNode(eng, "maxpool", node(k - 1, 0), pooled))
+                t = pooled
+            self._block(eng, getattr(self, f"conv{k}_0"), t, node(k, 0))
+            for j in range(1, k + 1):
+                r = k - j
+                src, y = node(r + 1, j - 1), node(r, j)
+                prefix = rows[r].span(0, j * nb[r])
+                # the up-sampled part and the consumer's output are dense: probed with an aligned dummy pointer, as Engine.new_cat does
+                probe = lambda c: E.biu_act(256, n, 1, sp[r][2], sp[r][3], c, c)
+                pu, py = probe(nb[r + 1]), probe(nb[r])
+                if E.lib.biu_conv_cat_ok(prefix.a(), C.byref(pu), C.byref(py), 1, 3, 3, 1, eng.dtype) == 1:
+                    u = eng.new_act(sp[r], nb[r + 1], lazy=False)
+                    eng.add(E.ResampleNode(eng, "bilinear", src, u))
+                    xin = E.CatAct(prefix, u)
+                    eng.cat_paths[f"conv{r}_{j}"] = "two-source"
+                else:
+                    cb = eng.new_buf(n, 1, sp[r][2], sp[r][3], j * nb[r] + nb[r + 1])
+                    eng.add(E.CopyNode(eng, prefix, cb.slice(0, j * nb[r], lazy=False)))
+                    eng.add(E.ResampleNode(eng, "bilinear", src, cb.slice(j * nb[r], nb[r + 1], lazy=False)))
+                    xin = cb.full()
+                    eng.cat_paths[f"conv{r}_{j}"] = "copy"
+                self._block(eng, getattr(self, f"conv{r}_{j}"), xin, y)
+        for name, cfg in self.output_heads.items():
+            if self.deep_supervision and self.train_mode:
+                trunks = [(f"{name}_{l}", node(0, l)) for l in range(1, L + 1)]
+            else:
+                trunks = [(f"{name}_{L}" if self.deep_supervision else name, node(0, L))]
+            for key, x0 in trunks:
+                head = E.HeadNode(eng, self.output_layers[key], x0, cfg.get("activation"), want_logits=False, want_act=True)
+                eng.add(head)
+                eng.heads.append(head)
+
+    def forward(self, x):
+        mode = (self.deep_supervision, self.train_mode)
+        if getattr(self, "_built_mode", mode) != mode:
+            self._engines.clear()         # the heads of a cached graph follow the flags it was built with
+        self._built_mode = mode
+        eng = self._engine_for(x)
+        outs = iter(E.run(eng, [x], [(i, "act") for i in range(len(eng.heads))]))
+        res = {}
+        L = self.levels
+        for name in self.output_heads:
+            if self.deep_supervision and self.train_mode:
+                for l in range(1, L + 1):
+                    res[f"{name}_{l}"] = next(outs)
+                res[name] = res[f"{name}_{L}"]
+            else:
+                res[name] = next(outs)
+        return res
+
+
+class MultiOutputNestedUNet(_NestedUNet):
+    """``MultiOutputNestedUNet(in_channels=1, output_heads=None, n_filter=32, deep_supervision=False, dilation=False, train_mode=True)``
+    (multi_output_nested_unet.py:58-156) -> dict of activated head outputs; with deep supervision and ``train_mode`` the keys are
+    ``name_1 ... name_4`` then ``name`` (the same tensor as ``name_4``).  ``dilation``: five entries, entry r for both convs of conv{r}_0."""
+    levels = 4
+
+    def __init__(self, in_channels=1, output_heads: Optional[Dict[str, dict]] = None, n_filter: int = 32, deep_supervision: bool = False,
+                 dilation=False, train_mode: bool = True):
+        super().__init__()
+        self._make(in_channels, output_heads, n_filter, deep_supervision, dilation, train_mode)
+
+
+class MultiOutputNestedUNet_3Levels(_NestedUNet):
+    """``MultiOutputNestedUNet_3Levels(in_channels=1, output_heads=None, n_filter=32, deep_supervision=False, dilation=False,
+    train_mode=True, **kwargs)`` (multi_output_nested_unet.py:159-240): three pooling steps, ``name_1 ... name_3`` with deep supervision.
+    ``dilation`` has four entries and applies as in the four-level network (the reference hands it to ``VGGBlock``'s ``dropout``
+    position instead: DESIGN.md, "Nested U-Net++")."""
+    levels = 3
+
+    def __init__(self, in_channels=1, output_heads: Optional[Dict[str, dict]] = None, n_filter=32, deep_supervision=False,
+                 dilation=False, train_mode=True, **kwargs):
+        super().__init__()
+        self._make(in_channels, output_heads, n_filter, deep_supervision, dilation, train_mode)

@@ -307,6 +307,14 @@ int biu_head_dlogits(const float* g_logits, const float* g_act, const float* act
 int biu_trilinear_up_fwd(const biu_act* x, const biu_xform* xf, const biu_act* out, int dtype, biu_stream stream);
 int biu_trilinear_up_bwd(const biu_act* dout, const biu_act* dx, int accumulate, int dtype, biu_stream stream);
 
+/* Bilinear x2 up-sampling, align_corners = True (nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True),
+ * multi_output_unet/multi_output_nested_unet.py:73): out = interp(T(x)); 2-D only (d == 1); out->h == 2 x->h, out->w == 2 x->w.
+ * Taps as PyTorch's, in fp32: scale = (n_in - 1) / (n_out - 1) (0 when n_out == 1), src = scale * o, i0 = (int)src,
+ * i1 = i0 + (i0 < n_in - 1), l1 = src - i0.  Both tensors may be pitched channel slices.
+ * bwd: dx (+)= adjoint(dout), gather form (no atomics: bit-reproducible).                                              */
+int biu_bilinear_up_fwd(const biu_act* x, const biu_xform* xf, const biu_act* out, int dtype, biu_stream stream);
+int biu_bilinear_up_bwd(const biu_act* dout, const biu_act* dx, int accumulate, int dtype, biu_stream stream);
+
 /* Depth-wise cross-correlation of two equal 2-D maps, padding='same' (Siam_UNet.depthwise_xcorr,
  * siam_unet/siam_unet.py:75-83): out[n,y,x,c] = sum_ij T(cur)[n,y+i-ph,x+j-pw,c] * T(prev)[n,i,j,c], ph=(H-1)/2, pw=(W-1)/2.
  * bwd needs identity transforms (materialised operands): dcur, dprev (+)= gradients.                                  */

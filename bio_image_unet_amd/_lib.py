@@ -36,6 +36,11 @@ class biu_xform(C.Structure):
     _fields_ = [("scale", C.c_void_p), ("shift", C.c_void_p), ("slope", C.c_void_p)]
 
 
+class biu_mo2d_term(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("nb", C.c_int32), ("partial_off", C.c_longlong), ("numel", C.c_longlong), ("pixels", C.c_longlong),
+                ("p0", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("weight", C.c_float)]
+
+
 _P = C.c_void_p
 _A = C.POINTER(biu_act)
 _X = C.POINTER(biu_xform)
@@ -96,6 +101,11 @@ SIGNATURES = {
     "biu_seg_loss_finish": (_I, [_P, _I, _I, C.c_longlong, _P, _I, _F, _F, _F, _I, _F, _F, _F, _I, _F, _P, _P]),
     "biu_seg_loss_coef": (_I, [_P, _P, _I, C.c_longlong, _F, _F, _F, _I, _F, _F, _F, _I, _F, _P, _P, _P]),
     "biu_head_dlogits": (_I, [_P, _P, _P, _I, _I, _I, C.c_longlong, _P, _I, _I, _P]),
+    "biu_mo2d_loss_blocks": (_I, [C.c_longlong]),
+    "biu_mo2d_loss_fwd": (_I, [_I, _F, _F, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "biu_mo2d_loss_finish": (_I, [_P, _I, _P, _P, _P]),
+    "biu_mo2d_loss_coef": (_I, [_P, _I, _P, _P, _P, _P]),
+    "biu_mo2d_loss_bwd": (_I, [_I, _F, _F, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "biu_trilinear_up_fwd": (_I, [_A, _X, _A, _I, _P]),
     "biu_trilinear_up_bwd": (_I, [_A, _A, _I, _I, _P]),
     "biu_bilinear_up_fwd": (_I, [_A, _X, _A, _I, _P]),

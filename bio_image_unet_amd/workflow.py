@@ -26,7 +26,7 @@ from torch import nn, optim
 from torch.utils.data import DataLoader, random_split
 
 from .losses import BCEDiceLoss, BCEDiceLossSiam, BCEDiceTemporalLoss, TverskyLoss, logcoshTverskyLoss, weightedBCELoss
-from .models import AttentionUnet, MultiOutputUnet3D, Siam_UNet, UNet3D, Unet, Unet_v0
+from .models import AttentionUnet, MultiOutputNestedUNet, MultiOutputUnet3D, Siam_UNet, UNet3D, Unet, Unet_v0
 from .optim import Adam
 from .utils import get_device, init_weights
 
@@ -438,6 +438,140 @@ class TrainerMo3d:
                 torch.save(self.state, os.path.join(self.save_dir, self.save_name))
             else:
                 print(f"\nValidation loss did not improve from {self.best_loss.item():.5f}")
+            if self.save_iter:
+                torch.save(self.state, os.path.join(self.save_dir, f"model_epoch_{epoch + self.epoch_start}.pt"))
+
+
+class TrainerMo2d:
+    """``bio_image_unet.multi_output_unet.Trainer`` counterpart (``multi_output_unet/train.py:18-131,144-232,369-407``).
+
+    Per head the criterion ``output_heads[name]['loss']`` (one of the ten of ``multi_output_unet.losses``) on the model's already
+    activated output, times the head's ``'weight'``; under deep supervision summed over the levels ``name_1 ... name_L`` with weights
+    ``[0.5, 0.75, 1.0]`` (``levels=3``) or ``[0.5, 0.75, 0.875, 1.0]`` (``levels=4``).  The whole sum is one fused autograd node
+    (``losses.MultiHeadLoss``).  ``clip_grad_norm_(1.0)`` before the step, ``ReduceLROnPlateau(patience=5, factor=0.2)``, and the
+    reference's checkpoint / ``params`` keys.  The ``[0, 1]`` assertion of ``BCEDiceLoss`` is raised where the loop reads the loss
+    (``total_loss.item()``, once per step), not in the middle of the step.
+
+    Quirks of the reference that change numbers, kept:
+
+    * validation applies the head activation (``softmax`` included) AGAIN to the already activated outputs (``:218,222``);
+    * validation under deep supervision always weights levels 1-3 with ``[0.5, 0.75, 1.0]``, also for the four-level network (``:215``);
+    * the model is never put in eval mode during validation: BatchNorm keeps using and updating batch statistics;
+    * ``levels`` outside {3, 4} raises ``ValueError`` at the first training step under deep supervision (``:170-172``).
+
+    ``SummaryWriter`` scalars (``Loss/train``, ``Loss/val``) are written only when ``tensorboard`` imports.  The PNG / TensorBoard image
+    logging of the reference (``plot_images``, ``log_validation_images``) is outside the hot path and is not ported."""
+
+    def __init__(self, dataset, num_epochs: int, network=MultiOutputNestedUNet, levels: int = 4, batch_size: int = 4, lr: float = 1e-4,
+                 in_channels: int = 1, output_heads: Optional[dict] = None, n_filter: int = 64, deep_supervision: bool = False,
+                 dilation=False, val_split: float = 0.2, save_dir: str = "./", save_name: str = "model.pt", save_iter: bool = False,
+                 load_weights: bool = False, device: Union[torch.device, str] = "auto"):
+        import random
+        from .multi_output_unet.losses import MultiHeadLoss
+        self.device = _pick_device(device)
+        self.network = network
+        self.model = network(n_filter=n_filter, in_channels=in_channels, output_heads=output_heads, dilation=dilation,
+                             deep_supervision=deep_supervision).to(self.device)
+        self.model.apply(init_weights)
+        self.data, self.num_epochs, self.batch_size, self.levels, self.lr = dataset, num_epochs, batch_size, levels, lr
+        self.best_loss = torch.tensor(float("inf"))
+        self.save_iter, self.n_filter, self.dilation, self.in_channels, self.output_heads = save_iter, n_filter, dilation, in_channels, output_heads
+        self.loss_functions = {name: self._get_loss_function(cfg["loss"]) for name, cfg in output_heads.items()}
+        self.activations = {name: cfg.get("activation", None) for name, cfg in output_heads.items()}
+        self.loss_weights = {name: cfg.get("weight", 1.0) for name, cfg in output_heads.items()}
+        self.criterion = MultiHeadLoss(output_heads, deep_supervision=bool(getattr(self.model, "deep_supervision", False)), levels=levels,
+                                       loss_functions=self.loss_functions)
+        n_val = int(len(dataset) * val_split)
+        self.dim = getattr(dataset, "dim_out", None)
+        train_data, val_data = random_split(dataset, [len(dataset) - n_val, n_val])
+        self.train_loader, self.val_loader = _loaders(dataset, train_data, val_data, batch_size, self.device)
+        self.optimizer = Adam(self.model.parameters(), lr=lr)
+        self.scheduler = optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="min", patience=5, factor=0.2)
+        self.save_dir, self.save_name = save_dir, save_name
+        os.makedirs(save_dir, exist_ok=True)
+        keys = ("clip_threshold", "gauss_noise_lims", "shot_noise_lims", "brightness_contrast", "random_rotate")
+        self.params = {"optimizer": self.optimizer.state_dict(), "lr": lr, "n_filter": n_filter, "deep_supervision": deep_supervision,
+                       "dilation": dilation, "batch_size": batch_size, "augmentation": getattr(dataset, "aug_factor", None),
+                       **{k: getattr(dataset, k, None) for k in keys}, "in_channels": in_channels, "output_heads": output_heads}
+        if load_weights:
+            self.state = torch.load(os.path.join(save_dir, save_name))
+            self.model.load_state_dict(self.state["state_dict"])
+            self.epoch_start = self.state["epoch"]
+        else:
+            self.epoch_start = 0
+        try:
+            from torch.utils.tensorboard import SummaryWriter
+            self.writer = SummaryWriter(log_dir=os.path.join(save_dir, "logs"))
+        except Exception:                   # tensorboard is optional here
+            self.writer = None
+        self.random_seed = 42
+        random.seed(self.random_seed)
+
+    @staticmethod
+    def _get_loss_function(loss_name):
+        from .multi_output_unet.losses import get_loss_function
+        return get_loss_function(loss_name)
+
+    _apply_activation = staticmethod(TrainerMo3d._apply_activation)
+
+    def _batch(self, batch):
+        x = batch["image"].to(self.device, non_blocking=True)
+        y = {key: _target(batch[key].to(self.device, non_blocking=True)) for key in self.output_heads}
+        return (x.unsqueeze(1) if x.dim() == 3 else x), y
+
+    def _total_loss(self, batch, validating):
+        x, y = self._batch(batch)
+        pred = self.model(x)
+        if not validating:
+            return self.criterion(pred, y)
+        # the activation once more on the activated outputs, and three level weights whatever the network's depth
+        ds = self.criterion.deep_supervision
+        keys = [f"{name}_{l}" for name in self.output_heads for l in (1, 2, 3)] if ds else list(self.output_heads)
+        act = {k: self._apply_activation(pred[k], self.activations.get(k.rsplit("_", 1)[0] if ds else k)) for k in keys}
+        return self.criterion(act, y, weights=[0.5, 0.75, 1.0] if ds else None)
+
+    def _scalar(self, tag, value, step):
+        if self.writer is not None:
+            self.writer.add_scalar(tag, value, step)
+
+    def iterate(self, epoch, mode):
+        if mode == "train":
+            running = 0.0
+            with _gc_paused():
+                for batch in tqdm(self.train_loader, total=len(self.train_loader), unit="batch"):
+                    loss = self._total_loss(batch, validating=False)
+                    self.optimizer.zero_grad()
+                    loss.backward()
+                    self.optimizer.clip_grad_norm_(1.0)          # multi_output_unet/train.py:186, as three launches (biu_grad_clip)
+                    self.optimizer.step()
+                    running += self.criterion.item()             # total_loss.item() (:189): the step's one host read
+            self._scalar("Loss/train", running / max(len(self.train_loader), 1), epoch + self.epoch_start)
+            return None
+        losses = []
+        with torch.no_grad():
+            for batch in tqdm(self.val_loader, total=len(self.val_loader), unit="batch"):
+                losses.append(self._total_loss(batch, validating=True).detach())
+                self.criterion.check_range()
+        val_loss = torch.stack(losses).mean()
+        self._scalar("Loss/val", val_loss.item(), epoch + self.epoch_start)
+        return val_loss
+
+    def start(self):
+        import time
+        for epoch in range(self.num_epochs):
+            t0 = time.time()
+            self.iterate(epoch, "train")
+            self.state = {"epoch": epoch + self.epoch_start, "epoch_start": self.epoch_start, "best_loss": self.best_loss,
+                          "state_dict": self.model.state_dict()}
+            self.state.update(self.params)
+            with torch.no_grad():
+                val_loss = self.iterate(epoch, "val")
+                self.scheduler.step(val_loss)
+            print(f"\nEpoch {epoch} completed in {round(time.time() - t0, 2)} seconds.")
+            if val_loss < self.best_loss:
+                print("\nValidation loss improved from %s to %s - saving model state" % (round(self.best_loss.item(), 5), round(val_loss.item(), 5)))
+                self.state["best_loss"] = self.best_loss = val_loss
+                torch.save(self.state, os.path.join(self.save_dir, self.save_name))
             if self.save_iter:
                 torch.save(self.state, os.path.join(self.save_dir, f"model_epoch_{epoch + self.epoch_start}.pt"))
 
@@ -904,3 +1038,146 @@ class PredictMo3d:
                     for k in self.target_keys:
                         stitch[k][v].add(preds[k][j].float(), (self.Z_start[zi], self.Y_start[yi], self.X_start[xi]), weight=wt)
         return {k: np.squeeze(torch.stack([s_.finish(False) for s_ in stitch[k]]).cpu().numpy()) for k in self.target_keys}
+
+
+class PredictMo2d:
+    """``bio_image_unet.multi_output_unet.Predict`` counterpart (``multi_output_unet/predict.py:13-285``) for in-memory arrays (a path
+    goes through ``tifffile`` when importable).
+
+    Float normalisation to [0, 1] per ``normalization_mode`` (no uint8 step); patches of ``min(image, max_patch_size)`` rounded up to a
+    multiple of 16, reflect padding when the image is smaller; origins ``linspace(...).astype('uint16')``; the model is built with
+    ``train_mode=False`` and the checkpoint's ``deep_supervision``, in eval mode.  The reference runs the model in fp16 on CUDA; here
+    the engine's dtype stays what it is (fp32, or bf16 after ``set_compute_dtype``) and each patch result is rounded to float16
+    before stitching, because the reference stores patches as float16.  Every head is stitched on the device (``biu_stitch_add`` /
+    ``biu_stitch_finish``) with a weight plane of 1 whose ``safe_margin = 20`` rows / columns are zeroed on every side that has a
+    neighbour; pixels no patch weights get the (float16) mean of that head's patches (``:279``).
+
+    As upstream, patches are cut on a stride of ``X_start[1]`` / ``Y_start[1]`` (``:180-181``) and stitched at ``X_start`` / ``Y_start``;
+    the first ``N_x x N_y`` windows of that stride are taken.  ``result`` is a dict of arrays per head, or ``None`` when ``result_path``
+    is given and the heads were written to ``result_path + name + '.tif'``."""
+
+    safe_margin = 20
+
+    def __init__(self, imgs, model_params, result_path=None, network=MultiOutputNestedUNet, max_patch_size=(1024, 1024), batch_size=1,
+                 normalization_mode="single", clip_threshold=(0., 99.98), add_tile=0, compress_tif=False, show_progress=True,
+                 device: Union[torch.device, str] = "auto", progress_notifier=None):
+        self.device = _pick_device(device)
+        if isinstance(imgs, str):
+            import tifffile
+            imgs = tifffile.imread(imgs)
+        self.max_patch_size, self.batch_size, self.add_tile = max_patch_size, batch_size, add_tile
+        self.normalization_mode, self.clip_threshold, self.result_path = normalization_mode, clip_threshold, result_path
+        imgs = np.array(imgs, dtype="float32")
+        if imgs.ndim == 2:
+            imgs = imgs[None]
+        self.imgs_shape = imgs.shape
+        imgs = self._preprocess(imgs, normalization_mode, clip_threshold)
+        patches = self._split(imgs)
+        mp = self.model_params = _load_params(model_params, self.device)
+        self.model = network(in_channels=mp["in_channels"], n_filter=mp["n_filter"], output_heads=mp["output_heads"],
+                             deep_supervision=mp.get("deep_supervision", False), train_mode=False).to(self.device)
+        self.model.load_state_dict(mp["state_dict"])
+        self.model.eval()
+        self.target_keys = list(mp["output_heads"].keys())
+        result = self._predict_and_stitch(patches, batch_size)
+        if result_path is not None:
+            for k in self.target_keys:
+                _write((result_path + k + ".tif") if os.path.exists(result_path) else (result_path + "_" + k + ".tif"), result[k])
+            self.result = None
+        else:
+            self.result = result
+
+    @staticmethod
+    def _preprocess(imgs, mode, clip):
+        """Percentile clip, then to [0, 1] (``predict.py:129-151``; lower bound ``nanpercentile``, upper ``percentile``)."""
+        def scale(a, lo, hi):
+            a = np.clip(a, a_min=lo, a_max=hi)
+            a = a - np.min(a)
+            return a / np.max(a)
+        if mode == "single":
+            for i, img in enumerate(imgs):
+                imgs[i] = scale(img, np.nanpercentile(img, clip[0]), np.percentile(img, clip[1]))
+            return imgs
+        if mode == "first":
+            return scale(imgs, np.nanpercentile(imgs[0], clip[0]), np.percentile(imgs[0], clip[1]))
+        if mode == "all":
+            return scale(imgs, np.nanpercentile(imgs, clip[0]), np.percentile(imgs, clip[1]))
+        raise ValueError(f"normalization_mode {mode} not valid!")
+
+    @staticmethod
+    def geometry(imgs_shape, max_patch_size, add_tile):
+        """Tiling of ``predict.py:153-177``: (patch_size, N_x, N_y, padded extents, X_start, Y_start)."""
+        _, h, w = imgs_shape
+        ph = (min(h, max_patch_size[0]) + 15) // 16 * 16
+        pw = (min(w, max_patch_size[1]) + 15) // 16 * 16
+        n_x = int(np.ceil(h / ph)) + add_tile
+        n_y = int(np.ceil(w / pw)) + add_tile
+        H, W = h + max(ph - h, 0), w + max(pw - w, 0)
+        return (ph, pw), n_x, n_y, (H, W), tile_starts(H, ph, n_x), tile_starts(W, pw, n_y)
+
+    @classmethod
+    def weight_plane(cls, j, k, n_x, n_y, patch_size):
+        """Ones with ``safe_margin`` rows / columns zeroed on every side of tile (j, k) that has a neighbour (``predict.py:259-269``)."""
+        w, m = np.ones(patch_size, dtype="float32"), cls.safe_margin
+        if j > 0:
+            w[:m, :] = 0
+        if j < n_x - 1:
+            w[-m:, :] = 0
+        if k > 0:
+            w[:, :m] = 0
+        if k < n_y - 1:
+            w[:, -m:] = 0
+        return w
+
+    def _split(self, imgs):
+        self.patch_size, self.N_x, self.N_y, (H, W), self.X_start, self.Y_start = self.geometry(self.imgs_shape, self.max_patch_size, self.add_tile)
+        ph, pw = self.patch_size
+        self.N_per_img = self.N_x * self.N_y
+        self.N = self.N_per_img * self.imgs_shape[0]
+        imgs = np.pad(imgs, ((0, 0), (0, H - self.imgs_shape[1]), (0, W - self.imgs_shape[2])), "reflect")
+        sx = int(self.X_start[1]) if self.N_x > 1 else 1
+        sy = int(self.Y_start[1]) if self.N_y > 1 else 1
+        if sx < 1 or sy < 1:
+            raise ValueError("slice step cannot be zero (add_tile on an image no larger than one patch)")      # as upstream's view[::0]
+        win = np.lib.stride_tricks.sliding_window_view(imgs, self.patch_size, axis=(1, 2))[:, ::sx, ::sy][:, :self.N_x, :self.N_y]
+        return np.ascontiguousarray(win).reshape(-1, ph, pw)
+
+    def _predict_and_stitch(self, patches, batch_size):
+        n_img, h, w = self.imgs_shape
+        ph, pw = self.patch_size
+        heads, cin = self.model_params["output_heads"], self.model_params["in_channels"]
+        H, W = max(ph, h), max(pw, w)
+        stitch = {k: [_Stitcher(self.device, heads[k]["channels"], (1, H, W)) for _ in range(n_img)] for k in self.target_keys}
+        sums = {k: torch.zeros((), dtype=torch.float64, device=self.device) for k in self.target_keys}
+        wcache = {}
+
+        def weight_of(j, k):
+            flags = (j > 0, j < self.N_x - 1, k > 0, k < self.N_y - 1)
+            if flags not in wcache:
+                wcache[flags] = torch.from_numpy(self.weight_plane(j, k, self.N_x, self.N_y, self.patch_size)[None]).to(self.device).contiguous()
+            return wcache[flags]
+        with torch.no_grad():
+            for b in range(0, patches.shape[0], batch_size):
+                x = torch.from_numpy(patches[b:b + batch_size]).to(self.device, non_blocking=True).view(-1, cin, ph, pw)
+                out = self.model(x)
+                for key in self.target_keys:
+                    res = out[key]
+                    want = (x.shape[0], heads[key]["channels"], ph, pw)
+                    if tuple(res.shape) != want:
+                        raise RuntimeError(f"Shape mismatch for target key '{key}': predicted {tuple(res.shape)}, expected {want}")
+                    p16 = res.to(torch.float16).float()                 # the reference keeps patches as float16
+                    sums[key] += p16.double().sum()
+                    for i in range(p16.shape[0]):
+                        img, tile = divmod(b + i, self.N_per_img)
+                        j, k = divmod(tile, self.N_y)
+                        stitch[key][img].add(p16[i].unsqueeze(1), (0, int(self.X_start[j]), int(self.Y_start[k])), weight=weight_of(j, k))
+        result = {}
+        for key in self.target_keys:
+            c = heads[key]["channels"]
+            fill = float(np.float16(float(sums[key]) / (patches.shape[0] * c * ph * pw)))      # np.mean of a float16 array is float16
+            done = []
+            for s_ in stitch[key]:
+                done.append(torch.where(s_.wsum[0].unsqueeze(0) > 0, s_.finish(False), torch.full((), fill, device=self.device)))
+            res = torch.stack(done).cpu().numpy()[:, :, 0]               # (n_img, channels, H, W)
+            result[key] = np.squeeze(res[:, :, :h, :w])
+        return result

@@ -301,6 +301,48 @@ int biu_seg_loss_coef(const float* g, const float* saved, int n, long long per_s
 int biu_head_dlogits(const float* g_logits, const float* g_act, const float* activated, int act, int n, int ch, long long spatial,
                      float* dst, int dst_channels, int dst_c0, biu_stream stream);
 
+/* The criteria of the 2-D multi-output trainer (multi_output_unet/losses.py) on ACTIVATED head outputs: pred / target fp32 contiguous
+ * [n, c, h, w] as the head kernel emits them; one head with its nlev <= BIU_MO2D_MAX_LEVELS deep-supervision predictions per launch
+ * (multi_output_unet/train.py:157-181: the levels share a target).  e = pred - target, M = n c h w, G_y / G_x = torch.gradient along h / w.
+ *   kind                          (p0, p1, p2)                    value
+ *   0 BCEDiceLoss                 (bce_weight, dice_weight, -)    p0 mean(-t max(log p, -100) - (1-t) max(log(1-p), -100)) + p1 (1 - (2 sum pt + 1e-5) / (sum p + sum t + 1e-5))
+ *   1 TverskyLoss, 2 logcosh...   (alpha, beta, smooth)           1 - Tv | log cosh(1 - Tv),  Tv = (TP + s) / (TP + alpha FP + beta FN + s) on probabilities
+ *   3 MSELoss  4 MAELoss  5 HuberLoss (delta, -, -)               mean e^2 | mean |e| | mean(|e| < delta ? e^2 / 2 : delta (|e| - delta / 2))
+ *   6 DistanceGradientLoss        (alpha, -, -)                   mean e^2 + alpha (mean (G_y e)^2 + mean (G_x e)^2)
+ *   7 WeightedDistanceGradient... (alpha, beta, -)                w = t > 0 ? beta : 1 - beta, e~ = w e: mean e~^2 + mean |e~| + alpha (mean (G_y e~)^2 + mean (G_x e~)^2)
+ *   8 WeightedVectorFieldLoss     (beta, magnitude_weight, -)     c == 2; w = (t0 != 0 or t1 != 0) ? beta : 1 - beta:
+ *                                                                 mean (w e)^2 + mean |w e| + p1 mean_{n h w} (w (p0^2 + p1^2) - w (t0^2 + t1^2))^2
+ * biu_mo2d_loss_fwd:    partial[nlev][biu_mo2d_loss_blocks(M)][BIU_MO2D_SLOTS] per-block sums (no atomics: bit-reproducible).  Kinds 6, 7
+ *                       refuse h < 2 or w < 2 (BIU_ERR_SHAPE), as torch.gradient does; kind 8 refuses c != 2.
+ * biu_mo2d_loss_finish: ONE one-block launch for all heads and levels of a step.  terms (device array, nterms <= BIU_MO2D_MAX_TERMS) name
+ *                       each (head, level): its partial rows (offset in floats into `workspace`), kind, parameters and weight
+ *                       (supervision weight x head weight) ->
+ *                       saved[8 + 8 nterms] = { sum_t weight_t loss_t, #pred outside [0, 1], #target outside [0, 1] (kind 0 terms), 0 x 5,
+ *                                               then per term { loss_t, merged sums[6], 0 } }.
+ * biu_mo2d_loss_coef:   g = d / d total (device scalar) -> coef[nterms][4].
+ * biu_mo2d_loss_bwd:    dpred[l] = d total / d pred[l] for the nlev levels of one head from its coef rows (coef + 4 * first term); the
+ *                       torch.gradient kinds gather G^T G e (a +-2 stencil per axis with its edge rows / columns), no atomics.
+ * (ea, eb): what the per-element arithmetic needs -- kind 5: (delta, 0); kinds 7, 8: (beta, 1 - beta) as the caller rounds them, i.e. the
+ * weight where the target is set and elsewhere; ignored by the other kinds.
+ * pred / dpred: host arrays of nlev device pointers.  16-byte accesses when every pointer is 16-byte aligned (and w % 4 == 0 for kinds
+ * 6, 7, h w % 4 == 0 for kind 8), with a scalar tail for the flat kinds; scalar accesses otherwise.                                    */
+#define BIU_MO2D_MAX_LEVELS 4
+#define BIU_MO2D_MAX_TERMS 32
+#define BIU_MO2D_SLOTS 8
+typedef struct biu_mo2d_term {
+    int kind, nb;               /* nb: rows of this term's partial (biu_mo2d_loss_blocks)          */
+    long long partial_off;      /* floats, into the workspace handed to biu_mo2d_loss_finish       */
+    long long numel, pixels;    /* n c h w and n h w                                               */
+    float p0, p1, p2, weight;
+} biu_mo2d_term;
+int biu_mo2d_loss_blocks(long long numel);
+int biu_mo2d_loss_fwd(int kind, float ea, float eb, const float* const* pred, int nlev, const float* target, int n, int c, int h, int w,
+                      float* partial, biu_stream stream);
+int biu_mo2d_loss_finish(const biu_mo2d_term* terms, int nterms, const float* workspace, float* saved, biu_stream stream);
+int biu_mo2d_loss_coef(const biu_mo2d_term* terms, int nterms, const float* g, const float* saved, float* coef, biu_stream stream);
+int biu_mo2d_loss_bwd(int kind, float ea, float eb, const float* const* pred, int nlev, const float* target, int n, int c, int h, int w,
+                      const float* coef, float* const* dpred, biu_stream stream);
+
 /* Trilinear x2 up-sampling, align_corners = False (F.interpolate(scale_factor=2, mode='trilinear'),
  * unet3d/unet3d.py:82,89,96): out = interp(T(x)); depth is doubled when out->d == 2 * x->d, kept when equal.
  * bwd: dx (+)= adjoint(dout).                                                                                        */

@@ -1,0 +1,235 @@
+"""On-the-fly training augmentation on the device for uint8 tile batches (``biu_augment_u8``).
+
+The reference augments offline: ``DataProcess.__augment`` runs an albumentations pipeline ``aug_factor`` times per tile and writes every
+result to disk (``unet/data.py:217-245``, ``siam_unet/data.py:236-243``, ``unet3d/data.py:209-239``).  Here the same five transforms run
+where the batch already is, fresh every epoch, in one kernel launch per field:
+
+=========  ==============================================================================================================
+recipe     stages (in the reference's order)
+=========  ==============================================================================================================
+"unet"     rot90 -> shift_scale_rotate -> brightness_contrast -> blur -> mult_noise
+"siam"     rot90 -> shift_scale_rotate -> gauss_noise -> brightness_contrast
+"unet3d"   as "siam"; the z-planes of a volume are channels, every plane gets the same in-plane transform
+=========  ==============================================================================================================
+
+The whole pipeline is applied with probability ``p``; ``shift_scale_rotate`` and ``brightness_contrast`` with 0.5, ``blur`` with 0.2, the
+noise stage with 0.3.  Fields named ``mask`` are masks (nearest-neighbour gather, nothing else touches them), every other field is an image
+(bilinear gather, then the intensity stages); ``kinds={"name": "mask" | "image"}`` overrides.  After every stage the value is clipped to
+[0, 255] and rounded to nearest-even, as a uint8 pipeline does.
+
+Geometry.  ``shift_scale_rotate`` maps a source pixel forward by ``x' = s (cos t (x - cx) + sin t (y - cy)) + cx + dx W``,
+``y' = s (-sin t (x - cx) + cos t (y - cy)) + cy + dy H`` about ``(cx, cy) = ((W - 1) / 2, (H - 1) / 2)``; with this sign a rotation by
++90 degrees of a square tile equals ``np.rot90(x, 1)`` and -90 degrees ``np.rot90(x, 3)``.  ``rot90`` is a pixel permutation, so it is composed
+with the inverse of that map into ONE 2x3 matrix per sample, computed on the host and handed to the kernel in float64 (the kernel does no
+trigonometry; its coordinates and interpolation weights are float64 too, so the gather agrees with a float64 restatement): one resampling per field.
+
+Randomness.  The per-sample record is a pure function of ``(seed, epoch, dataset index)`` (numpy's Philox generator with the key (seed, epoch) and the counter set to the index), so it does
+not depend on batch composition, thread timing or call order; per-pixel noise is Philox4x32-10 in the kernel, keyed by the seed with the
+counter (element group, dataset index, epoch, field-and-stage id).  Same seed -> same epoch, bit for bit.
+
+This is distribution-level equivalence to the reference pipeline, not bit parity ("On-device augmentation").
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import struct
+import threading
+import zlib
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+GATE, SSR, BC, BLUR, MULT, GAUSS = 1, 2, 4, 8, 16, 32          # include/biu.h: BIU_AUG_*
+ORDER_UNET, ORDER_SIAM = 0, 1
+MAX_BLUR = 15
+
+# include/biu.h: biu_aug_params, 96 bytes
+PARAMS_DTYPE = np.dtype([("flags", "<u4"), ("rot_k", "<u4"), ("blur_k", "<u4"), ("index", "<u4"), ("m", "<f8", (6,)),
+                         ("alpha", "<f4"), ("beta", "<f4"), ("noise_a", "<f4"), ("noise_b", "<f4"),
+                         ("angle", "<f4"), ("scale", "<f4"), ("dx", "<f4"), ("dy", "<f4")])
+assert PARAMS_DTYPE.itemsize == 96
+
+RECIPES = {"unet": ORDER_UNET, "siam": ORDER_SIAM, "unet3d": ORDER_SIAM}
+STAGE_P = {"shift_scale_rotate": 0.5, "brightness_contrast": 0.5, "blur": 0.2, "noise": 0.3}
+
+
+def field_id(name: str) -> int:
+    """28-bit id of a field name in the noise counter: the same whatever other fields a batch holds."""
+    return zlib.crc32(name.encode()) >> 4
+
+
+def _matrix(k: int, angle: float, scale: float, dx: float, dy: float, h: int, w: int):
+    """``inverse_matrix`` in plain Python floats (the feeder thread draws records while the training thread enqueues: every microsecond
+    here is taken from the interpreter lock both share)."""
+    if k % 2 and h != w:
+        raise ValueError("rot90 by an odd number of quarter turns needs a square tile")
+    if angle != 0:
+        t = math.radians(angle)
+        c, s = math.cos(t) / scale, math.sin(t) / scale
+    else:
+        c, s = 1.0 / scale, 0.0
+    # inverse of the forward matrix scale [[cos, sin], [-sin, cos]]: a = [[c, -s], [s, c]]; offset b = centre - a (centre + shift)
+    cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
+    ux, uy = cx + dx * w, cy + dy * h
+    bx, by = cx - (c * ux - s * uy), cy - (s * ux + c * uy)
+    # np.rot90(src, k)[y, x] = src[sy, sx] with (sx, sy) = P_k (x, y) + o_k; below: P_k a and P_k b + o_k
+    if k == 0:
+        return c, -s, bx, s, c, by
+    if k == 1:
+        return -s, -c, w - 1 - by, c, -s, bx
+    if k == 2:
+        return -c, s, w - 1 - bx, -s, -c, h - 1 - by
+    return s, c, by, -c, s, h - 1 - bx
+
+
+def inverse_matrix(rot_k: int, angle: float, scale: float, dx: float, dy: float, h: int, w: int) -> np.ndarray:
+    """float64 ``[m0 .. m5]``: output pixel (x, y) samples the source at ``(m0 x + m1 y + m2, m3 x + m4 y + m5)`` for
+    ``shift_scale_rotate(np.rot90(src, rot_k))``.  Whole-pixel cases come out as exact integers."""
+    return np.array(_matrix(int(rot_k) % 4, float(angle), float(scale), float(dx), float(dy), int(h), int(w))) + 0.0     # no negative zeros
+
+
+_F4 = struct.Struct("<4f")
+_REC = struct.Struct("<4I6d8f")
+assert _REC.size == PARAMS_DTYPE.itemsize
+
+
+def _pack(buf, offset, index, h, w, gate, rot_k, ssr, bc, blur_k, noise_flag, noise_a, noise_b):
+    """Write one record at ``buf[offset:]``; stages behind a closed gate, and stages not given, leave the identity.  The matrix is computed
+    from the fp32 values the record keeps, so the record alone says what the kernel was asked to do."""
+    if not gate:
+        rot_k, ssr, bc, blur_k, noise_flag = 0, None, None, 0, 0
+    flags = (GATE if gate else 0) | (SSR if ssr is not None else 0) | (BC if bc is not None else 0) | (BLUR if blur_k else 0) | noise_flag
+    angle, scale, dx, dy = _F4.unpack(_F4.pack(*ssr)) if ssr is not None else (0.0, 1.0, 0.0, 0.0)
+    alpha, beta = (bc[0], 255.0 * bc[1]) if bc is not None else (1.0, 0.0)
+    if not noise_flag:
+        noise_a = noise_b = 0.0
+    _REC.pack_into(buf, offset, flags, rot_k, blur_k, index, *_matrix(rot_k % 4, angle, scale, dx, dy, h, w), alpha, beta, noise_a, noise_b,
+                   angle, scale, dx, dy)
+
+
+def record(index: int, h: int, w: int, *, gate: bool = True, rot_k: int = 0, ssr=None, bc=None, blur_k: int = 0, mult=None,
+           gauss_sigma: Optional[float] = None) -> np.ndarray:
+    """One parameter record from its logical description: ``ssr = (angle in degrees, scale, dx, dy)``, ``bc = (alpha, beta)`` with beta as a
+    fraction of 255, ``mult = (lo, hi)``.  With ``gate=False`` the sample passes unchanged.  ``Augmenter.draw`` builds its records the same way."""
+    if blur_k and (blur_k % 2 == 0 or not 1 <= blur_k <= MAX_BLUR):
+        raise ValueError(f"blur kernel {blur_k}: odd and at most {MAX_BLUR}")
+    if mult is not None and gauss_sigma is not None:
+        raise ValueError("a record carries one noise stage")
+    noise = (MULT, mult[0], mult[1] - mult[0]) if mult is not None else (GAUSS, gauss_sigma, 0.0) if gauss_sigma is not None else (0, 0.0, 0.0)
+    buf = bytearray(_REC.size)
+    _pack(buf, 0, int(index), int(h), int(w), bool(gate), int(rot_k), ssr, bc, int(blur_k), *noise)
+    return np.frombuffer(buf, dtype=PARAMS_DTYPE)[0]
+
+
+class Augmenter:
+    """Draws per-sample parameter records on the host and runs ``biu_augment_u8`` on device batches; see the module docstring."""
+
+    def __init__(self, recipe: str, *, shiftscalerotate=(0, 0, 0), brightness_contrast=(0.25, 0.25), noise_lims=(0.5, 1.2), noise_amp=10,
+                 blur_limit=(3, 7), p: float = 0.8, seed: int = 0, kinds: Optional[Dict[str, str]] = None, shape: Optional[Sequence[int]] = None):
+        if recipe not in RECIPES:
+            raise ValueError(f'recipe "{recipe}" not defined (one of {sorted(RECIPES)})')
+        self.recipe, self.order = recipe, RECIPES[recipe]
+        self.shiftscalerotate = tuple(float(v) for v in shiftscalerotate)
+        self.brightness_contrast = tuple(float(v) for v in brightness_contrast)
+        self.noise_lims = tuple(float(v) for v in noise_lims)
+        self.noise_amp = float(noise_amp)
+        self.blur_limit = (int(blur_limit), int(blur_limit)) if np.isscalar(blur_limit) else tuple(int(v) for v in blur_limit)
+        if len(self.shiftscalerotate) != 3 or len(self.brightness_contrast) != 2 or len(self.noise_lims) != 2 or len(self.blur_limit) != 2:
+            raise ValueError("shiftscalerotate takes 3 limits, brightness_contrast, noise_lims and blur_limit 2")
+        if self.blur_limit[1] > MAX_BLUR:
+            raise ValueError(f"blur_limit {self.blur_limit}: box kernels above {MAX_BLUR} are not supported")
+        self.blur_sizes = [k for k in range(max(1, self.blur_limit[0]), self.blur_limit[1] + 1) if k % 2]
+        if not self.blur_sizes:
+            raise ValueError(f"blur_limit {self.blur_limit} holds no odd kernel size")
+        if self.noise_amp < 0 or not 0.0 <= p <= 1.0:
+            raise ValueError("noise_amp is a variance and p a probability")
+        self.p, self.seed = float(p), int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.kinds = dict(kinds or {})
+        for v in self.kinds.values():
+            if v not in ("mask", "image"):
+                raise ValueError(f'kind "{v}": "mask" or "image"')
+        self.shape = tuple(shape) if shape is not None else None
+        self._bitgen = np.random.Philox(key=[0, 0])              # draw() sets key and counter per sample
+        self._gen, self._state, self._lock = np.random.Generator(self._bitgen), self._bitgen.state, threading.Lock()
+
+    @classmethod
+    def from_store(cls, store, recipe: str, **overrides) -> "Augmenter":
+        """Limits from the attributes a ``TileStore`` records (those of the ``DataProcess`` it was converted from), else the defaults."""
+        kw = {}
+        for a in ("shiftscalerotate", "brightness_contrast", "noise_lims", "noise_amp", "blur_limit"):
+            v = getattr(store, "attrs", {}).get(a)
+            if v is not None:
+                kw[a] = v
+        kw["shape"] = tuple(next(iter(store.fields.values())))
+        kw.update(overrides)
+        return cls(recipe, **kw)
+
+    def describe(self) -> dict:
+        return {"recipe": self.recipe, "p": self.p, "seed": self.seed, "shiftscalerotate": self.shiftscalerotate,
+                "brightness_contrast": self.brightness_contrast, "noise_lims": self.noise_lims, "noise_amp": self.noise_amp,
+                "blur_limit": self.blur_limit, "stage_p": dict(STAGE_P), "kinds": dict(self.kinds)}
+
+    def kind(self, name: str) -> str:
+        return self.kinds.get(name, "mask" if name == "mask" else "image")
+
+    # ---- host: the per-sample records -------------------------------------------------------------------------------------------
+    def draw(self, epoch: int, indices, shape: Optional[Sequence[int]] = None) -> np.ndarray:
+        """Record array for the samples ``indices`` of epoch ``epoch``; ``shape``: the tile shape (its last two axes count)."""
+        shape = tuple(shape) if shape is not None else self.shape
+        if shape is None or len(shape) < 2:
+            raise ValueError("Augmenter.draw needs the tile shape (constructor's or this call's `shape`)")
+        h, w = int(shape[-2]), int(shape[-1])
+        idx = np.atleast_1d(np.asarray(indices, dtype=np.int64)).tolist()
+        buf = bytearray(len(idx) * _REC.size)
+        sym = lambda v, a: (2.0 * v - 1.0) * a
+        lim, bcl, sizes, unet = self.shiftscalerotate, self.brightness_contrast, self.blur_sizes, self.order == ORDER_UNET
+        noise = (MULT, self.noise_lims[0], self.noise_lims[1] - self.noise_lims[0]) if unet else (GAUSS, math.sqrt(self.noise_amp), 0.0)
+        with self._lock:
+            for j, i in enumerate(idx):
+                # the generator's stream is a function of its key (seed, epoch) and counter (0, dataset index, 0, 0) alone; a fixed number of
+                # uniforms in a fixed order whatever the gates say: nothing shifts the stream
+                st = self._state
+                st["state"]["key"][:] = (self.seed, int(epoch) & 0xFFFFFFFFFFFFFFFF)
+                st["state"]["counter"][:] = (0, i & 0xFFFFFFFFFFFFFFFF, 0, 0)
+                st["buffer_pos"], st["has_uint32"] = 4, 0
+                self._bitgen.state = st
+                u = self._gen.random(13).tolist()
+                _pack(buf, j * _REC.size, i & 0xFFFFFFFF, h, w, u[0] < self.p, int(u[1] * 4) if h == w else 2 * int(u[1] * 2),
+                      (sym(u[3], lim[2]), 1.0 + sym(u[4], lim[1]), sym(u[5], lim[0]), sym(u[6], lim[0])) if u[2] < STAGE_P["shift_scale_rotate"] else None,
+                      (1.0 + sym(u[8], bcl[1]), sym(u[9], bcl[0])) if u[7] < STAGE_P["brightness_contrast"] else None,
+                      sizes[min(int(u[11] * len(sizes)), len(sizes) - 1)] if unet and u[10] < STAGE_P["blur"] else 0,
+                      *(noise if u[12] < STAGE_P["noise"] else (0, 0.0, 0.0)))
+        return np.frombuffer(buf, dtype=PARAMS_DTYPE)
+
+    # ---- device ------------------------------------------------------------------------------------------------------------------
+    def __call__(self, batch: Dict[str, torch.Tensor], params: np.ndarray, epoch: int, out: Optional[Dict[str, torch.Tensor]] = None,
+                 params_dev: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """Augment ``{field: uint8 device tensor [B, H, W] | [B, C or D, H, W]}`` with the records ``params`` (``draw``'s result, one per
+        sample) on the current stream; ``out``: tensors to write into (never the inputs: a gather cannot run in place); ``params_dev``: the
+        same records already on the device as bytes (the feeder uploads them with the batch)."""
+        from ._lib import check, lib
+        params = np.ascontiguousarray(params, dtype=PARAMS_DTYPE)
+        first = next(iter(batch.values()))
+        if len(params) != first.shape[0]:
+            raise ValueError(f"{len(params)} parameter records for a batch of {first.shape[0]}")
+        blurs = params["blur_k"][(params["flags"] & BLUR) != 0]
+        max_blur = int(blurs.max()) if len(blurs) else 0
+        if params_dev is None:
+            params_dev = torch.from_numpy(params.view(np.uint8).copy()).to(first.device)
+        stream = C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)
+        res = {}
+        for name, t in batch.items():
+            if t.dtype != torch.uint8 or not t.is_cuda or t.dim() not in (3, 4) or not t.is_contiguous():
+                raise ValueError(f'field "{name}": a contiguous uint8 device tensor [B, H, W] or [B, C, H, W] is expected')
+            dst = out[name] if out is not None else torch.empty_like(t)
+            if dst.shape != t.shape or dst.dtype != torch.uint8 or dst.device != t.device or not dst.is_contiguous() or dst.data_ptr() == t.data_ptr():
+                raise ValueError(f'field "{name}": the output must be a second contiguous uint8 tensor of the same shape and device')
+            planes = t.shape[1] if t.dim() == 4 else 1
+            mask = self.kind(name) == "mask"
+            check(lib.biu_augment_u8(C.c_void_p(t.data_ptr()), C.c_void_p(dst.data_ptr()), t.shape[0], planes, t.shape[-2], t.shape[-1],
+                                     int(mask), C.c_void_p(params_dev.data_ptr()), self.order, 0 if mask else max_blur, self.seed,
+                                     int(epoch) & 0xFFFFFFFF, field_id(name), stream), "augment_u8")
+            res[name] = dst
+        return res

@@ -14,8 +14,9 @@ flat uint8 file per field, mapped into memory:
   PCIe) while the current step computes, and the batch reaches the network as uint8 -- the 1/255 scaling rides in the input-layout
   kernel (``biu_from_nchw_u8``), targets are widened by ``biu_u8_to_f32``.
 
-TIFF decoding, augmentation and tiling stay out of scope (``DataProcess``): they run once, offline, and their output is what this
-store holds.
+TIFF decoding and tiling stay out of scope (``DataProcess``): they run once, offline, and their output is what this store holds.
+Augmentation does not have to: ``DeviceFeeder(..., augmenter=augment.Augmenter(...))`` augments every training batch on the device, fresh
+every epoch, from a store of un-augmented tiles (``augment.py``).
 """
 from __future__ import annotations
 
@@ -64,7 +65,7 @@ class TileStore(torch.utils.data.Dataset):
         keys = list(keys) if keys is not None else [k for k, v in first.items() if torch.is_tensor(v) or isinstance(v, np.ndarray)]
         fields = {k: tuple(np.asarray(first[k]).shape) for k in keys}
         attrs = {}
-        for a in ("dim_out", "aug_factor", "clip_threshold", "noise_lims", "noise_amp", "brightness_contrast", "shiftscalerotate"):
+        for a in ("dim_out", "aug_factor", "clip_threshold", "noise_lims", "noise_amp", "brightness_contrast", "shiftscalerotate", "blur_limit"):
             if hasattr(dataset, a):
                 v = getattr(dataset, a)
                 attrs[a] = list(v) if isinstance(v, (tuple, list)) else v
@@ -102,9 +103,16 @@ class TileStore(torch.utils.data.Dataset):
 
 
 class DeviceFeeder:
-    """Iterable over uint8 device batches of a ``TileStore`` (one epoch per ``iter()``), ``depth`` batches in flight."""
+    """Iterable over uint8 device batches of a ``TileStore`` (one epoch per ``iter()``), ``depth`` batches in flight.
 
-    def __init__(self, store: TileStore, indices: Sequence[int], batch_size: int, device, drop_last: bool = True, depth: int = 3):
+    With an ``augmenter`` (``augment.Augmenter``) the feeder thread also draws the per-sample parameter records, uploads them with the batch
+    and enqueues the augmentation launches on the copy stream in front of the ``ready`` event, into a second set of device buffers: the work
+    overlaps the running step exactly as the upload does.  ``epoch`` (the second argument of ``Augmenter.draw``) advances per ``iter()``.
+    ``augment_stream="main"`` enqueues the launches on the consumer's stream at hand-over instead (same bytes; for A/B measurements of how
+    the augmentation kernels share the device with the step, ``tools/bench_augment.py``)."""
+
+    def __init__(self, store: TileStore, indices: Sequence[int], batch_size: int, device, drop_last: bool = True, depth: int = 3,
+                 augmenter=None, augment_stream: str = "copy"):
         self.store, self.indices, self.batch_size = store, list(indices), batch_size
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -117,6 +125,15 @@ class DeviceFeeder:
                                else torch.empty((batch_size,) + shp, dtype=torch.uint8, device=self.device))
         self.slots = [{"host": {k: mk(s, True) for k, s in store.fields.items()}, "dev": {k: mk(s, False) for k, s in store.fields.items()},
                        "ready": None, "free": None, "released": threading.Event()} for _ in range(self.depth)]
+        if augment_stream not in ("copy", "main"):
+            raise ValueError('augment_stream: "copy" or "main"')
+        self.augmenter, self.epoch, self.augment_on_main = augmenter, 0, augment_stream == "main"
+        if augmenter is not None:
+            from .augment import PARAMS_DTYPE
+            for slot in self.slots:
+                slot["aug"] = {k: mk(s, False) for k, s in store.fields.items()}
+                slot["params_host"] = torch.empty(batch_size * PARAMS_DTYPE.itemsize, dtype=torch.uint8).pin_memory()
+                slot["params_dev"] = torch.empty(batch_size * PARAMS_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
 
     def __len__(self):
         n = len(self.indices)
@@ -127,6 +144,8 @@ class DeviceFeeder:
         if self.drop_last:
             batches = [b for b in batches if len(b) == self.batch_size]
         filled: "queue.Queue" = queue.Queue(maxsize=self.depth - 1)
+        epoch, out_key = self.epoch, "dev" if self.augmenter is None else "aug"
+        self.epoch += 1
         stop = threading.Event()
         for slot in self.slots:
             slot["released"].set()
@@ -150,9 +169,19 @@ class DeviceFeeder:
                 if slot["free"] is not None:
                     slot["free"].synchronize()              # ... and the step that read its device buffers has finished on the GPU
                 self.store.batch_u8(idx, out=slot["host"])
+                if self.augmenter is not None:
+                    params = self.augmenter.draw(epoch, idx, shape=next(iter(self.store.fields.values())))
+                    nbytes = params.nbytes
+                    slot["params_host"][:nbytes].numpy()[:] = params.view(np.uint8)
                 with torch.cuda.stream(self.copy_stream):
                     for k in slot["host"]:
                         slot["dev"][k][:len(idx)].copy_(slot["host"][k][:len(idx)], non_blocking=True)
+                    if self.augmenter is not None:
+                        slot["params_dev"][:nbytes].copy_(slot["params_host"][:nbytes], non_blocking=True)
+                        slot["params"] = params
+                    if self.augmenter is not None and not self.augment_on_main:
+                        self.augmenter({k: v[:len(idx)] for k, v in slot["dev"].items()}, params, epoch,
+                                       out={k: v[:len(idx)] for k, v in slot["aug"].items()}, params_dev=slot["params_dev"])
                     ev = torch.cuda.Event()
                     ev.record(self.copy_stream)
                 slot["ready"] = ev
@@ -171,7 +200,10 @@ class DeviceFeeder:
                 bi, nb = item
                 slot = self.slots[bi % self.depth]
                 torch.cuda.current_stream(self.device).wait_event(slot["ready"])     # device-side wait: the host does not block
-                yield {k: v[:nb] for k, v in slot["dev"].items()}
+                if self.augmenter is not None and self.augment_on_main:
+                    self.augmenter({k: v[:nb] for k, v in slot["dev"].items()}, slot["params"], epoch,
+                                   out={k: v[:nb] for k, v in slot["aug"].items()}, params_dev=slot["params_dev"])
+                yield {k: v[:nb] for k, v in slot[out_key].items()}
                 done = torch.cuda.Event()
                 done.record(torch.cuda.current_stream(self.device))                  # everything enqueued so far read the slot
                 slot["free"] = done

@@ -12,8 +12,8 @@ numerics-relevant quirks, so a training run is step-for-step comparable:
 * The saved ``'optimizer'`` entry is the construction-time state (2-D / 3-D), never refreshed.
 
 What differs by design: the network class comes from this package (every layer a HIP kernel), the optimizer is the fused
-``biu_adam_step``, and data sets are any ``torch.utils.data.Dataset`` yielding the reference's dict items (TIFF I/O and
-augmentation are out of scope).
+``biu_adam_step``, and data sets are any ``torch.utils.data.Dataset`` yielding the reference's dict items (TIFF I/O is out of scope; ``Trainer2D`` / ``Trainer3D`` / ``TrainerSiam``
+take ``augment=True`` to augment the training batches of a ``feed.TileStore`` on the device, ``augment.py``).
 """
 from __future__ import annotations
 
@@ -50,13 +50,30 @@ def _make_criterion(name, params, extra=None):
     return table[name](params[0], params[1])
 
 
-def _loaders(dataset, train_data, val_data, batch_size, device):
+def _resolve_augment(augment, dataset, device, recipe):
+    """``augment`` keyword of the uint8 families' Trainers -> ``augment.Augmenter`` or None.  On-device augmentation works on the uint8 batches of a
+    ``DeviceFeeder``, so anything but a ``TileStore`` on a GPU is refused rather than silently trained un-augmented."""
+    if augment is None or augment is False:
+        return None
+    from .augment import Augmenter
+    from .feed import TileStore
+    if not isinstance(dataset, TileStore) or torch.device(device).type != "cuda":
+        raise ValueError("augment: on-device augmentation needs a feed.TileStore data set and a GPU device")
+    if augment is True:
+        return Augmenter.from_store(dataset, recipe)
+    if not isinstance(augment, Augmenter):
+        raise ValueError("augment: None, True or an augment.Augmenter")
+    return augment
+
+
+def _loaders(dataset, train_data, val_data, batch_size, device, augmenter=None):
     """The reference's loaders (``DataLoader(shuffle=False, drop_last=True, num_workers=0, pin_memory=True)``, unet/train.py:92-93)
     -- or, for a memory-mapped ``feed.TileStore``, asynchronous uint8 feeders over the same index split (same order, same
     batches; the tiles cross PCIe as bytes while the previous step computes)."""
     from .feed import DeviceFeeder, TileStore
     if isinstance(dataset, TileStore) and torch.device(device).type == "cuda":
-        return (DeviceFeeder(dataset, train_data.indices, batch_size, device), DeviceFeeder(dataset, val_data.indices, batch_size, device))
+        return (DeviceFeeder(dataset, train_data.indices, batch_size, device, augmenter=augmenter),     # training only, never validation
+                DeviceFeeder(dataset, val_data.indices, batch_size, device))
     return (DataLoader(train_data, batch_size=batch_size, pin_memory=True, drop_last=True),
             DataLoader(val_data, batch_size=batch_size, pin_memory=True, drop_last=True))
 
@@ -93,20 +110,25 @@ class _EpochLoop:
     """Shared skeleton: split, loaders, Adam + ReduceLROnPlateau, best-validation checkpointing."""
     item_key = "image"
 
-    def _setup(self, dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter):
+    def _setup(self, dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter=None):
         self.data, self.num_epochs, self.batch_size, self.lr = dataset, num_epochs, batch_size, lr
         self.best_loss = torch.tensor(float("inf"))
         self.save_iter, self.save_dir, self.save_name = save_iter, save_dir, save_name
         n_val = int(len(dataset) * val_split)
         self.dim = dataset.dim_out
         train_data, val_data = random_split(dataset, [len(dataset) - n_val, n_val])
-        self.train_loader, self.val_loader = _loaders(dataset, train_data, val_data, batch_size, self.device)
+        self.augmenter = augmenter
+        self.train_loader, self.val_loader = _loaders(dataset, train_data, val_data, batch_size, self.device, augmenter)
         self.optimizer = Adam(self.model.parameters(), lr=lr)
         self.scheduler = optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="min", patience=4, factor=0.1)
         os.makedirs(save_dir, exist_ok=True)
 
     def _data_attr(self, *names):
         return {n: getattr(self.data, n, None) for n in names}
+
+    def _augment_entry(self):
+        """Checkpoint entry of on-device augmentation; nothing when it is off, so those checkpoints keep their keys."""
+        return {} if self.augmenter is None else {"online_augmentation": self.augmenter.describe()}
 
     # subclasses: _forward_loss(batch, validating) -> loss
     def _train_epoch(self, epoch):
@@ -137,10 +159,13 @@ class Trainer2D(_EpochLoop):
     def __init__(self, dataset, num_epochs, network=Unet, batch_size=4, lr=1e-3, in_channels=1, out_channels=1,
                  channel_weights=None, n_filter=64, dilation=1, val_split=0.2, save_dir="./", save_name="model.pt",
                  save_iter=False, load_weights=False, loss_function="BCEDice", loss_params=(0.5, 0.5),
-                 device: Union[torch.device, str] = "auto", fp32_products: Optional[str] = None):
+                 device: Union[torch.device, str] = "auto", fp32_products: Optional[str] = None, augment=None):
         """``fp32_products`` (not in the reference): ``"exact"`` | ``"bf16x3"`` | ``"bf16x6"`` -- how the fp32 tensors of this trainer are
         multiplied (``bio_image_unet_amd.set_fp32_products``; process-wide).  ``"bf16x3"`` plays the role ``torch.backends.cudnn.allow_tf32``
-        plays for the reference; ``None`` leaves the process's mode alone (default: bf16x6, fp32-grade split products)."""
+        plays for the reference; ``None`` leaves the process's mode alone (default: bf16x6, fp32-grade split products).
+        ``augment`` (not in the reference): ``True`` or an ``augment.Augmenter`` -- the training batches of a ``feed.TileStore`` are augmented on
+        the device, fresh every epoch (recipe ``"unet"``); validation batches never are."""
+        augmenter = _resolve_augment(augment, dataset, _pick_device(device), "unet")
         if fp32_products is not None:
             from . import set_fp32_products
             set_fp32_products(fp32_products)
@@ -152,12 +177,12 @@ class Trainer2D(_EpochLoop):
         self.n_filter, self.in_channels, self.out_channels = n_filter, in_channels, out_channels
         self.channel_weights = torch.ones(out_channels) if channel_weights is None else torch.tensor(channel_weights)
         self.criterion = _make_criterion(loss_function, loss_params)
-        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter)
+        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter)
         self.params = {"optimizer": self.optimizer.state_dict(), "lr": lr, "loss_function": loss_function,
                        "loss_params": loss_params, "n_filter": n_filter, "dilation": dilation, "batch_size": batch_size,
                        "augmentation": getattr(dataset, "aug_factor", None), "in_channels": in_channels,
                        "out_channels": out_channels,
-                       **self._data_attr("clip_threshold", "noise_lims", "brightness_contrast", "shiftscalerotate")}
+                       **self._data_attr("clip_threshold", "noise_lims", "brightness_contrast", "shiftscalerotate"), **self._augment_entry()}
         if load_weights:
             self.state = torch.load(save_dir + "/" + save_name)
             self.model.load_state_dict(self.state["state_dict"])
@@ -203,9 +228,11 @@ class Trainer3D(_EpochLoop):
                  in_channels=1, out_channels=1, channel_weights=None, n_filter=64, dilation=1, val_split=0.2,
                  save_dir="./", save_name="model.pt", save_iter=False, load_weights=False, loss_function="BCEDice",
                  loss_params=(0.5, 0.5), time_loss_weight=0.1, device: Union[torch.device, str] = "auto",
-                 fp32_products: Optional[str] = None):
+                 fp32_products: Optional[str] = None, augment=None):
         """``fp32_products`` (not in the reference): ``"exact"`` | ``"bf16x3"`` | ``"bf16x6"`` -- how the fp32 3-D kernels of this trainer
-        multiply (``bio_image_unet_amd.set_fp32_products_3d``; process-wide, default ``"exact"``); ``None`` leaves the process mode alone."""
+        multiply (``bio_image_unet_amd.set_fp32_products_3d``; process-wide, default ``"exact"``); ``None`` leaves the process mode alone.
+        ``augment``: as for ``Trainer2D``, recipe ``"unet3d"`` (every z-plane of a volume gets the same in-plane transform)."""
+        augmenter = _resolve_augment(augment, dataset, _pick_device(device), "unet3d")
         if fp32_products is not None:
             from . import set_fp32_products_3d
             set_fp32_products_3d(fp32_products)
@@ -220,13 +247,13 @@ class Trainer3D(_EpochLoop):
         self.channel_weights = torch.ones(out_channels) if channel_weights is None else torch.tensor(channel_weights)
         self.criterion = _make_criterion(loss_function, loss_params)
         self.criterion_time = nn.SmoothL1Loss()
-        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter)
+        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter)
         self.params = {"optimizer": self.optimizer.state_dict(), "lr": lr, "loss_function": loss_function,
                        "loss_params": loss_params, "time_loss_weight": time_loss_weight, "n_filter": n_filter,
                        "use_interpolation": use_interpolation, "dilation": dilation, "batch_size": batch_size,
                        "augmentation": getattr(dataset, "aug_factor", None), "in_channels": in_channels,
                        "out_channels": out_channels,
-                       **self._data_attr("clip_threshold", "noise_amp", "brightness_contrast", "shiftscalerotate")}
+                       **self._data_attr("clip_threshold", "noise_amp", "brightness_contrast", "shiftscalerotate"), **self._augment_entry()}
         if load_weights:
             self.state = torch.load(save_dir + "/" + save_name)
             self.model.load_state_dict(self.state["state_dict"])
@@ -267,7 +294,8 @@ class TrainerSiam(_EpochLoop):
 
     def __init__(self, dataset, num_epochs, batch_size=4, lr=1e-3, n_filter=32, mode="max", val_split=0.2,
                  save_dir="./", save_name="model.pt", save_iter=False, loss_function="BCEDice", loss_params=(1, 1),
-                 load_weights=None, device: Union[torch.device, str] = "auto", fp32_products: Optional[str] = None):
+                 load_weights=None, device: Union[torch.device, str] = "auto", fp32_products: Optional[str] = None, augment=None):
+        augmenter = _resolve_augment(augment, dataset, _pick_device(device), "siam")      # see Trainer2D
         if fp32_products is not None:                 # see Trainer2D
             from . import set_fp32_products
             set_fp32_products(fp32_products)
@@ -277,7 +305,7 @@ class TrainerSiam(_EpochLoop):
         self.loss_function, self.loss_params = loss_function, loss_params
         # the Siam package's own criteria: its BCEDice takes nn.BCELoss on sigmoid(logits) (siam_unet/losses.py:5-39,73-105)
         self.criterion = _make_criterion(loss_function, loss_params, extra={"BCEDice": BCEDiceLossSiam, "weightedBCELoss": weightedBCELoss})
-        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter)
+        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter)
         if load_weights is not None:
             self.state = torch.load(load_weights)
             self.model.load_state_dict(self.state["state_dict"])
@@ -309,7 +337,7 @@ class TrainerSiam(_EpochLoop):
                           "optimizer": self.optimizer.state_dict(), "lr": self.lr, "loss": self.loss_function,
                           "loss_params": self.loss_params, "n_filter": self.n_filter, "mode": self.mode,
                           "augmentation": getattr(self.data, "aug_factor", None),
-                          **self._data_attr("clip_threshold", "noise_amp", "brightness_contrast", "shiftscalerotate")}
+                          **self._data_attr("clip_threshold", "noise_amp", "brightness_contrast", "shiftscalerotate"), **self._augment_entry()}
             with torch.no_grad():
                 val_loss = self.iterate(epoch, "val")
                 self.scheduler.step(val_loss)

@@ -527,6 +527,53 @@ int biu_stitch_finish(const float* acc, const float* wsum, int layers, int chann
                       biu_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * On-the-fly training augmentation of uint8 tile batches (the albumentations pipelines of unet/data.py:217-245,
+ * siam_unet/data.py:236-243, unet3d/data.py:209-239, which the reference runs offline)
+ *
+ * One record per sample, drawn on the host, shared by every field of the sample.  `m` is the INVERSE map of the composed rot90 and
+ * shift/scale/rotate: output pixel x, y samples the source at sx = m[0] x + m[1] y + m[2], sy = m[3] x + m[4] y + m[5] (bilinear for
+ * images, nearest for masks, reflect-101 outside).  It is double precision and so is the kernel's coordinate and interpolation arithmetic:
+ * in fp32 the coordinate error (1e-5 pixel at 256^2) moves 0.07 % of a noise image's pixels across a rounding tie, and a later stage with a
+ * gain above 1 (alpha, mult_noise) turns that grey level into two; in fp64 the gather agrees with a float64 restatement.
+ * The kernel reads flags, blur_k, index, m, alpha, beta, noise_a, noise_b; the rest documents the draw (rot_k, angle in degrees, scale,
+ * dx, dy as fractions of the tile).
+ *   BIU_AUG_BC    : v * alpha + beta                        (beta on the 0..255 scale)
+ *   BIU_AUG_BLUR  : blur_k x blur_k box mean, reflect-101  (odd, <= BIU_AUG_MAX_BLUR; stage order UNET only)
+ *   BIU_AUG_MULT  : v * (noise_a + noise_b * u)             (stage order UNET)
+ *   BIU_AUG_GAUSS : v + noise_a * N(0, 1)                   (stage order SIAM; Box-Muller)
+ * Stage order UNET: gather, BC, BLUR, MULT.  SIAM (also the 3-D recipe, planes as channels): gather, GAUSS, BC.  The value is clipped to
+ * [0, 255] and rounded to nearest-even after every stage.  Masks (is_mask != 0) stop after the gather.
+ * Noise: Philox4x32-10, key = seed, counter = (element / 4 for MULT, element / 2 for GAUSS, params.index, epoch, field_id * 16 + stage)
+ * with element = the pixel's index inside its sample's [planes, h, w] field; a MULT pixel takes word element % 4, a GAUSS pixel words
+ * 2 (element % 2) and the next; uniform = (word >> 8) * 2^-24.
+ *
+ * biu_augment_u8: src, dst [n, planes, h, w] uint8 on the device, dst != src; params: n records on the device; max_blur_k: the largest
+ *                 blur_k among the records whose BIU_AUG_BLUR is set (0: none -- the per-pixel kernel runs and a set bit is ignored).
+ * biu_philox_u32: out[4 i .. 4 i + 3] = Philox4x32-10(counter = (c0 + i, c1, c2, c3), key = seed), i < blocks -- the raw stream.
+ * ---------------------------------------------------------------------------------------------- */
+#define BIU_AUG_GATE 1u   /* the sample passed the pipeline gate (informational) */
+#define BIU_AUG_SSR 2u    /* shift/scale/rotate drawn (informational: it is part of m) */
+#define BIU_AUG_BC 4u
+#define BIU_AUG_BLUR 8u
+#define BIU_AUG_MULT 16u
+#define BIU_AUG_GAUSS 32u
+#define BIU_AUG_ORDER_UNET 0
+#define BIU_AUG_ORDER_SIAM 1
+#define BIU_AUG_STAGE_MULT 1u
+#define BIU_AUG_STAGE_GAUSS 2u
+#define BIU_AUG_MAX_BLUR 15
+typedef struct biu_aug_params {
+    uint32_t flags, rot_k, blur_k, index;
+    double m[6];
+    float alpha, beta, noise_a, noise_b;
+    float angle, scale, dx, dy;
+} biu_aug_params;             /* 96 bytes */
+int biu_augment_u8(const uint8_t* src, uint8_t* dst, int n, int planes, int h, int w, int is_mask, const biu_aug_params* params,
+                   int stage_order, int max_blur_k, unsigned long long seed, unsigned epoch, unsigned field_id, biu_stream stream);
+int biu_philox_u32(uint32_t* out, long long blocks, unsigned long long seed, unsigned c0, unsigned c1, unsigned c2, unsigned c3,
+                   biu_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused multi-tensor Adam                                                               [K14]
  * replaces torch.optim.Adam(lr) step: unet/train.py:102,139 (betas 0.9/0.999, eps 1e-8, no decay).
  * One launch updates `n` parameter tensors; ptrs are device arrays of device pointers.

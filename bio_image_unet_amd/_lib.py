@@ -47,6 +47,12 @@ class biu_aug_params(C.Structure):
                 ("angle", C.c_float), ("scale", C.c_float), ("dx", C.c_float), ("dy", C.c_float)]
 
 
+class biu_augf_params(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("rot_k", C.c_uint32), ("blur_k", C.c_uint32), ("index", C.c_uint32), ("m", C.c_double * 6),
+                ("cos_t", C.c_float), ("sin_t", C.c_float), ("alpha", C.c_float), ("beta", C.c_float), ("shot_s", C.c_float),
+                ("gauss_sigma", C.c_float), ("angle", C.c_float), ("scale", C.c_float), ("dx", C.c_float), ("dy", C.c_float)]
+
+
 _P = C.c_void_p
 _A = C.POINTER(biu_act)
 _X = C.POINTER(biu_xform)
@@ -158,6 +164,7 @@ SIGNATURES = {
     "biu_stitch_finish": (_I, [_P, _P, _I, _I, C.c_longlong, _P, _I, _P]),
     "biu_to_nchw": (_I, [_A, _X, _P, _I, _P]),
     "biu_augment_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
+    "biu_augment_f32": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "biu_philox_u32": (_I, [_P, C.c_longlong, C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, C.c_uint, _P]),
     "biu_adam_step": (_I, [_I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _F, _P]),
     "biu_adam_set_hyper": (_I, [_P, _F, _F, _F, _F, _I, _F, _P]),

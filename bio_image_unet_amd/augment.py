@@ -28,6 +28,8 @@ not depend on batch composition, thread timing or call order; per-pixel noise is
 counter (element group, dataset index, epoch, field-and-stage id).  Same seed -> same epoch, bit for bit.
 
 This is distribution-level equivalence to the reference pipeline, not bit parity ("On-device augmentation").
+
+The 2-D multi-output family's float fields have a pipeline of their own, ``AugmenterF32`` / ``biu_augment_f32`` in the second half of this file.
 """
 from __future__ import annotations
 
@@ -125,6 +127,9 @@ def record(index: int, h: int, w: int, *, gate: bool = True, rot_k: int = 0, ssr
 
 class Augmenter:
     """Draws per-sample parameter records on the host and runs ``biu_augment_u8`` on device batches; see the module docstring."""
+
+    params_dtype = PARAMS_DTYPE                            # DeviceFeeder sizes its record buffers by it
+    float_output = False
 
     def __init__(self, recipe: str, *, shiftscalerotate=(0, 0, 0), brightness_contrast=(0.25, 0.25), noise_lims=(0.5, 1.2), noise_amp=10,
                  blur_limit=(3, 7), p: float = 0.8, seed: int = 0, kinds: Optional[Dict[str, str]] = None, shape: Optional[Sequence[int]] = None):
@@ -231,5 +236,216 @@ class Augmenter:
             check(lib.biu_augment_u8(C.c_void_p(t.data_ptr()), C.c_void_p(dst.data_ptr()), t.shape[0], planes, t.shape[-2], t.shape[-1],
                                      int(mask), C.c_void_p(params_dev.data_ptr()), self.order, 0 if mask else max_blur, self.seed,
                                      int(epoch) & 0xFFFFFFFF, field_id(name), stream), "augment_u8")
+            res[name] = dst
+        return res
+
+
+# =====================================================================================================================================
+# float fields: the 2-D multi-output family (``biu_augment_f32``)
+# =====================================================================================================================================
+# The reference's pipeline for this family (``multi_output_unet/data.py:187-311``) is none of the three recipes above: either an arbitrary
+# angle (``scipy.ndimage.rotate(mode='grid-wrap')``, image ``order=0``) or a quarter turn, then ``RandomScale`` (nearest) -> ``Blur`` ->
+# ``PadIfNeeded(BORDER_WRAP)`` -> ``RandomCrop`` -> ``ShotNoise`` -> ``GaussNoise`` -> ``RandomBrightnessContrast``, on float32 data, with an
+# ``orientation`` target whose VALUES change under rotation.  Here rotation, scale and crop offset are one 2x3 map with wrap-around indices:
+#
+# =========  ================================================================================================================
+# kind       what the kernel does
+# =========  ================================================================================================================
+# "image"    nearest gather, then blur -> shot noise -> Gauss noise -> brightness/contrast (fp32, clipped to [0, 1])
+# "mask"     any scalar target (mask, probability, distance map): bilinear under an arbitrary angle, nearest otherwise
+# "vector"   plane pairs ``(cos phi, sin phi)``: nearest gather, the pair is rotated by the record's rotation (phi - t)
+# =========  ================================================================================================================
+#
+# The field ``image`` is an image, a field named ``orientation`` a vector, every other field a mask; ``kinds={...}`` overrides.
+ROT_F, SCALE_F, BLUR_F, SHOT_F, GAUSS_F, BC_F = 1, 2, 4, 8, 16, 32          # include/biu.h: BIU_AUGF_*
+KIND_IMAGE, KIND_MASK, KIND_VECTOR = 0, 1, 2
+KINDS_F32 = {"image": KIND_IMAGE, "mask": KIND_MASK, "vector": KIND_VECTOR}
+STAGE_P_MO2D = {"arbitrary_angle": 0.5, "scale": 0.75, "blur": 0.25, "shot_noise": 0.25, "gauss_noise": 0.25, "brightness_contrast": 0.5}
+
+# include/biu.h: biu_augf_params, 104 bytes; dx, dy in pixels
+PARAMS_F32_DTYPE = np.dtype([("flags", "<u4"), ("rot_k", "<u4"), ("blur_k", "<u4"), ("index", "<u4"), ("m", "<f8", (6,)),
+                             ("cos_t", "<f4"), ("sin_t", "<f4"), ("alpha", "<f4"), ("beta", "<f4"), ("shot_s", "<f4"), ("gauss_sigma", "<f4"),
+                             ("angle", "<f4"), ("scale", "<f4"), ("dx", "<f4"), ("dy", "<f4")])
+assert PARAMS_F32_DTYPE.itemsize == 104
+_F1 = struct.Struct("<f")
+_REC_F32 = struct.Struct("<4I6d10f")
+assert _REC_F32.size == PARAMS_F32_DTYPE.itemsize
+_QUARTER = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))                # (cos, sin) of k quarter turns, exact
+
+
+def _f32(v: float) -> float:
+    return _F1.unpack(_F1.pack(v))[0]
+
+
+def _pack_f32(buf, offset, index, h, w, rot_k, angle, scale, shift, blur_k, shot_s, gauss_sigma, bc):
+    """Write one float-path record at ``buf[offset:]``; stages not given leave the identity.  Matrix and ``(cos_t, sin_t)`` are computed from
+    the fp32 values the record keeps.  The rotation the orientation pair sees is ``rot_k`` quarter turns plus ``angle``."""
+    flags = ((ROT_F if angle is not None else 0) | (SCALE_F if scale is not None or shift != (0, 0) else 0) | (BLUR_F if blur_k else 0)
+             | (SHOT_F if shot_s is not None else 0) | (GAUSS_F if gauss_sigma is not None else 0) | (BC_F if bc is not None else 0))
+    a = _f32(angle) if angle is not None else 0.0
+    s = _f32(scale) if scale is not None else 1.0
+    dx, dy = float(int(shift[0])), float(int(shift[1]))
+    qc, qs = _QUARTER[rot_k % 4]
+    if a != 0:
+        t = math.radians(a)
+        ca, sa = math.cos(t), math.sin(t)
+        ct, st = qc * ca - qs * sa, qs * ca + qc * sa               # quarter turns only swap and negate
+    else:
+        ct, st = qc, qs
+    alpha, beta = bc if bc is not None else (1.0, 0.0)
+    _REC_F32.pack_into(buf, offset, flags, rot_k, blur_k, index, *_matrix(rot_k % 4, a, s, dx / w, dy / h, h, w), ct + 0.0, st + 0.0, alpha, beta,
+                       shot_s if shot_s is not None else 0.0, gauss_sigma if gauss_sigma is not None else 0.0, a, s, dx, dy)
+
+
+def record_f32(index: int, h: int, w: int, *, rot_k: int = 0, angle: Optional[float] = None, scale: Optional[float] = None, shift=(0, 0),
+               blur_k: int = 0, shot_s: Optional[float] = None, gauss_sigma: Optional[float] = None, bc=None) -> np.ndarray:
+    """One ``biu_augf_params`` record from its logical description: ``rot_k`` quarter turns, ``angle`` in degrees (given at all, mask fields
+    are gathered bilinearly), ``scale`` about the tile centre, ``shift = (dx, dy)`` in whole pixels, ``bc = (alpha, beta)`` with
+    ``v * alpha + beta`` on the [0, 1] scale.  ``AugmenterF32.draw`` builds its records the same way."""
+    if blur_k and (blur_k % 2 == 0 or not 1 <= blur_k <= MAX_BLUR):
+        raise ValueError(f"blur kernel {blur_k}: odd and at most {MAX_BLUR}")
+    if shot_s is not None and not shot_s > 0:
+        raise ValueError("shot noise needs a positive scale")
+    if scale is not None and not scale > 0:
+        raise ValueError("scale must be positive")
+    buf = bytearray(_REC_F32.size)
+    _pack_f32(buf, 0, int(index), int(h), int(w), int(rot_k), angle, scale, (int(shift[0]), int(shift[1])), int(blur_k), shot_s, gauss_sigma, bc)
+    return np.frombuffer(buf, dtype=PARAMS_F32_DTYPE)[0]
+
+
+def _pair(v, what):
+    v = (v, v) if np.isscalar(v) else tuple(v)
+    if len(v) != 2:
+        raise ValueError(f"{what} takes two limits")
+    return v
+
+
+class AugmenterF32:
+    """Draws ``biu_augf_params`` records on the host and runs ``biu_augment_f32`` on device batches of float32 or uint8 fields (the output is
+    always float32): the 2-D multi-output family's recipe ``"mo2d"``.  Same shape as ``Augmenter``."""
+
+    recipe = "mo2d"
+    params_dtype = PARAMS_F32_DTYPE
+    float_output = True                                    # DeviceFeeder: the augmented buffers are float32 whatever the store holds
+
+    def __init__(self, *, gauss_noise_lims=(0.01, 0.1), shot_noise_lims=(0.001, 0.01), brightness_contrast=(0.1, 0.1), blur_limit=(3, 5),
+                 random_rotate: bool = True, scale_limit=(0, 0), seed: int = 0, kinds: Optional[Dict[str, str]] = None,
+                 shape: Optional[Sequence[int]] = None):
+        self.gauss_noise_lims = tuple(float(v) for v in _pair(gauss_noise_lims, "gauss_noise_lims"))
+        self.shot_noise_lims = tuple(float(v) for v in _pair(shot_noise_lims, "shot_noise_lims"))
+        self.brightness_contrast = tuple(float(v) for v in _pair(brightness_contrast, "brightness_contrast"))
+        self.blur_limit = tuple(int(v) for v in _pair(blur_limit, "blur_limit"))
+        sl = _pair(scale_limit, "scale_limit")
+        self.scale_limit = tuple(float(v) for v in ((-sl[0], sl[0]) if np.isscalar(scale_limit) else sl))
+        self.random_rotate = bool(random_rotate)
+        if self.blur_limit[1] > MAX_BLUR:
+            raise ValueError(f"blur_limit {self.blur_limit}: box kernels above {MAX_BLUR} are not supported")
+        self.blur_sizes = [k for k in range(max(3, self.blur_limit[0]), self.blur_limit[1] + 1) if k % 2]
+        if not self.blur_sizes:
+            raise ValueError(f"blur_limit {self.blur_limit} holds no odd kernel size of 3 or more")
+        if not 0 < self.shot_noise_lims[0] <= self.shot_noise_lims[1]:
+            raise ValueError("shot_noise_lims: positive scales, lower first")
+        if not 0 <= self.gauss_noise_lims[0] <= self.gauss_noise_lims[1]:
+            raise ValueError("gauss_noise_lims: standard deviations, lower first")
+        if not -1 < self.scale_limit[0] <= self.scale_limit[1]:
+            raise ValueError("scale_limit: 1 + limit must stay positive, lower first")
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.kinds = dict(kinds or {})
+        for v in self.kinds.values():
+            if v not in KINDS_F32:
+                raise ValueError(f'kind "{v}": one of {sorted(KINDS_F32)}')
+        self.shape = tuple(shape) if shape is not None else None
+        self._bitgen = np.random.Philox(key=[0, 0])
+        self._gen, self._state, self._lock = np.random.Generator(self._bitgen), self._bitgen.state, threading.Lock()
+
+    @classmethod
+    def from_store(cls, store, recipe: str = "mo2d", **overrides) -> "AugmenterF32":
+        """Limits from the attributes a ``TileStore`` records (those of the ``DataProcess`` it was converted from), else the reference's defaults."""
+        if recipe != "mo2d":
+            raise ValueError(f'recipe "{recipe}" not defined for float fields (only "mo2d")')
+        kw = {}
+        for a in ("gauss_noise_lims", "shot_noise_lims", "brightness_contrast", "blur_limit", "random_rotate", "scale_limit"):
+            v = getattr(store, "attrs", {}).get(a)
+            if v is not None:
+                kw[a] = v
+        kw["shape"] = tuple(store.fields["image"] if "image" in store.fields else next(iter(store.fields.values())))
+        kw.update(overrides)
+        return cls(**kw)
+
+    def describe(self) -> dict:
+        return {"recipe": self.recipe, "seed": self.seed, "gauss_noise_lims": self.gauss_noise_lims, "shot_noise_lims": self.shot_noise_lims,
+                "brightness_contrast": self.brightness_contrast, "blur_limit": self.blur_limit, "random_rotate": self.random_rotate,
+                "scale_limit": self.scale_limit, "stage_p": dict(STAGE_P_MO2D), "kinds": dict(self.kinds)}
+
+    def kind(self, name: str) -> str:
+        return self.kinds.get(name, "image" if name == "image" else "vector" if name == "orientation" else "mask")
+
+    # ---- host: the per-sample records -------------------------------------------------------------------------------------------
+    def draw(self, epoch: int, indices, shape: Optional[Sequence[int]] = None) -> np.ndarray:
+        """Record array for the samples ``indices`` of epoch ``epoch``; ``shape``: the tile shape (its last two axes count).  Sixteen uniforms
+        per sample in a fixed order, whatever the gates say."""
+        shape = tuple(shape) if shape is not None else self.shape
+        if shape is None or len(shape) < 2:
+            raise ValueError("AugmenterF32.draw needs the tile shape (constructor's or this call's `shape`)")
+        h, w = int(shape[-2]), int(shape[-1])
+        idx = np.atleast_1d(np.asarray(indices, dtype=np.int64)).tolist()
+        buf = bytearray(len(idx) * _REC_F32.size)
+        lerp = lambda u, lim: lim[0] + u * (lim[1] - lim[0])
+        P, sizes, bcl = STAGE_P_MO2D, self.blur_sizes, self.brightness_contrast
+        with self._lock:
+            for j, i in enumerate(idx):
+                st = self._state
+                st["state"]["key"][:] = (self.seed, int(epoch) & 0xFFFFFFFFFFFFFFFF)
+                st["state"]["counter"][:] = (0, i & 0xFFFFFFFFFFFFFFFF, 0, 0)
+                st["buffer_pos"], st["has_uint32"] = 4, 0
+                self._bitgen.state = st
+                u = self._gen.random(16).tolist()
+                rot_k, angle, scale, shift = 0, None, None, (0, 0)
+                if self.random_rotate:
+                    if u[0] < P["arbitrary_angle"]:
+                        angle = 360.0 * u[1]
+                    else:                                        # {0, 1, 2, 3} on square tiles; upstream's randint(0, 3) never draws 3
+                        rot_k = int(u[2] * 4) if h == w else 2 * int(u[2] * 2)
+                if u[3] < P["scale"]:
+                    scale = _f32(1.0 + lerp(u[4], self.scale_limit))
+                    # RandomCrop out of the up-scaled tile: a whole-pixel offset around the centred crop; a down-scaled tile is wrap-padded
+                    fw, fh = max(int(round(w * scale)) - w, 0), max(int(round(h * scale)) - h, 0)
+                    shift = (fw // 2 - min(int(u[5] * (fw + 1)), fw), fh // 2 - min(int(u[6] * (fh + 1)), fh))
+                _pack_f32(buf, j * _REC_F32.size, i & 0xFFFFFFFF, h, w, rot_k, angle, scale, shift,
+                          sizes[min(int(u[8] * len(sizes)), len(sizes) - 1)] if u[7] < P["blur"] else 0,
+                          lerp(u[10], self.shot_noise_lims) if u[9] < P["shot_noise"] else None,
+                          lerp(u[12], self.gauss_noise_lims) if u[11] < P["gauss_noise"] else None,
+                          (1.0 + (2.0 * u[14] - 1.0) * bcl[1], (2.0 * u[15] - 1.0) * bcl[0]) if u[13] < P["brightness_contrast"] else None)
+        return np.frombuffer(buf, dtype=PARAMS_F32_DTYPE)
+
+    # ---- device ------------------------------------------------------------------------------------------------------------------
+    def __call__(self, batch: Dict[str, torch.Tensor], params: np.ndarray, epoch: int, out: Optional[Dict[str, torch.Tensor]] = None,
+                 params_dev: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """Augment ``{field: float32 or uint8 device tensor [B, H, W] | [B, C, H, W]}`` with the records ``params`` on the current stream into
+        float32 tensors (``out``'s when given; never the inputs: a gather cannot run in place)."""
+        from ._lib import check, lib
+        params = np.ascontiguousarray(params, dtype=PARAMS_F32_DTYPE)
+        first = next(iter(batch.values()))
+        if len(params) != first.shape[0]:
+            raise ValueError(f"{len(params)} parameter records for a batch of {first.shape[0]}")
+        blurs = params["blur_k"][(params["flags"] & BLUR_F) != 0]
+        max_blur = int(blurs.max()) if len(blurs) else 0
+        if params_dev is None:
+            params_dev = torch.from_numpy(params.view(np.uint8).copy()).to(first.device)
+        stream = C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)
+        res = {}
+        for name, t in batch.items():
+            if t.dtype not in (torch.uint8, torch.float32) or not t.is_cuda or t.dim() not in (3, 4) or not t.is_contiguous():
+                raise ValueError(f'field "{name}": a contiguous float32 or uint8 device tensor [B, H, W] or [B, C, H, W] is expected')
+            dst = out[name] if out is not None else torch.empty(t.shape, dtype=torch.float32, device=t.device)
+            if dst.shape != t.shape or dst.dtype != torch.float32 or dst.device != t.device or not dst.is_contiguous() or dst.data_ptr() == t.data_ptr():
+                raise ValueError(f'field "{name}": the output must be a second contiguous float32 tensor of the same shape and device')
+            planes = t.shape[1] if t.dim() == 4 else 1
+            kind = KINDS_F32[self.kind(name)]
+            if kind == KIND_VECTOR and planes % 2:
+                raise ValueError(f'field "{name}": a vector field holds (cos, sin) plane pairs, got {planes} plane(s)')
+            check(lib.biu_augment_f32(C.c_void_p(t.data_ptr()), int(t.dtype == torch.uint8), C.c_void_p(dst.data_ptr()), t.shape[0], planes,
+                                      t.shape[-2], t.shape[-1], kind, C.c_void_p(params_dev.data_ptr()), max_blur if kind == KIND_IMAGE else 0,
+                                      self.seed, int(epoch) & 0xFFFFFFFF, field_id(name), stream), "augment_f32")
             res[name] = dst
         return res

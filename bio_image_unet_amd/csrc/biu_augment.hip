@@ -18,33 +18,20 @@
 #include <hip/hip_runtime.h>
 
 #include "biu_common.h"
+#include "biu_philox.h"
 
 namespace {
 constexpr int TPB = 256;
-constexpr int GROUP = 16;                       // pixels per lane in the point kernel: one 16-byte store
+constexpr int GROUP = 16;                      // pixels per lane in the point kernel: one 16-byte store
 constexpr int TILE = 64;                        // the tile kernel's output tile is TILE x TILE
 constexpr int RMAX = BIU_AUG_MAX_BLUR / 2;      // 7
 constexpr int IN_MAX = TILE + 2 * RMAX;         // 78 rows / columns of intermediate
 constexpr int IN_PITCH = 80;
 
-struct U4 {
-    uint32_t x, y, z, w;
-};
-
-// Philox4x32-10 (Salmon et al., Random123): ten rounds, the key bumped between rounds
-__host__ __device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c.z;
-        c = U4{(uint32_t)(p1 >> 32) ^ c.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w ^ k1, (uint32_t)p0};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-__device__ __forceinline__ uint32_t word_of(const U4& r, int i) { return i == 0 ? r.x : i == 1 ? r.y : i == 2 ? r.z : r.w; }
-__device__ __forceinline__ float uniform24(uint32_t u) { return (float)(u >> 8) * 5.9604644775390625e-08f; }     // (u >> 8) * 2^-24, exact
+using biu_philox::U4;
+using biu_philox::philox4x32_10;      // biu_philox.h: shared with biu_augment_f32.hip
+using biu_philox::uniform24;
+using biu_philox::word_of;
 
 // reflect without repeating the edge: ... 2 1 | 0 1 2 ... n-1 | n-2 n-3 ...
 __device__ __forceinline__ int reflect101(int i, int n) {

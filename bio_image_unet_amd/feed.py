@@ -17,6 +17,11 @@ flat uint8 file per field, mapped into memory:
 TIFF decoding and tiling stay out of scope (``DataProcess``): they run once, offline, and their output is what this store holds.
 Augmentation does not have to: ``DeviceFeeder(..., augmenter=augment.Augmenter(...))`` augments every training batch on the device, fresh
 every epoch, from a store of un-augmented tiles (``augment.py``).
+
+The 2-D multi-output family's items are float32 (``multi_output_unet/data.py:318-349``): distance and probability maps, and an
+``orientation`` target that reaches the network as ``(cos, sin)`` in [-1, 1].  A store field therefore has a dtype, ``"u8"`` (the default) or
+``"f32"`` (file ``<path>.<field>.f32``, written and read back bit for bit, never scaled); the feeder carries float fields as float32 and
+``augment.AugmenterF32`` augments them.  A mixed store (``image`` as u8, targets as f32) keeps the image's PCIe traffic at a quarter.
 """
 from __future__ import annotations
 
@@ -30,10 +35,27 @@ import numpy as np
 import torch
 
 _MAGIC = "biu-tilestore-1"
+_NP_DTYPE = {"u8": np.uint8, "f32": np.float32}
+_TORCH_DTYPE = {"u8": torch.uint8, "f32": torch.float32}
+
+
+def _field_dtypes(fields, dtypes) -> Dict[str, str]:
+    """``dtypes``: None (all uint8), one name for every field, or ``{field: "u8" | "f32"}`` (fields it does not name are uint8)."""
+    if dtypes is None or isinstance(dtypes, str):
+        dtypes = {k: dtypes or "u8" for k in fields}
+    unknown = [k for k in dtypes if k not in fields]
+    if unknown:
+        raise ValueError(f"dtypes names fields the store does not have: {unknown}")
+    res = {k: dtypes.get(k, "u8") for k in fields}
+    for k, v in res.items():
+        if v not in _NP_DTYPE:
+            raise ValueError(f'field "{k}": dtype "{v}" not defined (one of {sorted(_NP_DTYPE)})')
+    return res
 
 
 class TileStore(torch.utils.data.Dataset):
-    """Flat uint8 files ``<path>.<field>.u8`` + ``<path>.json``; fields are ``[N, *shape]``."""
+    """Flat files ``<path>.<field>.u8`` (uint8) or ``<path>.<field>.f32`` (float32) + ``<path>.json``; fields are ``[N, *shape]``.  The
+    header's ``dtypes`` map is optional: a header without it (every all-uint8 store) names uint8 fields only."""
 
     def __init__(self, path: str, mode: str = "r"):
         with open(path + ".json") as f:
@@ -46,34 +68,50 @@ class TileStore(torch.utils.data.Dataset):
         for k, v in self.attrs.items():                      # aug_factor, clip_threshold, ...: the Trainers record them in checkpoints
             if k != "dim_out" and not hasattr(self, k):
                 setattr(self, k, v)
-        self.maps = {k: np.memmap(f"{path}.{k}.u8", dtype=np.uint8, mode=mode, shape=(self.n,) + shp) for k, shp in self.fields.items()}
+        self.dtypes = _field_dtypes(self.fields, hdr.get("dtypes"))
+        self.maps = {k: np.memmap(f"{path}.{k}.{self.dtypes[k]}", dtype=_NP_DTYPE[self.dtypes[k]], mode=mode, shape=(self.n,) + shp)
+                     for k, shp in self.fields.items()}
 
     # ---- construction ----------------------------------------------------------------------------------------------
     @classmethod
-    def create(cls, path: str, n: int, fields: Dict[str, Sequence[int]], attrs: Optional[dict] = None) -> "TileStore":
+    def create(cls, path: str, n: int, fields: Dict[str, Sequence[int]], attrs: Optional[dict] = None, dtypes=None) -> "TileStore":
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        dtypes = _field_dtypes(fields, dtypes)
         for k, shp in fields.items():
-            np.memmap(f"{path}.{k}.u8", dtype=np.uint8, mode="w+", shape=(n,) + tuple(shp)).flush()
+            np.memmap(f"{path}.{k}.{dtypes[k]}", dtype=_NP_DTYPE[dtypes[k]], mode="w+", shape=(n,) + tuple(shp)).flush()
+        hdr = {"magic": _MAGIC, "n": n, "fields": {k: list(v) for k, v in fields.items()}, "attrs": attrs or {}}
+        if any(v != "u8" for v in dtypes.values()):          # an all-uint8 store keeps the header every earlier reader knows
+            hdr["dtypes"] = dtypes
         with open(path + ".json", "w") as f:
-            json.dump({"magic": _MAGIC, "n": n, "fields": {k: list(v) for k, v in fields.items()}, "attrs": attrs or {}}, f)
+            json.dump(hdr, f)
         return cls(path, mode="r+")
 
     @classmethod
-    def from_dataset(cls, path: str, dataset: Iterable, keys: Optional[Sequence[str]] = None) -> "TileStore":
-        """Convert a data set with the reference's item contract (dict of float32 tensors in [0, 1]) into a store."""
+    def from_dataset(cls, path: str, dataset: Iterable, keys: Optional[Sequence[str]] = None, dtypes=None) -> "TileStore":
+        """Convert a data set with the reference's item contract (dict of float32 tensors) into a store.  uint8 fields (the default) hold
+        values in [0, 1] as multiples of 1/255; ``dtypes`` (``"f32"`` for every field, or ``{field: "u8" | "f32"}``) names the fields that
+        are written as the data set yields them: no clipping, no rounding.  Non-finite values are refused: the store holds what
+        ``DataProcess.__getitem__`` yields, i.e. NaN already replaced by ``nan_to_val``."""
         first = dataset[0]
         keys = list(keys) if keys is not None else [k for k, v in first.items() if torch.is_tensor(v) or isinstance(v, np.ndarray)]
         fields = {k: tuple(np.asarray(first[k]).shape) for k in keys}
         attrs = {}
-        for a in ("dim_out", "aug_factor", "clip_threshold", "noise_lims", "noise_amp", "brightness_contrast", "shiftscalerotate", "blur_limit"):
+        for a in ("dim_out", "aug_factor", "clip_threshold", "noise_lims", "noise_amp", "brightness_contrast", "shiftscalerotate", "blur_limit",
+                  "gauss_noise_lims", "shot_noise_lims", "random_rotate", "scale_limit"):
             if hasattr(dataset, a):
                 v = getattr(dataset, a)
                 attrs[a] = list(v) if isinstance(v, (tuple, list)) else v
-        st = cls.create(path, len(dataset), fields, attrs)
+        st = cls.create(path, len(dataset), fields, attrs, dtypes)
         for i in range(len(dataset)):
             item = dataset[i]
             for k in keys:
-                st.maps[k][i] = np.clip(np.rint(np.asarray(item[k], dtype=np.float64) * 255.0), 0, 255).astype(np.uint8)
+                if st.dtypes[k] == "f32":
+                    v = np.asarray(item[k], dtype=np.float32)
+                    if not np.isfinite(v).all():
+                        raise ValueError(f'field "{k}" of item {i} holds non-finite values: replace NaN (nan_to_val) before the store is written')
+                    st.maps[k][i] = v
+                else:
+                    st.maps[k][i] = np.clip(np.rint(np.asarray(item[k], dtype=np.float64) * 255.0), 0, 255).astype(np.uint8)
         st.flush()
         return st
 
@@ -81,15 +119,17 @@ class TileStore(torch.utils.data.Dataset):
         for m in self.maps.values():
             m.flush()
 
-    # ---- Dataset contract of the reference: float32 in [0, 1] ---------------------------------------------------------
+    # ---- Dataset contract of the reference: float32 (uint8 fields: in [0, 1]; float fields: as written) --------------
     def __len__(self):
         return self.n
 
     def __getitem__(self, i):
-        return {k: torch.from_numpy(np.asarray(m[i], dtype=np.float32) / 255.0) for k, m in self.maps.items()}
+        return {k: torch.from_numpy(np.array(m[i], dtype=np.float32) if self.dtypes[k] == "f32" else np.asarray(m[i], dtype=np.float32) / 255.0)
+                for k, m in self.maps.items()}
 
     def batch_u8(self, indices, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
-        """uint8 batch ``{field: [B, *shape]}`` gathered from the map (into ``out``'s tensors when given, e.g. pinned buffers)."""
+        """Batch ``{field: [B, *shape]}`` in the fields' own dtypes (uint8, or float32 for float fields), gathered from the map (into
+        ``out``'s tensors when given, e.g. pinned buffers).  ``batch_host`` is the same method under a dtype-neutral name."""
         idx = np.asarray(indices, dtype=np.int64)
         res = {}
         for k, m in self.maps.items():
@@ -101,9 +141,11 @@ class TileStore(torch.utils.data.Dataset):
                 res[k] = torch.from_numpy(np.take(m, idx, axis=0))
         return res
 
+    batch_host = batch_u8
+
 
 class DeviceFeeder:
-    """Iterable over uint8 device batches of a ``TileStore`` (one epoch per ``iter()``), ``depth`` batches in flight.
+    """Iterable over device batches of a ``TileStore`` in the fields' own dtypes (one epoch per ``iter()``), ``depth`` batches in flight.
 
     With an ``augmenter`` (``augment.Augmenter``) the feeder thread also draws the per-sample parameter records, uploads them with the batch
     and enqueues the augmentation launches on the copy stream in front of the ``ready`` event, into a second set of device buffers: the work
@@ -121,19 +163,23 @@ class DeviceFeeder:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.drop_last, self.depth = drop_last, max(2, depth)
         self.copy_stream = torch.cuda.Stream(device=self.device)
-        mk = lambda shp, pin: (torch.empty((batch_size,) + shp, dtype=torch.uint8).pin_memory() if pin
-                               else torch.empty((batch_size,) + shp, dtype=torch.uint8, device=self.device))
-        self.slots = [{"host": {k: mk(s, True) for k, s in store.fields.items()}, "dev": {k: mk(s, False) for k, s in store.fields.items()},
+        dtypes = {k: _TORCH_DTYPE[v] for k, v in getattr(store, "dtypes", {k: "u8" for k in store.fields}).items()}
+        mk = lambda k, pin, dt=None: (torch.empty((batch_size,) + store.fields[k], dtype=dt or dtypes[k]).pin_memory() if pin
+                                      else torch.empty((batch_size,) + store.fields[k], dtype=dt or dtypes[k], device=self.device))
+        self.slots = [{"host": {k: mk(k, True) for k in store.fields}, "dev": {k: mk(k, False) for k in store.fields},
                        "ready": None, "free": None, "released": threading.Event()} for _ in range(self.depth)]
         if augment_stream not in ("copy", "main"):
             raise ValueError('augment_stream: "copy" or "main"')
         self.augmenter, self.epoch, self.augment_on_main = augmenter, 0, augment_stream == "main"
         if augmenter is not None:
-            from .augment import PARAMS_DTYPE
+            float_out = bool(getattr(augmenter, "float_output", False))     # augment.AugmenterF32 writes float32 whatever the field holds
+            if not float_out and any(dt != torch.uint8 for dt in dtypes.values()):
+                raise ValueError("a store with float fields needs augment.AugmenterF32 (augment.Augmenter works on uint8 fields)")
+            rec = augmenter.params_dtype.itemsize
             for slot in self.slots:
-                slot["aug"] = {k: mk(s, False) for k, s in store.fields.items()}
-                slot["params_host"] = torch.empty(batch_size * PARAMS_DTYPE.itemsize, dtype=torch.uint8).pin_memory()
-                slot["params_dev"] = torch.empty(batch_size * PARAMS_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+                slot["aug"] = {k: mk(k, False, torch.float32 if float_out else None) for k in store.fields}
+                slot["params_host"] = torch.empty(batch_size * rec, dtype=torch.uint8).pin_memory()
+                slot["params_dev"] = torch.empty(batch_size * rec, dtype=torch.uint8, device=self.device)
 
     def __len__(self):
         n = len(self.indices)

@@ -51,18 +51,20 @@ def _make_criterion(name, params, extra=None):
 
 
 def _resolve_augment(augment, dataset, device, recipe):
-    """``augment`` keyword of the uint8 families' Trainers -> ``augment.Augmenter`` or None.  On-device augmentation works on the uint8 batches of a
-    ``DeviceFeeder``, so anything but a ``TileStore`` on a GPU is refused rather than silently trained un-augmented."""
+    """``augment`` keyword of the Trainers -> ``augment.Augmenter`` (the uint8 families), ``augment.AugmenterF32`` (recipe ``"mo2d"``) or None.
+    On-device augmentation works on the batches of a ``DeviceFeeder``, so anything but a ``TileStore`` on a GPU is refused rather than
+    silently trained un-augmented."""
     if augment is None or augment is False:
         return None
-    from .augment import Augmenter
+    from .augment import Augmenter, AugmenterF32
     from .feed import TileStore
+    cls = AugmenterF32 if recipe == "mo2d" else Augmenter
     if not isinstance(dataset, TileStore) or torch.device(device).type != "cuda":
         raise ValueError("augment: on-device augmentation needs a feed.TileStore data set and a GPU device")
     if augment is True:
-        return Augmenter.from_store(dataset, recipe)
-    if not isinstance(augment, Augmenter):
-        raise ValueError("augment: None, True or an augment.Augmenter")
+        return cls.from_store(dataset, recipe)
+    if not isinstance(augment, cls):
+        raise ValueError(f"augment: None, True or an augment.{cls.__name__}")
     return augment
 
 
@@ -470,7 +472,19 @@ class TrainerMo3d:
                 torch.save(self.state, os.path.join(self.save_dir, f"model_epoch_{epoch + self.epoch_start}.pt"))
 
 
-class TrainerMo2d:
+class _OwnKeywords(type):
+    """``TrainerMo2d.__init__`` keeps the reference's parameter list exactly, names, order and defaults (the drop-in contract that
+    ``tests/test_mo2d_losses_host.py`` pins).  A keyword this package adds is therefore taken where the class is called, keyword-only and
+    behind everything the reference knows, and is in place on the instance when ``__init__`` runs."""
+
+    def __call__(cls, *args, augment=None, **kwargs):
+        self = cls.__new__(cls)
+        self._augment = augment
+        self.__init__(*args, **kwargs)
+        return self
+
+
+class TrainerMo2d(metaclass=_OwnKeywords):
     """``bio_image_unet.multi_output_unet.Trainer`` counterpart (``multi_output_unet/train.py:18-131,144-232,369-407``).
 
     Per head the criterion ``output_heads[name]['loss']`` (one of the ten of ``multi_output_unet.losses``) on the model's already
@@ -494,9 +508,13 @@ class TrainerMo2d:
                  in_channels: int = 1, output_heads: Optional[dict] = None, n_filter: int = 64, deep_supervision: bool = False,
                  dilation=False, val_split: float = 0.2, save_dir: str = "./", save_name: str = "model.pt", save_iter: bool = False,
                  load_weights: bool = False, device: Union[torch.device, str] = "auto"):
+        """``TrainerMo2d(..., augment=None)`` (keyword only, not in the reference, which augments offline; taken by ``_OwnKeywords``): ``True`` or
+        an ``augment.AugmenterF32`` -- the training batches of a ``feed.TileStore`` are augmented on the device, fresh every epoch
+        (``augment.py``, recipe ``"mo2d"``); validation batches never."""
         import random
         from .multi_output_unet.losses import MultiHeadLoss
         self.device = _pick_device(device)
+        self.augmenter = _resolve_augment(getattr(self, "_augment", None), dataset, self.device, "mo2d")
         self.network = network
         self.model = network(n_filter=n_filter, in_channels=in_channels, output_heads=output_heads, dilation=dilation,
                              deep_supervision=deep_supervision).to(self.device)
@@ -512,7 +530,7 @@ class TrainerMo2d:
         n_val = int(len(dataset) * val_split)
         self.dim = getattr(dataset, "dim_out", None)
         train_data, val_data = random_split(dataset, [len(dataset) - n_val, n_val])
-        self.train_loader, self.val_loader = _loaders(dataset, train_data, val_data, batch_size, self.device)
+        self.train_loader, self.val_loader = _loaders(dataset, train_data, val_data, batch_size, self.device, self.augmenter)
         self.optimizer = Adam(self.model.parameters(), lr=lr)
         self.scheduler = optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="min", patience=5, factor=0.2)
         self.save_dir, self.save_name = save_dir, save_name
@@ -521,6 +539,8 @@ class TrainerMo2d:
         self.params = {"optimizer": self.optimizer.state_dict(), "lr": lr, "n_filter": n_filter, "deep_supervision": deep_supervision,
                        "dilation": dilation, "batch_size": batch_size, "augmentation": getattr(dataset, "aug_factor", None),
                        **{k: getattr(dataset, k, None) for k in keys}, "in_channels": in_channels, "output_heads": output_heads}
+        if self.augmenter is not None:      # only when it is on: every other checkpoint keeps its keys
+            self.params["online_augmentation"] = self.augmenter.describe()
         if load_weights:
             self.state = torch.load(os.path.join(save_dir, save_name))
             self.model.load_state_dict(self.state["state_dict"])

@@ -574,7 +574,58 @@ int biu_philox_u32(uint32_t* out, long long blocks, unsigned long long seed, uns
                    biu_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Fused multi-tensor Adam                                                               [K14]
+ * On-the-fly training augmentation of float fields: the 2-D multi-output family (multi_output_unet/data.py:187-311, which the
+ * reference runs offline through scipy.ndimage.rotate and albumentations).  One launch per field per batch.
+ *
+ * src [n, planes, h, w]: float32, or uint8 (src_is_u8 != 0) widened on load as (float)byte / 255.0f (correctly rounded, the value
+ * TileStore.__getitem__ yields).  dst: float32 of the same shape, never src.  One record per sample, drawn on the host:
+ *   m : output pixel (x, y) samples the source at (m0 x + m1 y + m2, m3 x + m4 y + m5); fp64 coordinates and weights as for the uint8
+ *       kernel.  Indices WRAP (scipy's mode='grid-wrap', cv2.BORDER_WRAP): i mod n.  Nearest is floor(c + 0.5).
+ * kind:
+ *   BIU_AUGF_IMAGE  : nearest gather, then BLUR -> SHOT -> GAUSS -> BC, each when its flag is set, in fp32
+ *   BIU_AUGF_MASK   : any scalar target.  Bilinear gather when BIU_AUGF_ROT is set (an arbitrary-angle rotation), nearest otherwise;
+ *                     nothing else
+ *   BIU_AUGF_VECTOR : planes even; plane pairs (c, s) = (cos phi, sin phi).  Both planes are gathered nearest at the same source pixel
+ *                     and the pair is rotated with the record's rotation t: (c cos_t + s sin_t, s cos_t - c sin_t).  The host writes exact
+ *                     0 / +-1 for quarter turns, so those are sign-and-swap, bit for bit.
+ * Stages (IMAGE):
+ *   BIU_AUGF_BLUR  : blur_k x blur_k box mean (odd, <= BIU_AUG_MAX_BLUR) of the GATHERED image: the halo continues the affine map (and
+ *                    wraps in the source); fp32 sums, first k along x, then k along y, times 1 / k^2
+ *   BIU_AUGF_SHOT  : lin = v^2.2, lambda = lin / shot_s, n ~ Poisson(lambda), v = clip(n shot_s, 0, 1)^(1 / 2.2).
+ *                    lambda < 32: inversion with ONE uniform u: p = exp(-lambda), cdf = p, n = 0;
+ *                      while (u >= cdf && n < BIU_AUGF_POISSON_CAP && (n < lambda || p > 2^-32)) { ++n; p *= lambda / n; cdf += p; }
+ *                    otherwise n = max(0, floor(lambda + sqrt(lambda) z + 0.5)), z one Box-Muller normal
+ *   BIU_AUGF_GAUSS : v = clip(v + gauss_sigma z, 0, 1)
+ *   BIU_AUGF_BC    : v = clip(v alpha + beta, 0, 1)
+ * Per-pixel randomness as for the uint8 kernel: Philox4x32-10, key = seed, counter = (element / 2, index, epoch, field_id * 16 + stage)
+ * with stage BIU_AUGF_STAGE_SHOT | BIU_AUGF_STAGE_GAUSS; element % 2 picks words (0, 1) or (2, 3): u1, u2 = (word >> 8) * 2^-24,
+ * z = sqrt(-2 ln(1 - u1)) cos(2 pi u2); the inversion uses u1.
+ * The kernel reads flags, blur_k, index, m, cos_t .. gauss_sigma; rot_k, angle (degrees), scale and dx, dy (whole pixels) document the draw.
+ * max_blur_k: the largest blur_k among the records whose BIU_AUGF_BLUR is set (0: none -- the per-pixel kernel runs, a set bit is ignored).
+ * ---------------------------------------------------------------------------------------------- */
+#define BIU_AUGF_IMAGE 0
+#define BIU_AUGF_MASK 1
+#define BIU_AUGF_VECTOR 2
+#define BIU_AUGF_ROT 1u     /* an arbitrary-angle rotation is part of m: MASK fields are gathered bilinearly */
+#define BIU_AUGF_SCALE 2u   /* informational: scale and crop offset are part of m */
+#define BIU_AUGF_BLUR 4u
+#define BIU_AUGF_SHOT 8u
+#define BIU_AUGF_GAUSS 16u
+#define BIU_AUGF_BC 32u
+#define BIU_AUGF_STAGE_SHOT 3u
+#define BIU_AUGF_STAGE_GAUSS 4u
+#define BIU_AUGF_POISSON_CAP 128
+typedef struct biu_augf_params {
+    uint32_t flags, rot_k, blur_k, index;
+    double m[6];
+    float cos_t, sin_t, alpha, beta, shot_s, gauss_sigma;
+    float angle, scale, dx, dy;
+} biu_augf_params;            /* 104 bytes */
+int biu_augment_f32(const void* src, int src_is_u8, float* dst, int n, int planes, int h, int w, int kind, const biu_augf_params* params,
+                    int max_blur_k, unsigned long long seed, unsigned epoch, unsigned field_id, biu_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fused multi-tensor Adam                                                              [K14]
  * replaces torch.optim.Adam(lr) step: unet/train.py:102,139 (betas 0.9/0.999, eps 1e-8, no decay).
  * One launch updates `n` parameter tensors; ptrs are device arrays of device pointers.
  * ---------------------------------------------------------------------------------------------- */

@@ -29,7 +29,8 @@ counter (element group, dataset index, epoch, field-and-stage id).  Same seed ->
 
 This is distribution-level equivalence to the reference pipeline, not bit parity ("On-device augmentation").
 
-The 2-D multi-output family's float fields have a pipeline of their own, ``AugmenterF32`` / ``biu_augment_f32`` in the second half of this file.
+The 2-D multi-output family's float fields have a pipeline of their own, ``AugmenterF32`` / ``biu_augment_f32`` in the second half of this file;
+the two classes share the record stream and the launch loop (``_AugmenterCore``) and keep their own records, limits and kernels.
 """
 from __future__ import annotations
 
@@ -125,11 +126,95 @@ def record(index: int, h: int, w: int, *, gate: bool = True, rot_k: int = 0, ssr
     return np.frombuffer(buf, dtype=PARAMS_DTYPE)[0]
 
 
-class Augmenter:
+class _AugmenterCore:
+    """What ``Augmenter`` and ``AugmenterF32`` share: the per-sample Philox stream and the record buffer on the host, the checks and the
+    per-field loop around the launch on the device.  A subclass names its record (``params_dtype``, ``_rec``, ``n_uniform``, ``blur_flag``), its
+    kinds, the store attributes its constructor takes and its tensor dtypes, and provides ``_packer`` and ``_launch``."""
+
+    def _init_core(self, seed, kinds, shape):
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.kinds = dict(kinds or {})
+        for v in self.kinds.values():
+            if v not in self.allowed_kinds:
+                raise ValueError(f'kind "{v}": one of {sorted(self.allowed_kinds)}')
+        self.shape = tuple(shape) if shape is not None else None
+        self._bitgen = np.random.Philox(key=[0, 0])              # draw() sets key and counter per sample
+        self._gen, self._state, self._lock = np.random.Generator(self._bitgen), self._bitgen.state, threading.Lock()
+
+    @classmethod
+    def _store_kw(cls, store, overrides):
+        """Constructor keywords from the attributes a ``TileStore`` records (those of the ``DataProcess`` it was converted from)."""
+        attrs = getattr(store, "attrs", {})
+        kw = {a: attrs[a] for a in cls.store_attrs if attrs.get(a) is not None}
+        kw["shape"] = tuple(store.fields["image"] if "image" in store.fields else next(iter(store.fields.values())))
+        kw.update(overrides)
+        return kw
+
+    # ---- host: the per-sample records -------------------------------------------------------------------------------------------
+    def draw(self, epoch: int, indices, shape: Optional[Sequence[int]] = None) -> np.ndarray:
+        """Record array for the samples ``indices`` of epoch ``epoch``; ``shape``: the tile shape (its last two axes count)."""
+        shape = tuple(shape) if shape is not None else self.shape
+        if shape is None or len(shape) < 2:
+            raise ValueError(f"{type(self).__name__}.draw needs the tile shape (constructor's or this call's `shape`)")
+        idx = np.atleast_1d(np.asarray(indices, dtype=np.int64)).tolist()
+        size, n = self._rec.size, self.n_uniform
+        buf = bytearray(len(idx) * size)
+        pack = self._packer(int(shape[-2]), int(shape[-1]))
+        key = (self.seed, int(epoch) & 0xFFFFFFFFFFFFFFFF)
+        with self._lock:
+            for j, i in enumerate(idx):
+                # the generator's stream is a function of its key (seed, epoch) and counter (0, dataset index, 0, 0) alone; a fixed number of
+                # uniforms in a fixed order whatever the gates say: nothing shifts the stream
+                st = self._state
+                st["state"]["key"][:] = key
+                st["state"]["counter"][:] = (0, i & 0xFFFFFFFFFFFFFFFF, 0, 0)
+                st["buffer_pos"], st["has_uint32"] = 4, 0
+                self._bitgen.state = st
+                pack(buf, j * size, i & 0xFFFFFFFF, self._gen.random(n).tolist())
+        return np.frombuffer(buf, dtype=self.params_dtype)
+
+    # ---- device ------------------------------------------------------------------------------------------------------------------
+    def __call__(self, batch: Dict[str, torch.Tensor], params: np.ndarray, epoch: int, out: Optional[Dict[str, torch.Tensor]] = None,
+                 params_dev: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """Augment ``{field: device tensor [B, H, W] | [B, C or D, H, W]}`` with the records ``params`` (``draw``'s result, one per sample) on the
+        current stream; ``out``: tensors to write into (never the inputs: a gather cannot run in place); ``params_dev``: the same records
+        already on the device as bytes (the feeder uploads them with the batch).  ``Augmenter`` takes and writes uint8; ``AugmenterF32``
+        takes float32 or uint8 and always writes float32."""
+        from ._lib import check, lib
+        params = np.ascontiguousarray(params, dtype=self.params_dtype)
+        first = next(iter(batch.values()))
+        if len(params) != first.shape[0]:
+            raise ValueError(f"{len(params)} parameter records for a batch of {first.shape[0]}")
+        blurs = params["blur_k"][(params["flags"] & self.blur_flag) != 0]
+        max_blur = int(blurs.max()) if len(blurs) else 0
+        if params_dev is None:
+            params_dev = torch.from_numpy(params.view(np.uint8).copy()).to(first.device)
+        stream = C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)
+        src, dst_dtype = self.src_dtypes, self.dst_dtype
+        res = {}
+        for name, t in batch.items():
+            if t.dtype not in src or not t.is_cuda or t.dim() not in (3, 4) or not t.is_contiguous():
+                raise ValueError(f'field "{name}": a contiguous {_names(src)} device tensor [B, H, W] or [B, C, H, W] is expected')
+            dst = out[name] if out is not None else torch.empty(t.shape, dtype=dst_dtype, device=t.device)
+            if dst.shape != t.shape or dst.dtype != dst_dtype or dst.device != t.device or not dst.is_contiguous() or dst.data_ptr() == t.data_ptr():
+                raise ValueError(f'field "{name}": the output must be a second contiguous {_names((dst_dtype,))} tensor of the same shape and device')
+            check(self._launch(lib, name, t, dst, t.shape[1] if t.dim() == 4 else 1, params_dev, max_blur, int(epoch) & 0xFFFFFFFF, stream),
+                  self.launch_name)
+            res[name] = dst
+        return res
+
+
+def _names(dtypes) -> str:
+    return " or ".join(str(d).split(".")[-1] for d in dtypes)
+
+
+class Augmenter(_AugmenterCore):
     """Draws per-sample parameter records on the host and runs ``biu_augment_u8`` on device batches; see the module docstring."""
 
-    params_dtype = PARAMS_DTYPE                            # DeviceFeeder sizes its record buffers by it
-    float_output = False
+    params_dtype, _rec, n_uniform, blur_flag = PARAMS_DTYPE, _REC, 13, BLUR        # DeviceFeeder sizes its record buffers by params_dtype
+    allowed_kinds = ("mask", "image")
+    store_attrs = ("shiftscalerotate", "brightness_contrast", "noise_lims", "noise_amp", "blur_limit")
+    src_dtypes, dst_dtype, launch_name = (torch.uint8,), torch.uint8, "augment_u8"
 
     def __init__(self, recipe: str, *, shiftscalerotate=(0, 0, 0), brightness_contrast=(0.25, 0.25), noise_lims=(0.5, 1.2), noise_amp=10,
                  blur_limit=(3, 7), p: float = 0.8, seed: int = 0, kinds: Optional[Dict[str, str]] = None, shape: Optional[Sequence[int]] = None):
@@ -150,26 +235,13 @@ class Augmenter:
             raise ValueError(f"blur_limit {self.blur_limit} holds no odd kernel size")
         if self.noise_amp < 0 or not 0.0 <= p <= 1.0:
             raise ValueError("noise_amp is a variance and p a probability")
-        self.p, self.seed = float(p), int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.kinds = dict(kinds or {})
-        for v in self.kinds.values():
-            if v not in ("mask", "image"):
-                raise ValueError(f'kind "{v}": "mask" or "image"')
-        self.shape = tuple(shape) if shape is not None else None
-        self._bitgen = np.random.Philox(key=[0, 0])              # draw() sets key and counter per sample
-        self._gen, self._state, self._lock = np.random.Generator(self._bitgen), self._bitgen.state, threading.Lock()
+        self.p = float(p)
+        self._init_core(seed, kinds, shape)
 
     @classmethod
     def from_store(cls, store, recipe: str, **overrides) -> "Augmenter":
-        """Limits from the attributes a ``TileStore`` records (those of the ``DataProcess`` it was converted from), else the defaults."""
-        kw = {}
-        for a in ("shiftscalerotate", "brightness_contrast", "noise_lims", "noise_amp", "blur_limit"):
-            v = getattr(store, "attrs", {}).get(a)
-            if v is not None:
-                kw[a] = v
-        kw["shape"] = tuple(next(iter(store.fields.values())))
-        kw.update(overrides)
-        return cls(recipe, **kw)
+        """Limits from the attributes a ``TileStore`` records, else the defaults."""
+        return cls(recipe, **cls._store_kw(store, overrides))
 
     def describe(self) -> dict:
         return {"recipe": self.recipe, "p": self.p, "seed": self.seed, "shiftscalerotate": self.shiftscalerotate,
@@ -179,65 +251,24 @@ class Augmenter:
     def kind(self, name: str) -> str:
         return self.kinds.get(name, "mask" if name == "mask" else "image")
 
-    # ---- host: the per-sample records -------------------------------------------------------------------------------------------
-    def draw(self, epoch: int, indices, shape: Optional[Sequence[int]] = None) -> np.ndarray:
-        """Record array for the samples ``indices`` of epoch ``epoch``; ``shape``: the tile shape (its last two axes count)."""
-        shape = tuple(shape) if shape is not None else self.shape
-        if shape is None or len(shape) < 2:
-            raise ValueError("Augmenter.draw needs the tile shape (constructor's or this call's `shape`)")
-        h, w = int(shape[-2]), int(shape[-1])
-        idx = np.atleast_1d(np.asarray(indices, dtype=np.int64)).tolist()
-        buf = bytearray(len(idx) * _REC.size)
+    def _packer(self, h, w):
+        """``draw``'s record from thirteen uniforms."""
         sym = lambda v, a: (2.0 * v - 1.0) * a
-        lim, bcl, sizes, unet = self.shiftscalerotate, self.brightness_contrast, self.blur_sizes, self.order == ORDER_UNET
+        p, lim, bcl, sizes, unet = self.p, self.shiftscalerotate, self.brightness_contrast, self.blur_sizes, self.order == ORDER_UNET
         noise = (MULT, self.noise_lims[0], self.noise_lims[1] - self.noise_lims[0]) if unet else (GAUSS, math.sqrt(self.noise_amp), 0.0)
-        with self._lock:
-            for j, i in enumerate(idx):
-                # the generator's stream is a function of its key (seed, epoch) and counter (0, dataset index, 0, 0) alone; a fixed number of
-                # uniforms in a fixed order whatever the gates say: nothing shifts the stream
-                st = self._state
-                st["state"]["key"][:] = (self.seed, int(epoch) & 0xFFFFFFFFFFFFFFFF)
-                st["state"]["counter"][:] = (0, i & 0xFFFFFFFFFFFFFFFF, 0, 0)
-                st["buffer_pos"], st["has_uint32"] = 4, 0
-                self._bitgen.state = st
-                u = self._gen.random(13).tolist()
-                _pack(buf, j * _REC.size, i & 0xFFFFFFFF, h, w, u[0] < self.p, int(u[1] * 4) if h == w else 2 * int(u[1] * 2),
-                      (sym(u[3], lim[2]), 1.0 + sym(u[4], lim[1]), sym(u[5], lim[0]), sym(u[6], lim[0])) if u[2] < STAGE_P["shift_scale_rotate"] else None,
-                      (1.0 + sym(u[8], bcl[1]), sym(u[9], bcl[0])) if u[7] < STAGE_P["brightness_contrast"] else None,
-                      sizes[min(int(u[11] * len(sizes)), len(sizes) - 1)] if unet and u[10] < STAGE_P["blur"] else 0,
-                      *(noise if u[12] < STAGE_P["noise"] else (0, 0.0, 0.0)))
-        return np.frombuffer(buf, dtype=PARAMS_DTYPE)
 
-    # ---- device ------------------------------------------------------------------------------------------------------------------
-    def __call__(self, batch: Dict[str, torch.Tensor], params: np.ndarray, epoch: int, out: Optional[Dict[str, torch.Tensor]] = None,
-                 params_dev: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        """Augment ``{field: uint8 device tensor [B, H, W] | [B, C or D, H, W]}`` with the records ``params`` (``draw``'s result, one per
-        sample) on the current stream; ``out``: tensors to write into (never the inputs: a gather cannot run in place); ``params_dev``: the
-        same records already on the device as bytes (the feeder uploads them with the batch)."""
-        from ._lib import check, lib
-        params = np.ascontiguousarray(params, dtype=PARAMS_DTYPE)
-        first = next(iter(batch.values()))
-        if len(params) != first.shape[0]:
-            raise ValueError(f"{len(params)} parameter records for a batch of {first.shape[0]}")
-        blurs = params["blur_k"][(params["flags"] & BLUR) != 0]
-        max_blur = int(blurs.max()) if len(blurs) else 0
-        if params_dev is None:
-            params_dev = torch.from_numpy(params.view(np.uint8).copy()).to(first.device)
-        stream = C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)
-        res = {}
-        for name, t in batch.items():
-            if t.dtype != torch.uint8 or not t.is_cuda or t.dim() not in (3, 4) or not t.is_contiguous():
-                raise ValueError(f'field "{name}": a contiguous uint8 device tensor [B, H, W] or [B, C, H, W] is expected')
-            dst = out[name] if out is not None else torch.empty_like(t)
-            if dst.shape != t.shape or dst.dtype != torch.uint8 or dst.device != t.device or not dst.is_contiguous() or dst.data_ptr() == t.data_ptr():
-                raise ValueError(f'field "{name}": the output must be a second contiguous uint8 tensor of the same shape and device')
-            planes = t.shape[1] if t.dim() == 4 else 1
-            mask = self.kind(name) == "mask"
-            check(lib.biu_augment_u8(C.c_void_p(t.data_ptr()), C.c_void_p(dst.data_ptr()), t.shape[0], planes, t.shape[-2], t.shape[-1],
-                                     int(mask), C.c_void_p(params_dev.data_ptr()), self.order, 0 if mask else max_blur, self.seed,
-                                     int(epoch) & 0xFFFFFFFF, field_id(name), stream), "augment_u8")
-            res[name] = dst
-        return res
+        def pack(buf, offset, index, u):
+            _pack(buf, offset, index, h, w, u[0] < p, int(u[1] * 4) if h == w else 2 * int(u[1] * 2),
+                  (sym(u[3], lim[2]), 1.0 + sym(u[4], lim[1]), sym(u[5], lim[0]), sym(u[6], lim[0])) if u[2] < STAGE_P["shift_scale_rotate"] else None,
+                  (1.0 + sym(u[8], bcl[1]), sym(u[9], bcl[0])) if u[7] < STAGE_P["brightness_contrast"] else None,
+                  sizes[min(int(u[11] * len(sizes)), len(sizes) - 1)] if unet and u[10] < STAGE_P["blur"] else 0,
+                  *(noise if u[12] < STAGE_P["noise"] else (0, 0.0, 0.0)))
+        return pack
+
+    def _launch(self, lib, name, t, dst, planes, params_dev, max_blur, epoch, stream):
+        mask = self.kind(name) == "mask"
+        return lib.biu_augment_u8(C.c_void_p(t.data_ptr()), C.c_void_p(dst.data_ptr()), t.shape[0], planes, t.shape[-2], t.shape[-1], int(mask),
+                                  C.c_void_p(params_dev.data_ptr()), self.order, 0 if mask else max_blur, self.seed, epoch, field_id(name), stream)
 
 
 # =====================================================================================================================================
@@ -320,13 +351,15 @@ def _pair(v, what):
     return v
 
 
-class AugmenterF32:
+class AugmenterF32(_AugmenterCore):
     """Draws ``biu_augf_params`` records on the host and runs ``biu_augment_f32`` on device batches of float32 or uint8 fields (the output is
-    always float32): the 2-D multi-output family's recipe ``"mo2d"``.  Same shape as ``Augmenter``."""
+    always float32, so ``DeviceFeeder``'s augmented buffers are float32 whatever the store holds): the 2-D multi-output family's recipe ``"mo2d"``."""
 
     recipe = "mo2d"
-    params_dtype = PARAMS_F32_DTYPE
-    float_output = True                                    # DeviceFeeder: the augmented buffers are float32 whatever the store holds
+    params_dtype, _rec, n_uniform, blur_flag = PARAMS_F32_DTYPE, _REC_F32, 16, BLUR_F
+    allowed_kinds = tuple(KINDS_F32)
+    store_attrs = ("gauss_noise_lims", "shot_noise_lims", "brightness_contrast", "blur_limit", "random_rotate", "scale_limit")
+    src_dtypes, dst_dtype, launch_name = (torch.float32, torch.uint8), torch.float32, "augment_f32"
 
     def __init__(self, *, gauss_noise_lims=(0.01, 0.1), shot_noise_lims=(0.001, 0.01), brightness_contrast=(0.1, 0.1), blur_limit=(3, 5),
                  random_rotate: bool = True, scale_limit=(0, 0), seed: int = 0, kinds: Optional[Dict[str, str]] = None,
@@ -349,28 +382,14 @@ class AugmenterF32:
             raise ValueError("gauss_noise_lims: standard deviations, lower first")
         if not -1 < self.scale_limit[0] <= self.scale_limit[1]:
             raise ValueError("scale_limit: 1 + limit must stay positive, lower first")
-        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.kinds = dict(kinds or {})
-        for v in self.kinds.values():
-            if v not in KINDS_F32:
-                raise ValueError(f'kind "{v}": one of {sorted(KINDS_F32)}')
-        self.shape = tuple(shape) if shape is not None else None
-        self._bitgen = np.random.Philox(key=[0, 0])
-        self._gen, self._state, self._lock = np.random.Generator(self._bitgen), self._bitgen.state, threading.Lock()
+        self._init_core(seed, kinds, shape)
 
     @classmethod
     def from_store(cls, store, recipe: str = "mo2d", **overrides) -> "AugmenterF32":
-        """Limits from the attributes a ``TileStore`` records (those of the ``DataProcess`` it was converted from), else the reference's defaults."""
+        """Limits from the attributes a ``TileStore`` records, else the reference's defaults."""
         if recipe != "mo2d":
             raise ValueError(f'recipe "{recipe}" not defined for float fields (only "mo2d")')
-        kw = {}
-        for a in ("gauss_noise_lims", "shot_noise_lims", "brightness_contrast", "blur_limit", "random_rotate", "scale_limit"):
-            v = getattr(store, "attrs", {}).get(a)
-            if v is not None:
-                kw[a] = v
-        kw["shape"] = tuple(store.fields["image"] if "image" in store.fields else next(iter(store.fields.values())))
-        kw.update(overrides)
-        return cls(**kw)
+        return cls(**cls._store_kw(store, overrides))
 
     def describe(self) -> dict:
         return {"recipe": self.recipe, "seed": self.seed, "gauss_noise_lims": self.gauss_noise_lims, "shot_noise_lims": self.shot_noise_lims,
@@ -380,72 +399,35 @@ class AugmenterF32:
     def kind(self, name: str) -> str:
         return self.kinds.get(name, "image" if name == "image" else "vector" if name == "orientation" else "mask")
 
-    # ---- host: the per-sample records -------------------------------------------------------------------------------------------
-    def draw(self, epoch: int, indices, shape: Optional[Sequence[int]] = None) -> np.ndarray:
-        """Record array for the samples ``indices`` of epoch ``epoch``; ``shape``: the tile shape (its last two axes count).  Sixteen uniforms
-        per sample in a fixed order, whatever the gates say."""
-        shape = tuple(shape) if shape is not None else self.shape
-        if shape is None or len(shape) < 2:
-            raise ValueError("AugmenterF32.draw needs the tile shape (constructor's or this call's `shape`)")
-        h, w = int(shape[-2]), int(shape[-1])
-        idx = np.atleast_1d(np.asarray(indices, dtype=np.int64)).tolist()
-        buf = bytearray(len(idx) * _REC_F32.size)
+    def _packer(self, h, w):
+        """``draw``'s record from sixteen uniforms."""
         lerp = lambda u, lim: lim[0] + u * (lim[1] - lim[0])
-        P, sizes, bcl = STAGE_P_MO2D, self.blur_sizes, self.brightness_contrast
-        with self._lock:
-            for j, i in enumerate(idx):
-                st = self._state
-                st["state"]["key"][:] = (self.seed, int(epoch) & 0xFFFFFFFFFFFFFFFF)
-                st["state"]["counter"][:] = (0, i & 0xFFFFFFFFFFFFFFFF, 0, 0)
-                st["buffer_pos"], st["has_uint32"] = 4, 0
-                self._bitgen.state = st
-                u = self._gen.random(16).tolist()
-                rot_k, angle, scale, shift = 0, None, None, (0, 0)
-                if self.random_rotate:
-                    if u[0] < P["arbitrary_angle"]:
-                        angle = 360.0 * u[1]
-                    else:                                        # {0, 1, 2, 3} on square tiles; upstream's randint(0, 3) never draws 3
-                        rot_k = int(u[2] * 4) if h == w else 2 * int(u[2] * 2)
-                if u[3] < P["scale"]:
-                    scale = _f32(1.0 + lerp(u[4], self.scale_limit))
-                    # RandomCrop out of the up-scaled tile: a whole-pixel offset around the centred crop; a down-scaled tile is wrap-padded
-                    fw, fh = max(int(round(w * scale)) - w, 0), max(int(round(h * scale)) - h, 0)
-                    shift = (fw // 2 - min(int(u[5] * (fw + 1)), fw), fh // 2 - min(int(u[6] * (fh + 1)), fh))
-                _pack_f32(buf, j * _REC_F32.size, i & 0xFFFFFFFF, h, w, rot_k, angle, scale, shift,
-                          sizes[min(int(u[8] * len(sizes)), len(sizes) - 1)] if u[7] < P["blur"] else 0,
-                          lerp(u[10], self.shot_noise_lims) if u[9] < P["shot_noise"] else None,
-                          lerp(u[12], self.gauss_noise_lims) if u[11] < P["gauss_noise"] else None,
-                          (1.0 + (2.0 * u[14] - 1.0) * bcl[1], (2.0 * u[15] - 1.0) * bcl[0]) if u[13] < P["brightness_contrast"] else None)
-        return np.frombuffer(buf, dtype=PARAMS_F32_DTYPE)
+        P, sizes, bcl, rotate = STAGE_P_MO2D, self.blur_sizes, self.brightness_contrast, self.random_rotate
+        scale_limit, shot_lims, gauss_lims = self.scale_limit, self.shot_noise_lims, self.gauss_noise_lims
 
-    # ---- device ------------------------------------------------------------------------------------------------------------------
-    def __call__(self, batch: Dict[str, torch.Tensor], params: np.ndarray, epoch: int, out: Optional[Dict[str, torch.Tensor]] = None,
-                 params_dev: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        """Augment ``{field: float32 or uint8 device tensor [B, H, W] | [B, C, H, W]}`` with the records ``params`` on the current stream into
-        float32 tensors (``out``'s when given; never the inputs: a gather cannot run in place)."""
-        from ._lib import check, lib
-        params = np.ascontiguousarray(params, dtype=PARAMS_F32_DTYPE)
-        first = next(iter(batch.values()))
-        if len(params) != first.shape[0]:
-            raise ValueError(f"{len(params)} parameter records for a batch of {first.shape[0]}")
-        blurs = params["blur_k"][(params["flags"] & BLUR_F) != 0]
-        max_blur = int(blurs.max()) if len(blurs) else 0
-        if params_dev is None:
-            params_dev = torch.from_numpy(params.view(np.uint8).copy()).to(first.device)
-        stream = C.c_void_p(torch.cuda.current_stream(first.device).cuda_stream)
-        res = {}
-        for name, t in batch.items():
-            if t.dtype not in (torch.uint8, torch.float32) or not t.is_cuda or t.dim() not in (3, 4) or not t.is_contiguous():
-                raise ValueError(f'field "{name}": a contiguous float32 or uint8 device tensor [B, H, W] or [B, C, H, W] is expected')
-            dst = out[name] if out is not None else torch.empty(t.shape, dtype=torch.float32, device=t.device)
-            if dst.shape != t.shape or dst.dtype != torch.float32 or dst.device != t.device or not dst.is_contiguous() or dst.data_ptr() == t.data_ptr():
-                raise ValueError(f'field "{name}": the output must be a second contiguous float32 tensor of the same shape and device')
-            planes = t.shape[1] if t.dim() == 4 else 1
-            kind = KINDS_F32[self.kind(name)]
-            if kind == KIND_VECTOR and planes % 2:
-                raise ValueError(f'field "{name}": a vector field holds (cos, sin) plane pairs, got {planes} plane(s)')
-            check(lib.biu_augment_f32(C.c_void_p(t.data_ptr()), int(t.dtype == torch.uint8), C.c_void_p(dst.data_ptr()), t.shape[0], planes,
-                                      t.shape[-2], t.shape[-1], kind, C.c_void_p(params_dev.data_ptr()), max_blur if kind == KIND_IMAGE else 0,
-                                      self.seed, int(epoch) & 0xFFFFFFFF, field_id(name), stream), "augment_f32")
-            res[name] = dst
-        return res
+        def pack(buf, offset, index, u):
+            rot_k, angle, scale, shift = 0, None, None, (0, 0)
+            if rotate:
+                if u[0] < P["arbitrary_angle"]:
+                    angle = 360.0 * u[1]
+                else:                                        # {0, 1, 2, 3} on square tiles; upstream's randint(0, 3) never draws 3
+                    rot_k = int(u[2] * 4) if h == w else 2 * int(u[2] * 2)
+            if u[3] < P["scale"]:
+                scale = _f32(1.0 + lerp(u[4], scale_limit))
+                # RandomCrop out of the up-scaled tile: a whole-pixel offset around the centred crop; a down-scaled tile is wrap-padded
+                fw, fh = max(int(round(w * scale)) - w, 0), max(int(round(h * scale)) - h, 0)
+                shift = (fw // 2 - min(int(u[5] * (fw + 1)), fw), fh // 2 - min(int(u[6] * (fh + 1)), fh))
+            _pack_f32(buf, offset, index, h, w, rot_k, angle, scale, shift,
+                      sizes[min(int(u[8] * len(sizes)), len(sizes) - 1)] if u[7] < P["blur"] else 0,
+                      lerp(u[10], shot_lims) if u[9] < P["shot_noise"] else None,
+                      lerp(u[12], gauss_lims) if u[11] < P["gauss_noise"] else None,
+                      (1.0 + (2.0 * u[14] - 1.0) * bcl[1], (2.0 * u[15] - 1.0) * bcl[0]) if u[13] < P["brightness_contrast"] else None)
+        return pack
+
+    def _launch(self, lib, name, t, dst, planes, params_dev, max_blur, epoch, stream):
+        kind = KINDS_F32[self.kind(name)]
+        if kind == KIND_VECTOR and planes % 2:
+            raise ValueError(f'field "{name}": a vector field holds (cos, sin) plane pairs, got {planes} plane(s)')
+        return lib.biu_augment_f32(C.c_void_p(t.data_ptr()), int(t.dtype == torch.uint8), C.c_void_p(dst.data_ptr()), t.shape[0], planes,
+                                   t.shape[-2], t.shape[-1], kind, C.c_void_p(params_dev.data_ptr()), max_blur if kind == KIND_IMAGE else 0,
+                                   self.seed, epoch, field_id(name), stream)

@@ -172,12 +172,12 @@ class DeviceFeeder:
             raise ValueError('augment_stream: "copy" or "main"')
         self.augmenter, self.epoch, self.augment_on_main = augmenter, 0, augment_stream == "main"
         if augmenter is not None:
-            float_out = bool(getattr(augmenter, "float_output", False))     # augment.AugmenterF32 writes float32 whatever the field holds
-            if not float_out and any(dt != torch.uint8 for dt in dtypes.values()):
+            out_dtype = augmenter.dst_dtype                                  # augment.AugmenterF32 writes float32 whatever the field holds
+            if out_dtype == torch.uint8 and any(dt != torch.uint8 for dt in dtypes.values()):
                 raise ValueError("a store with float fields needs augment.AugmenterF32 (augment.Augmenter works on uint8 fields)")
             rec = augmenter.params_dtype.itemsize
             for slot in self.slots:
-                slot["aug"] = {k: mk(k, False, torch.float32 if float_out else None) for k in store.fields}
+                slot["aug"] = {k: mk(k, False, out_dtype) for k in store.fields}
                 slot["params_host"] = torch.empty(batch_size * rec, dtype=torch.uint8).pin_memory()
                 slot["params_dev"] = torch.empty(batch_size * rec, dtype=torch.uint8, device=self.device)
 

@@ -14,6 +14,12 @@ numerics-relevant quirks, so a training run is step-for-step comparable:
 What differs by design: the network class comes from this package (every layer a HIP kernel), the optimizer is the fused
 ``biu_adam_step``, and data sets are any ``torch.utils.data.Dataset`` yielding the reference's dict items (TIFF I/O is out of scope; ``Trainer2D`` / ``Trainer3D`` / ``TrainerSiam``
 take ``augment=True`` to augment the training batches of a ``feed.TileStore`` on the device, ``augment.py``).
+
+Layout: all five Trainers sit on ``_EpochLoop`` (construction tail, batch loop, validation loop, epoch driver); a family is its constructor,
+a few class attributes (scheduler, gradient clip, which lines it prints), ``_forward_loss`` (``_total_loss`` on the two multi-output families,
+which share ``_MultiHeadLoop``), ``_checkpoint(epoch, val_loss)`` -- the dictionary it saves -- and ``_report`` where its text differs.  The
+Predicts share checkpoint loading (``_load_params``), percentile normalisation (``_percentile_rescale``) and result writing (``_write``,
+``_write_heads``).
 """
 from __future__ import annotations
 
@@ -108,22 +114,42 @@ class _gc_paused:
         return False
 
 
-class _EpochLoop:
-    """Shared skeleton: split, loaders, Adam + ReduceLROnPlateau, best-validation checkpointing."""
-    item_key = "image"
+def _set_fp32_products(mode, three_d=False):
+    """``fp32_products`` keyword of the Trainers: process-wide, ``None`` leaves the process's mode alone."""
+    if mode is not None:
+        from . import set_fp32_products, set_fp32_products_3d
+        (set_fp32_products_3d if three_d else set_fp32_products)(mode)
 
-    def _setup(self, dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter=None):
+
+class _EpochLoop:
+    """The one loop under the five Trainers: split, loaders, Adam + ReduceLROnPlateau, the training batch loop, the validation loop and the
+    epoch driver with best-validation checkpointing.  A family states what is its own as the class attributes below and provides
+    ``_forward_loss(batch, validating) -> loss``, ``_checkpoint(epoch, val_loss) -> dict`` and, where its text differs, ``_report``."""
+    patience, factor = 4, 0.1           # ReduceLROnPlateau
+    grad_clip = None                    # max norm for clip_grad_norm_ between backward() and step()
+    announces = True                    # "Starting training / validation epoch ..." lines
+    validates_last_batch = False        # Trainer2D: the validation loss is the last batch's, not the mean
+    resumes_epoch = False               # load_weights continues the checkpoint's epoch count (epoch_start)
+    reads_loss = False                  # TrainerMo2d: the criterion keeps the step's loss for one host read per step
+    writer = None                       # TrainerMo2d: tensorboard SummaryWriter, when it imports
+
+    def _setup(self, dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter=None, load_from=None):
         self.data, self.num_epochs, self.batch_size, self.lr = dataset, num_epochs, batch_size, lr
         self.best_loss = torch.tensor(float("inf"))
         self.save_iter, self.save_dir, self.save_name = save_iter, save_dir, save_name
         n_val = int(len(dataset) * val_split)
-        self.dim = dataset.dim_out
         train_data, val_data = random_split(dataset, [len(dataset) - n_val, n_val])
         self.augmenter = augmenter
         self.train_loader, self.val_loader = _loaders(dataset, train_data, val_data, batch_size, self.device, augmenter)
         self.optimizer = Adam(self.model.parameters(), lr=lr)
-        self.scheduler = optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="min", patience=4, factor=0.1)
+        self.scheduler = optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="min", patience=self.patience, factor=self.factor)
         os.makedirs(save_dir, exist_ok=True)
+        self.epoch_start = 0
+        if load_from is not None:
+            self.state = torch.load(load_from)
+            self.model.load_state_dict(self.state["state_dict"])
+            if self.resumes_epoch:
+                self.epoch_start = self.state["epoch"]
 
     def _data_attr(self, *names):
         return {n: getattr(self.data, n, None) for n in names}
@@ -132,31 +158,73 @@ class _EpochLoop:
         """Checkpoint entry of on-device augmentation; nothing when it is off, so those checkpoints keep their keys."""
         return {} if self.augmenter is None else {"online_augmentation": self.augmenter.describe()}
 
-    # subclasses: _forward_loss(batch, validating) -> loss
     def _train_epoch(self, epoch):
-        print("\nStarting training epoch %s ..." % epoch)
+        if self.announces:
+            print("\nStarting training epoch %s ..." % epoch)
+        clip, reads_loss, running = self.grad_clip, self.reads_loss, 0.0
         with _gc_paused():
             for batch in tqdm(self.train_loader, total=len(self.train_loader), unit="batch"):
                 loss = self._forward_loss(batch, validating=False)
                 self.optimizer.zero_grad()
                 loss.backward()
+                if clip is not None:
+                    self.optimizer.clip_grad_norm_(clip)        # multi_output_unet/train.py:186, multi_output_unet3d/train.py:201, as three launches (biu_grad_clip)
                 self.optimizer.step()
+                if reads_loss:
+                    running += self.criterion.item()             # total_loss.item() (multi_output_unet/train.py:189): the step's one host read
+        if self.writer is not None:
+            self.writer.add_scalar("Loss/train", running / max(len(self.train_loader), 1), epoch + self.epoch_start)
+
+    def _validate(self, epoch):
+        if self.announces:
+            print("\nStarting validation epoch %s ..." % epoch)
+        losses = []
+        with torch.no_grad():
+            for batch in tqdm(self.val_loader, total=len(self.val_loader), unit="batch"):
+                losses.append(self._forward_loss(batch, validating=True).detach())
+                if self.reads_loss:
+                    self.criterion.check_range()
+        if self.validates_last_batch:           # reference: appended once, after the loop -> last batch only
+            losses = losses[-1:]
+        val_loss = torch.stack(losses).mean()
+        if self.writer is not None:
+            self.writer.add_scalar("Loss/val", val_loss.item(), epoch + self.epoch_start)
+        return val_loss
+
+    def iterate(self, epoch, mode):
+        return self._train_epoch(epoch) if mode == "train" else self._validate(epoch)
+
+    def _report(self, epoch, improved, best, val, seconds):
+        if improved:
+            print("\nValidation loss improved from %s to %s - saving model state" % (round(best, 5), round(val, 5)))
 
     def _save(self, name):
-        torch.save(self.state, self.save_dir + "/" + name)
+        torch.save(self.state, os.path.join(self.save_dir, name))
 
-    def _after_validation(self, epoch, val_loss):
-        if val_loss < self.best_loss:
-            print("\nValidation loss improved from %s to %s - saving model state"
-                  % (round(self.best_loss.item(), 5), round(val_loss.item(), 5)))
-            self.state["best_loss"] = self.best_loss = val_loss
-            self._save(self.save_name)
-        if self.save_iter:
-            self._save(f"model_epoch_{epoch}.pt")
+    def start(self, test_data_path=None, result_path=None, test_resize_dim=(512, 512)):
+        import time
+        for epoch in range(self.num_epochs):
+            t0 = time.time()
+            self._train_epoch(epoch)
+            with torch.no_grad():
+                val_loss = self._validate(epoch)
+                self.state = self._checkpoint(epoch, val_loss)
+                self.scheduler.step(val_loss)
+            improved = bool(val_loss < self.best_loss)
+            self._report(epoch, improved, self.best_loss.item(), val_loss.item(), time.time() - t0)
+            if improved:
+                self.state["best_loss"] = self.best_loss = val_loss
+                self._save(self.save_name)
+            if self.save_iter:
+                self._save(f"model_epoch_{epoch + self.epoch_start}.pt")
+            if test_data_path is not None:
+                raise NotImplementedError("per-epoch prediction of TIFF test folders is outside the hot path; call "
+                                          "Predict on arrays instead")
 
 
 class Trainer2D(_EpochLoop):
     """``bio_image_unet.unet.Trainer`` counterpart (``unet/train.py:16-198``)."""
+    validates_last_batch = True
 
     def __init__(self, dataset, num_epochs, network=Unet, batch_size=4, lr=1e-3, in_channels=1, out_channels=1,
                  channel_weights=None, n_filter=64, dilation=1, val_split=0.2, save_dir="./", save_name="model.pt",
@@ -168,26 +236,22 @@ class Trainer2D(_EpochLoop):
         ``augment`` (not in the reference): ``True`` or an ``augment.Augmenter`` -- the training batches of a ``feed.TileStore`` are augmented on
         the device, fresh every epoch (recipe ``"unet"``); validation batches never are."""
         augmenter = _resolve_augment(augment, dataset, _pick_device(device), "unet")
-        if fp32_products is not None:
-            from . import set_fp32_products
-            set_fp32_products(fp32_products)
+        _set_fp32_products(fp32_products)
         self.device = _pick_device(device)
         self.network = network
         self.model = network(n_filter=n_filter, in_channels=in_channels, out_channels=out_channels, dilation=dilation).to(self.device)
         self.model.apply(init_weights)
-        self.loss_function, self.loss_params = loss_function, loss_params
+        self.loss_function, self.loss_params, self.dim = loss_function, loss_params, dataset.dim_out
         self.n_filter, self.in_channels, self.out_channels = n_filter, in_channels, out_channels
         self.channel_weights = torch.ones(out_channels) if channel_weights is None else torch.tensor(channel_weights)
         self.criterion = _make_criterion(loss_function, loss_params)
-        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter)
+        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter,
+                    os.path.join(save_dir, save_name) if load_weights else None)
         self.params = {"optimizer": self.optimizer.state_dict(), "lr": lr, "loss_function": loss_function,
                        "loss_params": loss_params, "n_filter": n_filter, "dilation": dilation, "batch_size": batch_size,
                        "augmentation": getattr(dataset, "aug_factor", None), "in_channels": in_channels,
                        "out_channels": out_channels,
                        **self._data_attr("clip_threshold", "noise_lims", "brightness_contrast", "shiftscalerotate"), **self._augment_entry()}
-        if load_weights:
-            self.state = torch.load(save_dir + "/" + save_name)
-            self.model.load_state_dict(self.state["state_dict"])
 
     def _forward_loss(self, batch, validating):
         d = self.dim
@@ -199,28 +263,8 @@ class Trainer2D(_EpochLoop):
         # NOTE the reference indexes the BATCH axis with the channel index
         return sum(self.criterion(logits[ch], y[ch]) * cw[j] for j, ch in enumerate(range(self.out_channels))) / sum(cw)
 
-    def _validate(self, epoch):
-        print("\nStarting validation epoch %s ..." % epoch)
-        losses = []
-        loss = None
-        with torch.no_grad():
-            for batch in tqdm(self.val_loader, total=len(self.val_loader), unit="batch"):
-                loss = self._forward_loss(batch, validating=True)
-        losses.append(loss.detach())            # reference: appended once, after the loop -> last batch only
-        return torch.stack(losses).mean()
-
-    def start(self, test_data_path=None, result_path=None, test_resize_dim=(512, 512)):
-        for epoch in range(self.num_epochs):
-            self._train_epoch(epoch)
-            self.state = {"epoch": epoch, "best_loss": self.best_loss, "state_dict": self.model.state_dict()}
-            self.state.update(self.params)
-            with torch.no_grad():
-                val_loss = self._validate(epoch)
-                self.scheduler.step(val_loss)
-            self._after_validation(epoch, val_loss)
-            if test_data_path is not None:
-                raise NotImplementedError("per-epoch prediction of TIFF test folders is outside the hot path; call "
-                                          "Predict on arrays instead")
+    def _checkpoint(self, epoch, val_loss):
+        return {"epoch": epoch, "best_loss": self.best_loss, "state_dict": self.model.state_dict(), **self.params}
 
 
 class Trainer3D(_EpochLoop):
@@ -235,9 +279,7 @@ class Trainer3D(_EpochLoop):
         multiply (``bio_image_unet_amd.set_fp32_products_3d``; process-wide, default ``"exact"``); ``None`` leaves the process mode alone.
         ``augment``: as for ``Trainer2D``, recipe ``"unet3d"`` (every z-plane of a volume gets the same in-plane transform)."""
         augmenter = _resolve_augment(augment, dataset, _pick_device(device), "unet3d")
-        if fp32_products is not None:
-            from . import set_fp32_products_3d
-            set_fp32_products_3d(fp32_products)
+        _set_fp32_products(fp32_products, three_d=True)
         self.device = _pick_device(device)
         self.network = network
         self.model = network(n_filter=n_filter, in_channels=in_channels, out_channels=out_channels,
@@ -245,20 +287,18 @@ class Trainer3D(_EpochLoop):
         self.model.apply(init_weights)          # a no-op on Conv3d layers, as in the reference
         self.loss_function, self.loss_params, self.time_loss_weight = loss_function, loss_params, time_loss_weight
         self.n_filter, self.in_channels, self.out_channels = n_filter, in_channels, out_channels
-        self.use_interpolation = use_interpolation
+        self.use_interpolation, self.dim = use_interpolation, dataset.dim_out
         self.channel_weights = torch.ones(out_channels) if channel_weights is None else torch.tensor(channel_weights)
         self.criterion = _make_criterion(loss_function, loss_params)
         self.criterion_time = nn.SmoothL1Loss()
-        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter)
+        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter,
+                    os.path.join(save_dir, save_name) if load_weights else None)
         self.params = {"optimizer": self.optimizer.state_dict(), "lr": lr, "loss_function": loss_function,
                        "loss_params": loss_params, "time_loss_weight": time_loss_weight, "n_filter": n_filter,
                        "use_interpolation": use_interpolation, "dilation": dilation, "batch_size": batch_size,
                        "augmentation": getattr(dataset, "aug_factor", None), "in_channels": in_channels,
                        "out_channels": out_channels,
                        **self._data_attr("clip_threshold", "noise_amp", "brightness_contrast", "shiftscalerotate"), **self._augment_entry()}
-        if load_weights:
-            self.state = torch.load(save_dir + "/" + save_name)
-            self.model.load_state_dict(self.state["state_dict"])
 
     def _forward_loss(self, batch, validating):
         d = self.dim
@@ -269,26 +309,8 @@ class Trainer3D(_EpochLoop):
         # criterion(y_logits, y_i) + SmoothL1(y_logits[1:], y_logits[:-1]) * w (unet3d/train.py:140-145), one fused pass each way
         return self.criterion(logits, y, time_weight=w)
 
-    def _validate(self, epoch):
-        print("\nStarting validation epoch %s ..." % epoch)
-        losses = []
-        with torch.no_grad():
-            for batch in tqdm(self.val_loader, total=len(self.val_loader), unit="batch"):
-                losses.append(self._forward_loss(batch, validating=True).detach())
-        return torch.stack(losses).mean()
-
-    def start(self, test_data_path=None, result_path=None, test_resize_dim=(512, 512)):
-        for epoch in range(self.num_epochs):
-            self._train_epoch(epoch)
-            with torch.no_grad():
-                val_loss = self._validate(epoch)
-                self.state = {"val_loss": val_loss, "epoch": epoch, "best_loss": self.best_loss,
-                              "state_dict": self.model.state_dict()}
-                self.state.update(self.params)
-                self.scheduler.step(val_loss)
-            self._after_validation(epoch, val_loss)
-            if test_data_path is not None:
-                raise NotImplementedError("per-epoch prediction of TIFF test folders is outside the hot path")
+    def _checkpoint(self, epoch, val_loss):
+        return {"val_loss": val_loss, "epoch": epoch, "best_loss": self.best_loss, "state_dict": self.model.state_dict(), **self.params}
 
 
 class TrainerSiam(_EpochLoop):
@@ -298,19 +320,14 @@ class TrainerSiam(_EpochLoop):
                  save_dir="./", save_name="model.pt", save_iter=False, loss_function="BCEDice", loss_params=(1, 1),
                  load_weights=None, device: Union[torch.device, str] = "auto", fp32_products: Optional[str] = None, augment=None):
         augmenter = _resolve_augment(augment, dataset, _pick_device(device), "siam")      # see Trainer2D
-        if fp32_products is not None:                 # see Trainer2D
-            from . import set_fp32_products
-            set_fp32_products(fp32_products)
+        _set_fp32_products(fp32_products)                                                 # see Trainer2D
         self.device = _pick_device(device)
         self.model = Siam_UNet(n_filter=n_filter, mode=mode).to(self.device)      # no init_weights here (reference :61)
-        self.n_filter, self.mode = n_filter, mode
+        self.n_filter, self.mode, self.dim = n_filter, mode, dataset.dim_out
         self.loss_function, self.loss_params = loss_function, loss_params
         # the Siam package's own criteria: its BCEDice takes nn.BCELoss on sigmoid(logits) (siam_unet/losses.py:5-39,73-105)
         self.criterion = _make_criterion(loss_function, loss_params, extra={"BCEDice": BCEDiceLossSiam, "weightedBCELoss": weightedBCELoss})
-        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter)
-        if load_weights is not None:
-            self.state = torch.load(load_weights)
-            self.model.load_state_dict(self.state["state_dict"])
+        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter, load_weights)
 
     def _forward_loss(self, batch, validating):
         d = self.dim
@@ -321,42 +338,44 @@ class TrainerSiam(_EpochLoop):
         _, logits = self.model(x, px)
         return self.criterion(logits, y)
 
-    def iterate(self, epoch, mode):
-        if mode == "train":
-            self._train_epoch(epoch)
-            return None
-        print("\nStarting validation epoch %s ..." % epoch)
-        losses = []
-        with torch.no_grad():
-            for batch in tqdm(self.val_loader, total=len(self.val_loader), unit="batch"):
-                losses.append(self._forward_loss(batch, validating=True).detach())
-        return torch.stack(losses).mean()
+    def _checkpoint(self, epoch, val_loss):
+        """The only family whose ``optimizer`` entry is taken every epoch."""
+        return {"epoch": epoch, "best_loss": self.best_loss, "state_dict": self.model.state_dict(),
+                "optimizer": self.optimizer.state_dict(), "lr": self.lr, "loss": self.loss_function,
+                "loss_params": self.loss_params, "n_filter": self.n_filter, "mode": self.mode,
+                "augmentation": getattr(self.data, "aug_factor", None),
+                **self._data_attr("clip_threshold", "noise_amp", "brightness_contrast", "shiftscalerotate"), **self._augment_entry()}
 
-    def start(self, test_data_path=None, result_path=None, test_resize_dim=(512, 512)):
-        for epoch in range(self.num_epochs):
-            self.iterate(epoch, "train")
-            self.state = {"epoch": epoch, "best_loss": self.best_loss, "state_dict": self.model.state_dict(),
-                          "optimizer": self.optimizer.state_dict(), "lr": self.lr, "loss": self.loss_function,
-                          "loss_params": self.loss_params, "n_filter": self.n_filter, "mode": self.mode,
-                          "augmentation": getattr(self.data, "aug_factor", None),
-                          **self._data_attr("clip_threshold", "noise_amp", "brightness_contrast", "shiftscalerotate"), **self._augment_entry()}
-            with torch.no_grad():
-                val_loss = self.iterate(epoch, "val")
-                self.scheduler.step(val_loss)
-            if val_loss < self.best_loss:
-                print(f"\nEpoch {epoch}: Validation loss improved from {round(self.best_loss.item(), 5)} to "
-                      f"{round(val_loss.item(), 5)} - saving model state")
-                self.state["best_loss"] = self.best_loss = val_loss
-                self._save(self.save_name)
-            else:
-                print(f"\nEpoch {epoch}: Validation loss did not improve from {round(self.best_loss.item(), 5)}")
-            if self.save_iter:
-                self._save(f"model_epoch_{epoch}.pt")
-            if test_data_path is not None:
-                raise NotImplementedError("per-epoch prediction of TIFF test folders is outside the hot path")
+    def _report(self, epoch, improved, best, val, seconds):
+        if improved:
+            print(f"\nEpoch {epoch}: Validation loss improved from {round(best, 5)} to {round(val, 5)} - saving model state")
+        else:
+            print(f"\nEpoch {epoch}: Validation loss did not improve from {round(best, 5)}")
 
 
-class TrainerMo3d:
+class _MultiHeadLoop(_EpochLoop):
+    """What the two multi-output families share: per-head criteria, activations and weights out of ``output_heads``, ``clip_grad_norm_(1.0)``
+    before the step, ``ReduceLROnPlateau(patience=5, factor=0.2)``, no "Starting ..." lines, and a checkpoint that counts epochs on from the
+    one ``load_weights`` read."""
+    patience, factor, grad_clip, announces, resumes_epoch = 5, 0.2, 1.0, False, True
+
+    def _set_heads(self, output_heads):
+        self.output_heads = output_heads
+        self.loss_functions = {name: self._get_loss_function(cfg["loss"]) for name, cfg in output_heads.items()}
+        self.activations = {name: cfg.get("activation", None) for name, cfg in output_heads.items()}
+        self.loss_weights = {name: cfg.get("weight", 1.0) for name, cfg in output_heads.items()}
+
+    @staticmethod
+    def _apply_activation(x, activation):
+        fn = {"sigmoid": torch.sigmoid, "tanh": torch.tanh, "relu": torch.relu, "softmax": lambda t: torch.softmax(t, dim=1)}
+        return fn[activation](x) if activation in fn else x
+
+    def _checkpoint(self, epoch, val_loss):
+        return {"epoch": epoch + self.epoch_start, "epoch_start": self.epoch_start, "best_loss": self.best_loss,
+                "state_dict": self.model.state_dict(), **self.params}
+
+
+class TrainerMo3d(_MultiHeadLoop):
     """``bio_image_unet.multi_output_unet3d.Trainer`` counterpart (``multi_output_unet3d/train.py:17-292``).
 
     Per-head loss ``output_heads[name]['loss']`` applied to the model's (already activated) output, summed with the heads'
@@ -367,47 +386,29 @@ class TrainerMo3d:
                  lr=1e-3, in_channels=1, n_filter=64, dilation=1, val_split=0.2, save_dir="./", save_name="model.pt",
                  save_iter=False, load_weights=False, loss_function="BCEDice", loss_params=(0.5, 0.5), time_loss_weight=0.1,
                  device: Union[torch.device, str] = "auto", fp32_products: Optional[str] = None):
-        if fp32_products is not None:                 # see Trainer3D
-            from . import set_fp32_products_3d
-            set_fp32_products_3d(fp32_products)
+        _set_fp32_products(fp32_products, three_d=True)             # see Trainer3D
         self.device = _pick_device(device)
         self.network = network
         self.model = network(n_filter=n_filter, in_channels=in_channels, output_heads=output_heads,
                              use_interpolation=use_interpolation).to(self.device)
         self.model.apply(init_weights)          # a no-op on Conv3d layers, as in the reference
-        self.data, self.output_heads, self.num_epochs, self.batch_size, self.lr = dataset, output_heads, num_epochs, batch_size, lr
-        self.best_loss = torch.tensor(float("inf"))
-        self.save_iter, self.save_dir, self.save_name = save_iter, save_dir, save_name
         self.loss_function, self.loss_params, self.time_loss_weight = loss_function, loss_params, time_loss_weight
-        self.n_filter, self.in_channels, self.use_interpolation = n_filter, in_channels, use_interpolation
-        self.loss_functions = {name: self._get_loss_function(cfg["loss"]) for name, cfg in output_heads.items()}
-        self.activations = {name: cfg.get("activation", None) for name, cfg in output_heads.items()}
-        self.loss_weights = {name: cfg.get("weight", 1.0) for name, cfg in output_heads.items()}
-        n_val = int(len(dataset) * val_split)
-        self.dim = dataset.dim_out
-        train_data, val_data = random_split(dataset, [len(dataset) - n_val, n_val])
-        self.train_loader, self.val_loader = _loaders(dataset, train_data, val_data, batch_size, self.device)
+        self.n_filter, self.in_channels, self.use_interpolation, self.dim = n_filter, in_channels, use_interpolation, dataset.dim_out
+        self._set_heads(output_heads)
         if loss_function == "BCEDiceTemporalLoss":
             self.criterion = BCEDiceTemporalLoss(loss_params=loss_params)
         else:
             self.criterion = _make_criterion(loss_function, loss_params)       # built but unused by the loop, as upstream
         self.criterion_time = nn.SmoothL1Loss()
-        self.optimizer = Adam(self.model.parameters(), lr=lr)
-        self.scheduler = optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="min", patience=5, factor=0.2)
-        os.makedirs(save_dir, exist_ok=True)
-        keys = ("clip_threshold", "scale_limit", "rotate_limit", "gauss_noise_lims", "shot_noise_lims", "blur_limit",
-                "random_rotate", "brightness_contrast")
+        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter,
+                    load_from=os.path.join(save_dir, save_name) if load_weights else None)
         self.params = {"optimizer": self.optimizer.state_dict(), "lr": lr, "loss_function": loss_function,
                        "loss_params": loss_params, "time_loss_weight": time_loss_weight, "n_filter": n_filter,
                        "use_interpolation": use_interpolation, "dilation": dilation, "batch_size": batch_size,
                        "augmentation": getattr(dataset, "aug_factor", None),
-                       **{k: getattr(dataset, k, None) for k in keys}, "in_channels": in_channels, "output_heads": output_heads}
-        if load_weights:
-            self.state = torch.load(os.path.join(save_dir, save_name))
-            self.model.load_state_dict(self.state["state_dict"])
-            self.epoch_start = self.state["epoch"]
-        else:
-            self.epoch_start = 0
+                       **self._data_attr("clip_threshold", "scale_limit", "rotate_limit", "gauss_noise_lims", "shot_noise_lims", "blur_limit",
+                                         "random_rotate", "brightness_contrast"),
+                       "in_channels": in_channels, "output_heads": output_heads}
 
     @staticmethod
     def _get_loss_function(loss_name):
@@ -416,11 +417,6 @@ class TrainerMo3d:
         if loss_name not in table:
             raise ValueError(f'Loss "{loss_name}" not defined!')
         return table[loss_name]()
-
-    @staticmethod
-    def _apply_activation(x, activation):
-        fn = {"sigmoid": torch.sigmoid, "tanh": torch.tanh, "relu": torch.relu, "softmax": lambda t: torch.softmax(t, dim=1)}
-        return fn[activation](x) if activation in fn else x
 
     def _total_loss(self, batch, validating):
         x = batch["volume"].to(self.device, non_blocking=True)
@@ -437,39 +433,13 @@ class TrainerMo3d:
             total = total + self.loss_weights[name] * self.loss_functions[name](p, target)
         return total
 
-    def iterate(self, epoch, mode):
-        if mode == "train":
-            with _gc_paused():
-                for batch in tqdm(self.train_loader, total=len(self.train_loader), unit="batch"):
-                    loss = self._total_loss(batch, validating=False)
-                    self.optimizer.zero_grad()
-                    loss.backward()
-                    self.optimizer.clip_grad_norm_(1.0)          # multi_output_unet3d/train.py:201, as three launches (biu_grad_clip)
-                    self.optimizer.step()
-            return None
-        losses = []
-        with torch.no_grad():
-            for batch in tqdm(self.val_loader, total=len(self.val_loader), unit="batch"):
-                losses.append(self._total_loss(batch, validating=True).detach())
-        return torch.stack(losses).mean()
+    _forward_loss = _total_loss
 
-    def start(self):
-        for epoch in range(self.num_epochs):
-            self.iterate(epoch, "train")
-            self.state = {"epoch": epoch + self.epoch_start, "epoch_start": self.epoch_start, "best_loss": self.best_loss,
-                          "state_dict": self.model.state_dict()}
-            self.state.update(self.params)
-            with torch.no_grad():
-                val_loss = self.iterate(epoch, "val")
-                self.scheduler.step(val_loss)
-            if val_loss < self.best_loss:
-                print(f"\nValidation loss improved from {self.best_loss.item():.5f} to {val_loss.item():.5f} - saving model state")
-                self.state["best_loss"] = self.best_loss = val_loss
-                torch.save(self.state, os.path.join(self.save_dir, self.save_name))
-            else:
-                print(f"\nValidation loss did not improve from {self.best_loss.item():.5f}")
-            if self.save_iter:
-                torch.save(self.state, os.path.join(self.save_dir, f"model_epoch_{epoch + self.epoch_start}.pt"))
+    def _report(self, epoch, improved, best, val, seconds):
+        if improved:
+            print(f"\nValidation loss improved from {best:.5f} to {val:.5f} - saving model state")
+        else:
+            print(f"\nValidation loss did not improve from {best:.5f}")
 
 
 class _OwnKeywords(type):
@@ -484,7 +454,7 @@ class _OwnKeywords(type):
         return self
 
 
-class TrainerMo2d(metaclass=_OwnKeywords):
+class TrainerMo2d(_MultiHeadLoop, metaclass=_OwnKeywords):
     """``bio_image_unet.multi_output_unet.Trainer`` counterpart (``multi_output_unet/train.py:18-131,144-232,369-407``).
 
     Per head the criterion ``output_heads[name]['loss']`` (one of the ten of ``multi_output_unet.losses``) on the model's already
@@ -503,6 +473,7 @@ class TrainerMo2d(metaclass=_OwnKeywords):
 
     ``SummaryWriter`` scalars (``Loss/train``, ``Loss/val``) are written only when ``tensorboard`` imports.  The PNG / TensorBoard image
     logging of the reference (``plot_images``, ``log_validation_images``) is outside the hot path and is not ported."""
+    reads_loss = True
 
     def __init__(self, dataset, num_epochs: int, network=MultiOutputNestedUNet, levels: int = 4, batch_size: int = 4, lr: float = 1e-4,
                  in_channels: int = 1, output_heads: Optional[dict] = None, n_filter: int = 64, deep_supervision: bool = False,
@@ -514,39 +485,22 @@ class TrainerMo2d(metaclass=_OwnKeywords):
         import random
         from .multi_output_unet.losses import MultiHeadLoss
         self.device = _pick_device(device)
-        self.augmenter = _resolve_augment(getattr(self, "_augment", None), dataset, self.device, "mo2d")
+        augmenter = _resolve_augment(getattr(self, "_augment", None), dataset, self.device, "mo2d")
         self.network = network
         self.model = network(n_filter=n_filter, in_channels=in_channels, output_heads=output_heads, dilation=dilation,
                              deep_supervision=deep_supervision).to(self.device)
         self.model.apply(init_weights)
-        self.data, self.num_epochs, self.batch_size, self.levels, self.lr = dataset, num_epochs, batch_size, levels, lr
-        self.best_loss = torch.tensor(float("inf"))
-        self.save_iter, self.n_filter, self.dilation, self.in_channels, self.output_heads = save_iter, n_filter, dilation, in_channels, output_heads
-        self.loss_functions = {name: self._get_loss_function(cfg["loss"]) for name, cfg in output_heads.items()}
-        self.activations = {name: cfg.get("activation", None) for name, cfg in output_heads.items()}
-        self.loss_weights = {name: cfg.get("weight", 1.0) for name, cfg in output_heads.items()}
+        self.levels, self.n_filter, self.dilation, self.in_channels = levels, n_filter, dilation, in_channels
+        self.dim = getattr(dataset, "dim_out", None)
+        self._set_heads(output_heads)
         self.criterion = MultiHeadLoss(output_heads, deep_supervision=bool(getattr(self.model, "deep_supervision", False)), levels=levels,
                                        loss_functions=self.loss_functions)
-        n_val = int(len(dataset) * val_split)
-        self.dim = getattr(dataset, "dim_out", None)
-        train_data, val_data = random_split(dataset, [len(dataset) - n_val, n_val])
-        self.train_loader, self.val_loader = _loaders(dataset, train_data, val_data, batch_size, self.device, self.augmenter)
-        self.optimizer = Adam(self.model.parameters(), lr=lr)
-        self.scheduler = optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="min", patience=5, factor=0.2)
-        self.save_dir, self.save_name = save_dir, save_name
-        os.makedirs(save_dir, exist_ok=True)
-        keys = ("clip_threshold", "gauss_noise_lims", "shot_noise_lims", "brightness_contrast", "random_rotate")
+        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter,
+                    os.path.join(save_dir, save_name) if load_weights else None)
         self.params = {"optimizer": self.optimizer.state_dict(), "lr": lr, "n_filter": n_filter, "deep_supervision": deep_supervision,
                        "dilation": dilation, "batch_size": batch_size, "augmentation": getattr(dataset, "aug_factor", None),
-                       **{k: getattr(dataset, k, None) for k in keys}, "in_channels": in_channels, "output_heads": output_heads}
-        if self.augmenter is not None:      # only when it is on: every other checkpoint keeps its keys
-            self.params["online_augmentation"] = self.augmenter.describe()
-        if load_weights:
-            self.state = torch.load(os.path.join(save_dir, save_name))
-            self.model.load_state_dict(self.state["state_dict"])
-            self.epoch_start = self.state["epoch"]
-        else:
-            self.epoch_start = 0
+                       **self._data_attr("clip_threshold", "gauss_noise_lims", "shot_noise_lims", "brightness_contrast", "random_rotate"),
+                       "in_channels": in_channels, "output_heads": output_heads, **self._augment_entry()}
         try:
             from torch.utils.tensorboard import SummaryWriter
             self.writer = SummaryWriter(log_dir=os.path.join(save_dir, "logs"))
@@ -559,8 +513,6 @@ class TrainerMo2d(metaclass=_OwnKeywords):
     def _get_loss_function(loss_name):
         from .multi_output_unet.losses import get_loss_function
         return get_loss_function(loss_name)
-
-    _apply_activation = staticmethod(TrainerMo3d._apply_activation)
 
     def _batch(self, batch):
         x = batch["image"].to(self.device, non_blocking=True)
@@ -578,73 +530,41 @@ class TrainerMo2d(metaclass=_OwnKeywords):
         act = {k: self._apply_activation(pred[k], self.activations.get(k.rsplit("_", 1)[0] if ds else k)) for k in keys}
         return self.criterion(act, y, weights=[0.5, 0.75, 1.0] if ds else None)
 
-    def _scalar(self, tag, value, step):
-        if self.writer is not None:
-            self.writer.add_scalar(tag, value, step)
+    _forward_loss = _total_loss
 
-    def iterate(self, epoch, mode):
-        if mode == "train":
-            running = 0.0
-            with _gc_paused():
-                for batch in tqdm(self.train_loader, total=len(self.train_loader), unit="batch"):
-                    loss = self._total_loss(batch, validating=False)
-                    self.optimizer.zero_grad()
-                    loss.backward()
-                    self.optimizer.clip_grad_norm_(1.0)          # multi_output_unet/train.py:186, as three launches (biu_grad_clip)
-                    self.optimizer.step()
-                    running += self.criterion.item()             # total_loss.item() (:189): the step's one host read
-            self._scalar("Loss/train", running / max(len(self.train_loader), 1), epoch + self.epoch_start)
-            return None
-        losses = []
-        with torch.no_grad():
-            for batch in tqdm(self.val_loader, total=len(self.val_loader), unit="batch"):
-                losses.append(self._total_loss(batch, validating=True).detach())
-                self.criterion.check_range()
-        val_loss = torch.stack(losses).mean()
-        self._scalar("Loss/val", val_loss.item(), epoch + self.epoch_start)
-        return val_loss
-
-    def start(self):
-        import time
-        for epoch in range(self.num_epochs):
-            t0 = time.time()
-            self.iterate(epoch, "train")
-            self.state = {"epoch": epoch + self.epoch_start, "epoch_start": self.epoch_start, "best_loss": self.best_loss,
-                          "state_dict": self.model.state_dict()}
-            self.state.update(self.params)
-            with torch.no_grad():
-                val_loss = self.iterate(epoch, "val")
-                self.scheduler.step(val_loss)
-            print(f"\nEpoch {epoch} completed in {round(time.time() - t0, 2)} seconds.")
-            if val_loss < self.best_loss:
-                print("\nValidation loss improved from %s to %s - saving model state" % (round(self.best_loss.item(), 5), round(val_loss.item(), 5)))
-                self.state["best_loss"] = self.best_loss = val_loss
-                torch.save(self.state, os.path.join(self.save_dir, self.save_name))
-            if self.save_iter:
-                torch.save(self.state, os.path.join(self.save_dir, f"model_epoch_{epoch + self.epoch_start}.pt"))
+    def _report(self, epoch, improved, best, val, seconds):
+        print(f"\nEpoch {epoch} completed in {round(seconds, 2)} seconds.")
+        super()._report(epoch, improved, best, val, seconds)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # 2-D prediction: normalise -> tile -> forward (eval) -> uint8 -> stitch (mean of overlaps)
 # ----------------------------------------------------------------------------------------------------------------------
-def normalise_stack(imgs: np.ndarray, mode: str, clip, invert: bool) -> np.ndarray:
-    """Percentile clip and rescale to [0, 255] (``unet/predict.py:122-150``): per image ('single'), by the first image's
-    histogram ('first') or the whole stack's ('all').  Lower bound ``nanpercentile``, upper ``percentile`` as upstream."""
-    def scale(a, lo, hi):
-        a = np.clip(a, a_min=lo, a_max=hi)
+def _percentile_rescale(imgs, mode, clip, top=None, invert=False):
+    """Percentile clip, shift to 0 and divide by the maximum -- then times ``top`` and, with ``invert``, ``top - a``: per image ('single'), by
+    the first image's histogram ('first') or the whole stack's ('all').  Lower bound ``nanpercentile``, upper ``percentile`` as upstream."""
+    def scale(a, ref):
+        a = np.clip(a, a_min=np.nanpercentile(ref, clip[0]), a_max=np.percentile(ref, clip[1]))
         a = a - np.min(a)
-        a = a / np.max(a) * 255
-        return 255 - a if invert else a
+        a = a / np.max(a)
+        if top is not None:
+            a = a * top
+        return top - a if invert else a
 
     if mode == "single":
         for i, img in enumerate(imgs):
-            imgs[i] = scale(img, np.nanpercentile(img, clip[0]), np.percentile(img, clip[1]))
+            imgs[i] = scale(img, img)
         return imgs
     if mode == "first":
-        return scale(imgs, np.nanpercentile(imgs[0], clip[0]), np.percentile(imgs[0], clip[1]))
+        return scale(imgs, imgs[0])
     if mode == "all":
-        return scale(imgs, np.nanpercentile(imgs, clip[0]), np.percentile(imgs, clip[1]))
+        return scale(imgs, imgs)
     raise ValueError(f"normalization_mode {mode} not valid!")
+
+
+def normalise_stack(imgs: np.ndarray, mode: str, clip, invert: bool) -> np.ndarray:
+    """Percentile clip and rescale to [0, 255], ``a / max * 255`` in that order (``unet/predict.py:122-150``)."""
+    return _percentile_rescale(imgs, mode, clip, 255, invert)
 
 
 def tile_starts(extent: int, tile: int, n: int) -> np.ndarray:
@@ -729,7 +649,7 @@ class Predict2D:
         imgs = normalise_stack(imgs, normalization_mode, clip_threshold, invert)
         patches = self._split(imgs)
 
-        self.model_params = torch.load(model_params, map_location=self.device) if isinstance(model_params, str) else model_params
+        self.model_params = _load_params(model_params, self.device)
         if network is None:
             network = self.model_params.get("network")
             if network is None:
@@ -751,7 +671,8 @@ class Predict2D:
         self.model.load_state_dict(mp["state_dict"])
         self.model.eval()
         self.imgs_result = self._predict_and_stitch(patches, batch_size)
-        self._save(result_name, normalize_result)
+        # float16 like ``save_as_tif`` in the TIFF only; the ``.npy`` fallback keeps the array as it is
+        _write(result_name, _unit_range(self.imgs_result) if normalize_result else self.imgs_result, tif_dtype="float16" if normalize_result else None)
 
     def _split(self, imgs):
         n_img, h, w = self.imgs_shape
@@ -800,33 +721,36 @@ class Predict2D:
         res = torch.stack(done).cpu().numpy()[:, :, 0]                       # (n_img, oc, H, W)
         return np.squeeze(res[:, :, :h, :w])
 
-    def _save(self, result_name, normalize):
-        if result_name is None:
-            return
-        img = self.imgs_result
-        if normalize:
-            img = img - np.nanmin(img)
-            img = img / np.nanpercentile(img, 99.8)
-            img = np.clip(img, 0, 1)
-        try:
-            import tifffile
-            tifffile.imwrite(result_name, img.astype("float16") if normalize else img)
-        except ImportError:
-            np.save(result_name + ".npy" if not result_name.endswith(".npy") else result_name, img)
-
 
 def _load_params(model_params, device):
     return torch.load(model_params, map_location=device) if isinstance(model_params, str) else model_params
 
 
-def _write(result_name, arr):
+def _unit_range(img):
+    """``normalize_result``: shift to 0, divide by the 99.8th percentile, clip to [0, 1]."""
+    img = img - np.nanmin(img)
+    img = img / np.nanpercentile(img, 99.8)
+    return np.clip(img, 0, 1)
+
+
+def _write(result_name, arr, tif_dtype=None):
     if result_name is None:
         return
     try:
         import tifffile
-        tifffile.imwrite(result_name, arr)
+        tifffile.imwrite(result_name, arr if tif_dtype is None else arr.astype(tif_dtype))
     except ImportError:
         np.save(result_name if result_name.endswith(".npy") else result_name + ".npy", arr)
+
+
+def _write_heads(result_path, result):
+    """``result_path`` given: one file per head (``result_path + name + '.tif'`` in an existing folder, else ``result_path_name.tif``) and
+    ``None``; otherwise the dictionary itself."""
+    if result_path is None:
+        return result
+    for k, arr in result.items():
+        _write((result_path + k + ".tif") if os.path.exists(result_path) else (result_path + "_" + k + ".tif"), arr)
+    return None
 
 
 class Predict3D:
@@ -850,12 +774,7 @@ class Predict3D:
         if vol.ndim == 2:
             vol = vol[None]
             self.vol_shape = vol.shape
-        lo, hi = np.nanpercentile(vol, clip_threshold[0]), np.percentile(vol, clip_threshold[1])
-        vol = np.clip(vol, lo, hi)
-        vol = vol - np.min(vol)
-        vol = vol / np.max(vol) * 255
-        if invert:
-            vol = 255 - vol
+        vol = normalise_stack(vol, "all", clip_threshold, invert)       # the whole volume's histogram, whatever normalization_mode says
         patches = self._split(vol)
         mp = self.model_params = _load_params(model_params, self.device)
         self.model = network(n_filter=mp["n_filter"], in_channels=mp["in_channels"], out_channels=mp["out_channels"],
@@ -874,11 +793,7 @@ class Predict3D:
                 st.add(_quantize_u8(prob).view((1,) + self.resize_dim), origins[i], layer=i % 3, overwrite=True)
         out = st.finish(True)[0].cpu().numpy()
         self.vol_result = np.squeeze(out[:vs[0], :vs[1], :vs[2]])
-        out = self.vol_result
-        if normalize_result:
-            out = out - np.nanmin(out)
-            out = np.clip(out / np.nanpercentile(out, 99.8), 0, 1).astype("float16")
-        _write(result_name, out)
+        _write(result_name, _unit_range(self.vol_result).astype("float16") if normalize_result else self.vol_result)
 
     def _split(self, vol):
         vs, rd, ap = self.vol_shape, self.resize_dim, self.add_patch
@@ -998,13 +913,7 @@ class PredictMo3d:
         self.model.load_state_dict(mp["state_dict"])
         self.model.eval()
         self.target_keys = list(mp["output_heads"].keys())
-        result = self._predict_and_blend(patches, batch_size)
-        if result_path is not None:
-            for k in self.target_keys:
-                _write((result_path + k + ".tif") if os.path.exists(result_path) else (result_path + "_" + k + ".tif"), result[k])
-            self.result = None
-        else:
-            self.result = result
+        self.result = _write_heads(result_path, self._predict_and_blend(patches, batch_size))
 
     @staticmethod
     def _preprocess(imgs, mode, clip):
@@ -1127,30 +1036,12 @@ class PredictMo2d:
         self.model.load_state_dict(mp["state_dict"])
         self.model.eval()
         self.target_keys = list(mp["output_heads"].keys())
-        result = self._predict_and_stitch(patches, batch_size)
-        if result_path is not None:
-            for k in self.target_keys:
-                _write((result_path + k + ".tif") if os.path.exists(result_path) else (result_path + "_" + k + ".tif"), result[k])
-            self.result = None
-        else:
-            self.result = result
+        self.result = _write_heads(result_path, self._predict_and_stitch(patches, batch_size))
 
     @staticmethod
     def _preprocess(imgs, mode, clip):
         """Percentile clip, then to [0, 1] (``predict.py:129-151``; lower bound ``nanpercentile``, upper ``percentile``)."""
-        def scale(a, lo, hi):
-            a = np.clip(a, a_min=lo, a_max=hi)
-            a = a - np.min(a)
-            return a / np.max(a)
-        if mode == "single":
-            for i, img in enumerate(imgs):
-                imgs[i] = scale(img, np.nanpercentile(img, clip[0]), np.percentile(img, clip[1]))
-            return imgs
-        if mode == "first":
-            return scale(imgs, np.nanpercentile(imgs[0], clip[0]), np.percentile(imgs[0], clip[1]))
-        if mode == "all":
-            return scale(imgs, np.nanpercentile(imgs, clip[0]), np.percentile(imgs, clip[1]))
-        raise ValueError(f"normalization_mode {mode} not valid!")
+        return _percentile_rescale(imgs, mode, clip)
 
     @staticmethod
     def geometry(imgs_shape, max_patch_size, add_tile):

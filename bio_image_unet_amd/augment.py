@@ -30,7 +30,8 @@ counter (element group, dataset index, epoch, field-and-stage id).  Same seed ->
 This is distribution-level equivalence to the reference pipeline, not bit parity ("On-device augmentation").
 
 The 2-D multi-output family's float fields have a pipeline of their own, ``AugmenterF32`` / ``biu_augment_f32`` in the second half of this file;
-the two classes share the record stream and the launch loop (``_AugmenterCore``) and keep their own records, limits and kernels.
+the 3-D multi-output family's volumes a third, ``AugmenterVol`` / ``biu_augment_vol_f32`` at the end.  The three classes share the record
+stream and the launch loop (``_AugmenterCore``) and keep their own limits and kernels (the two float classes share the record).
 """
 from __future__ import annotations
 
@@ -127,9 +128,11 @@ def record(index: int, h: int, w: int, *, gate: bool = True, rot_k: int = 0, ssr
 
 
 class _AugmenterCore:
-    """What ``Augmenter`` and ``AugmenterF32`` share: the per-sample Philox stream and the record buffer on the host, the checks and the
-    per-field loop around the launch on the device.  A subclass names its record (``params_dtype``, ``_rec``, ``n_uniform``, ``blur_flag``), its
-    kinds, the store attributes its constructor takes and its tensor dtypes, and provides ``_packer`` and ``_launch``."""
+    """What ``Augmenter``, ``AugmenterF32`` and ``AugmenterVol`` share: the per-sample Philox stream and the record buffer on the host, the
+    checks and the per-field loop around the launch on the device.  A subclass names its record (``params_dtype``, ``_rec``, ``n_uniform``,
+    ``blur_flag``), its kinds, the store attributes its constructor takes, its tensor dtypes and layouts (``field_dims``, ``field_layout``), and
+    provides ``_packer`` and ``_launch``."""
+    field_dims, field_layout = (3, 4), "[B, H, W] or [B, C, H, W]"      # a field without / with the channel axis
 
     def _init_core(self, seed, kinds, shape):
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -176,7 +179,7 @@ class _AugmenterCore:
     # ---- device ------------------------------------------------------------------------------------------------------------------
     def __call__(self, batch: Dict[str, torch.Tensor], params: np.ndarray, epoch: int, out: Optional[Dict[str, torch.Tensor]] = None,
                  params_dev: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        """Augment ``{field: device tensor [B, H, W] | [B, C or D, H, W]}`` with the records ``params`` (``draw``'s result, one per sample) on the
+        """Augment ``{field: device tensor [B, H, W] | [B, C or D, H, W]}`` (``AugmenterVol``: ``[B, D, H, W] | [B, C, D, H, W]``) with the records ``params`` (``draw``'s result, one per sample) on the
         current stream; ``out``: tensors to write into (never the inputs: a gather cannot run in place); ``params_dev``: the same records
         already on the device as bytes (the feeder uploads them with the batch).  ``Augmenter`` takes and writes uint8; ``AugmenterF32``
         takes float32 or uint8 and always writes float32."""
@@ -193,12 +196,12 @@ class _AugmenterCore:
         src, dst_dtype = self.src_dtypes, self.dst_dtype
         res = {}
         for name, t in batch.items():
-            if t.dtype not in src or not t.is_cuda or t.dim() not in (3, 4) or not t.is_contiguous():
-                raise ValueError(f'field "{name}": a contiguous {_names(src)} device tensor [B, H, W] or [B, C, H, W] is expected')
+            if t.dtype not in src or not t.is_cuda or t.dim() not in self.field_dims or not t.is_contiguous():
+                raise ValueError(f'field "{name}": a contiguous {_names(src)} device tensor {self.field_layout} is expected')
             dst = out[name] if out is not None else torch.empty(t.shape, dtype=dst_dtype, device=t.device)
             if dst.shape != t.shape or dst.dtype != dst_dtype or dst.device != t.device or not dst.is_contiguous() or dst.data_ptr() == t.data_ptr():
                 raise ValueError(f'field "{name}": the output must be a second contiguous {_names((dst_dtype,))} tensor of the same shape and device')
-            check(self._launch(lib, name, t, dst, t.shape[1] if t.dim() == 4 else 1, params_dev, max_blur, int(epoch) & 0xFFFFFFFF, stream),
+            check(self._launch(lib, name, t, dst, t.shape[1] if t.dim() == self.field_dims[1] else 1, params_dev, max_blur, int(epoch) & 0xFFFFFFFF, stream),
                   self.launch_name)
             res[name] = dst
         return res
@@ -431,3 +434,138 @@ class AugmenterF32(_AugmenterCore):
         return lib.biu_augment_f32(C.c_void_p(t.data_ptr()), int(t.dtype == torch.uint8), C.c_void_p(dst.data_ptr()), t.shape[0], planes,
                                    t.shape[-2], t.shape[-1], kind, C.c_void_p(params_dev.data_ptr()), max_blur if kind == KIND_IMAGE else 0,
                                    self.seed, epoch, field_id(name), stream)
+
+
+# =====================================================================================================================================
+# float volumes: the 3-D multi-output family (``biu_augment_vol_f32``)
+# =====================================================================================================================================
+# The reference's pipeline for this family (``multi_output_unet3d/data.py:152-178``): ``ShiftScaleRotate(shift_limit=0, p=0.8)`` ->
+# ``RandomCrop3D(dim_out)`` on the volume and every target (each declared ``mask3d``), then, with probability 0.8, slice by slice on the
+# volume alone ``RandomBrightnessContrast(p=0.5)`` -> ``Blur(p=0.3)`` -> ``ShotNoise(p=0.5)`` -> ``GaussNoise(p=0.5)``.  Every z-plane of every
+# channel gets the same in-plane map; nothing wraps:
+#
+# =========  ================================================================================================================
+# kind       what the kernel does
+# =========  ================================================================================================================
+# "image"    bilinear gather, then brightness/contrast -> blur (of that result) -> shot noise -> Gauss noise (fp32, clipped to [0, 1])
+# "mask"     any scalar target: nearest gather, nothing else
+# "vector"   channel pairs ``(cos phi, sin phi)``, a volume apart: nearest gather, the pair is rotated by the record's rotation (phi - t)
+# =========  ================================================================================================================
+#
+# The fields ``volume`` and ``image`` are images, a field named ``orientation`` a vector, every other field a mask; ``kinds={...}`` overrides.
+BORDER_REFLECT, BORDER_CONSTANT = 0, 1                                        # include/biu.h: BIU_AUGV_*
+BORDERS_VOL = {"reflect": BORDER_REFLECT, "constant": BORDER_CONSTANT}
+STAGE_P_MO3D = {"shift_scale_rotate": 0.8, "intensity": 0.8, "brightness_contrast": 0.5, "blur": 0.3, "shot_noise": 0.5, "gauss_noise": 0.5}
+
+
+class AugmenterVol(_AugmenterCore):
+    """Draws ``biu_augf_params`` records on the host and runs ``biu_augment_vol_f32`` on device batches of float32 or uint8 volumes
+    ``[B, D, H, W]`` or ``[B, C, D, H, W]`` (the output is always float32): the 3-D multi-output family's recipe ``"mo3d"``.
+
+    Limits default to the reference constructor's.  ``border``: what lies outside a plane, ``"reflect"`` (reflect-101, albumentations 1.4's
+    default for ``ShiftScaleRotate`` and what this package's uint8 recipes do) or ``"constant"`` (0, albumentations 2's default).  The blur's own
+    border is always reflect-101, as ``cv2.blur``'s.  ``RandomCrop3D(dim_out)`` is the identity here: the tiles of a store already have
+    ``dim_out``, so there is nothing to crop and no offset to draw.
+
+    ``draw`` takes thirteen uniforms per sample, in this order whatever the gates say:
+
+    ==  ==================================================================================================
+    u   use
+    ==  ==================================================================================================
+    0   shift-scale-rotate gate (< 0.8)
+    1   scale: ``1 + scale_limit[0] + u (scale_limit[1] - scale_limit[0])``
+    2   angle in degrees: ``rotate_limit[0] + u (rotate_limit[1] - rotate_limit[0])``, about the plane centre, ``_matrix``'s sign
+    3   gate of the intensity block as a whole (< 0.8); the four gates below count only behind it
+    4   brightness/contrast gate (< 0.5)
+    5   contrast: ``alpha = 1 + (2 u - 1) brightness_contrast[1]``
+    6   brightness: ``beta = (2 u - 1) brightness_contrast[0]``
+    7   blur gate (< 0.3)
+    8   blur size: one of the odd sizes in ``blur_limit``
+    9   shot-noise gate (< 0.5)
+    10  shot-noise scale in ``shot_noise_lims``
+    11  Gauss-noise gate (< 0.5)
+    12  Gauss-noise standard deviation in ``gauss_noise_lims``
+    ==  ==================================================================================================
+    """
+
+    recipe = "mo3d"
+    params_dtype, _rec, n_uniform, blur_flag = PARAMS_F32_DTYPE, _REC_F32, 13, BLUR_F
+    allowed_kinds = tuple(KINDS_F32)
+    store_attrs = ("scale_limit", "rotate_limit", "gauss_noise_lims", "shot_noise_lims", "brightness_contrast", "blur_limit")
+    src_dtypes, dst_dtype, launch_name = (torch.float32, torch.uint8), torch.float32, "augment_vol_f32"
+    field_dims, field_layout = (4, 5), "[B, D, H, W] or [B, C, D, H, W]"
+
+    def __init__(self, *, scale_limit=(-0.75, 0), rotate_limit=(0, 360), gauss_noise_lims=(0.01, 0.1), shot_noise_lims=(0.005, 0.01),
+                 brightness_contrast=(0.1, 0.1), blur_limit=(3, 7), border: str = "reflect", seed: int = 0,
+                 kinds: Optional[Dict[str, str]] = None, shape: Optional[Sequence[int]] = None):
+        sl, rl = _pair(scale_limit, "scale_limit"), _pair(rotate_limit, "rotate_limit")
+        self.scale_limit = tuple(float(v) for v in ((-sl[0], sl[0]) if np.isscalar(scale_limit) else sl))
+        self.rotate_limit = tuple(float(v) for v in ((-rl[0], rl[0]) if np.isscalar(rotate_limit) else rl))
+        self.gauss_noise_lims = tuple(float(v) for v in _pair(gauss_noise_lims, "gauss_noise_lims"))
+        self.shot_noise_lims = tuple(float(v) for v in _pair(shot_noise_lims, "shot_noise_lims"))
+        self.brightness_contrast = tuple(float(v) for v in _pair(brightness_contrast, "brightness_contrast"))
+        self.blur_limit = tuple(int(v) for v in _pair(blur_limit, "blur_limit"))
+        if border not in BORDERS_VOL:
+            raise ValueError(f'border "{border}": one of {sorted(BORDERS_VOL)}')
+        self.border = border
+        if self.blur_limit[1] > MAX_BLUR:
+            raise ValueError(f"blur_limit {self.blur_limit}: box kernels above {MAX_BLUR} are not supported")
+        self.blur_sizes = [k for k in range(max(3, self.blur_limit[0]), self.blur_limit[1] + 1) if k % 2]
+        if not self.blur_sizes:
+            raise ValueError(f"blur_limit {self.blur_limit} holds no odd kernel size of 3 or more")
+        if not 0 < self.shot_noise_lims[0] <= self.shot_noise_lims[1]:
+            raise ValueError("shot_noise_lims: positive scales, lower first")
+        if not 0 <= self.gauss_noise_lims[0] <= self.gauss_noise_lims[1]:
+            raise ValueError("gauss_noise_lims: standard deviations, lower first")
+        if not -1 < self.scale_limit[0] <= self.scale_limit[1]:
+            raise ValueError("scale_limit: 1 + limit must stay positive, lower first")
+        if not self.rotate_limit[0] <= self.rotate_limit[1] or not all(math.isfinite(v) for v in self.rotate_limit):
+            raise ValueError("rotate_limit: finite angles in degrees, lower first")
+        self._init_core(seed, kinds, shape)
+
+    @classmethod
+    def _store_kw(cls, store, overrides):
+        kw = super()._store_kw(store, {})
+        if "image" not in store.fields and "volume" in store.fields:
+            kw["shape"] = tuple(store.fields["volume"])
+        kw.update(overrides)
+        return kw
+
+    @classmethod
+    def from_store(cls, store, recipe: str = "mo3d", **overrides) -> "AugmenterVol":
+        """Limits from the attributes a ``TileStore`` records, else the reference's defaults."""
+        if recipe != "mo3d":
+            raise ValueError(f'recipe "{recipe}" not defined for float volumes (only "mo3d")')
+        return cls(**cls._store_kw(store, overrides))
+
+    def describe(self) -> dict:
+        return {"recipe": self.recipe, "seed": self.seed, "scale_limit": self.scale_limit, "rotate_limit": self.rotate_limit,
+                "gauss_noise_lims": self.gauss_noise_lims, "shot_noise_lims": self.shot_noise_lims,
+                "brightness_contrast": self.brightness_contrast, "blur_limit": self.blur_limit, "border": self.border,
+                "stage_p": dict(STAGE_P_MO3D), "kinds": dict(self.kinds)}
+
+    def kind(self, name: str) -> str:
+        return self.kinds.get(name, "image" if name in ("volume", "image") else "vector" if name == "orientation" else "mask")
+
+    def _packer(self, h, w):
+        """``draw``'s record from thirteen uniforms (class docstring)."""
+        lerp = lambda u, lim: lim[0] + u * (lim[1] - lim[0])
+        P, sizes, bcl = STAGE_P_MO3D, self.blur_sizes, self.brightness_contrast
+        scale_limit, rotate_limit, shot_lims, gauss_lims = self.scale_limit, self.rotate_limit, self.shot_noise_lims, self.gauss_noise_lims
+
+        def pack(buf, offset, index, u):
+            ssr, on = u[0] < P["shift_scale_rotate"], u[3] < P["intensity"]
+            _pack_f32(buf, offset, index, h, w, 0, lerp(u[2], rotate_limit) if ssr else None, 1.0 + lerp(u[1], scale_limit) if ssr else None, (0, 0),
+                      sizes[min(int(u[8] * len(sizes)), len(sizes) - 1)] if on and u[7] < P["blur"] else 0,
+                      lerp(u[10], shot_lims) if on and u[9] < P["shot_noise"] else None,
+                      lerp(u[12], gauss_lims) if on and u[11] < P["gauss_noise"] else None,
+                      (1.0 + (2.0 * u[5] - 1.0) * bcl[1], (2.0 * u[6] - 1.0) * bcl[0]) if on and u[4] < P["brightness_contrast"] else None)
+        return pack
+
+    def _launch(self, lib, name, t, dst, channels, params_dev, max_blur, epoch, stream):
+        kind = KINDS_F32[self.kind(name)]
+        if kind == KIND_VECTOR and channels % 2:
+            raise ValueError(f'field "{name}": a vector field holds (cos, sin) channel pairs [B, 2 j, D, H, W], got {channels} channel(s)')
+        return lib.biu_augment_vol_f32(C.c_void_p(t.data_ptr()), int(t.dtype == torch.uint8), C.c_void_p(dst.data_ptr()), t.shape[0], channels,
+                                       t.shape[-3], t.shape[-2], t.shape[-1], kind, BORDERS_VOL[self.border], C.c_void_p(params_dev.data_ptr()),
+                                       max_blur if kind == KIND_IMAGE else 0, self.seed, epoch, field_id(name), stream)

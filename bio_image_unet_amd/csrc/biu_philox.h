@@ -1,5 +1,5 @@
 // Philox4x32-10 (Salmon et al., Random123) and the 24-bit uniform the augmentation kernels draw from it: shared by biu_augment.hip (uint8
-// batches) and biu_augment_f32.hip (float fields), so both read the one stream tests/augment_oracle.py restates.
+// batches), biu_augment_f32.hip (float fields) and biu_augment_vol.hip (float volumes), so all read the one stream tests/augment_oracle.py restates.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -21,7 +21,7 @@ every epoch, from a store of un-augmented tiles (``augment.py``).
 The 2-D multi-output family's items are float32 (``multi_output_unet/data.py:318-349``): distance and probability maps, and an
 ``orientation`` target that reaches the network as ``(cos, sin)`` in [-1, 1].  A store field therefore has a dtype, ``"u8"`` (the default) or
 ``"f32"`` (file ``<path>.<field>.f32``, written and read back bit for bit, never scaled); the feeder carries float fields as float32 and
-``augment.AugmenterF32`` augments them.  A mixed store (``image`` as u8, targets as f32) keeps the image's PCIe traffic at a quarter.
+``augment.AugmenterF32`` (2-D) or ``augment.AugmenterVol`` (volumes) augments them.  A mixed store (``image`` as u8, targets as f32) keeps the image's PCIe traffic at a quarter.
 """
 from __future__ import annotations
 
@@ -97,7 +97,7 @@ class TileStore(torch.utils.data.Dataset):
         fields = {k: tuple(np.asarray(first[k]).shape) for k in keys}
         attrs = {}
         for a in ("dim_out", "aug_factor", "clip_threshold", "noise_lims", "noise_amp", "brightness_contrast", "shiftscalerotate", "blur_limit",
-                  "gauss_noise_lims", "shot_noise_lims", "random_rotate", "scale_limit"):
+                  "gauss_noise_lims", "shot_noise_lims", "random_rotate", "scale_limit", "rotate_limit"):
             if hasattr(dataset, a):
                 v = getattr(dataset, a)
                 attrs[a] = list(v) if isinstance(v, (tuple, list)) else v
@@ -174,7 +174,7 @@ class DeviceFeeder:
         if augmenter is not None:
             out_dtype = augmenter.dst_dtype                                  # augment.AugmenterF32 writes float32 whatever the field holds
             if out_dtype == torch.uint8 and any(dt != torch.uint8 for dt in dtypes.values()):
-                raise ValueError("a store with float fields needs augment.AugmenterF32 (augment.Augmenter works on uint8 fields)")
+                raise ValueError("a store with float fields needs augment.AugmenterF32 or AugmenterVol (augment.Augmenter works on uint8 fields)")
             rec = augmenter.params_dtype.itemsize
             for slot in self.slots:
                 slot["aug"] = {k: mk(k, False, out_dtype) for k in store.fields}

@@ -12,7 +12,7 @@ numerics-relevant quirks, so a training run is step-for-step comparable:
 * The saved ``'optimizer'`` entry is the construction-time state (2-D / 3-D), never refreshed.
 
 What differs by design: the network class comes from this package (every layer a HIP kernel), the optimizer is the fused
-``biu_adam_step``, and data sets are any ``torch.utils.data.Dataset`` yielding the reference's dict items (TIFF I/O is out of scope; ``Trainer2D`` / ``Trainer3D`` / ``TrainerSiam``
+``biu_adam_step``, and data sets are any ``torch.utils.data.Dataset`` yielding the reference's dict items (TIFF I/O is out of scope; all five Trainers
 take ``augment=True`` to augment the training batches of a ``feed.TileStore`` on the device, ``augment.py``).
 
 Layout: all five Trainers sit on ``_EpochLoop`` (construction tail, batch loop, validation loop, epoch driver); a family is its constructor,
@@ -57,14 +57,15 @@ def _make_criterion(name, params, extra=None):
 
 
 def _resolve_augment(augment, dataset, device, recipe):
-    """``augment`` keyword of the Trainers -> ``augment.Augmenter`` (the uint8 families), ``augment.AugmenterF32`` (recipe ``"mo2d"``) or None.
+    """``augment`` keyword of the Trainers -> ``augment.Augmenter`` (the uint8 families), ``augment.AugmenterF32`` (recipe ``"mo2d"``),
+    ``augment.AugmenterVol`` (recipe ``"mo3d"``) or None.
     On-device augmentation works on the batches of a ``DeviceFeeder``, so anything but a ``TileStore`` on a GPU is refused rather than
     silently trained un-augmented."""
     if augment is None or augment is False:
         return None
-    from .augment import Augmenter, AugmenterF32
+    from .augment import Augmenter, AugmenterF32, AugmenterVol
     from .feed import TileStore
-    cls = AugmenterF32 if recipe == "mo2d" else Augmenter
+    cls = {"mo2d": AugmenterF32, "mo3d": AugmenterVol}.get(recipe, Augmenter)
     if not isinstance(dataset, TileStore) or torch.device(device).type != "cuda":
         raise ValueError("augment: on-device augmentation needs a feed.TileStore data set and a GPU device")
     if augment is True:
@@ -385,9 +386,12 @@ class TrainerMo3d(_MultiHeadLoop):
     def __init__(self, dataset, output_heads, num_epochs, network=MultiOutputUnet3D, use_interpolation=False, batch_size=4,
                  lr=1e-3, in_channels=1, n_filter=64, dilation=1, val_split=0.2, save_dir="./", save_name="model.pt",
                  save_iter=False, load_weights=False, loss_function="BCEDice", loss_params=(0.5, 0.5), time_loss_weight=0.1,
-                 device: Union[torch.device, str] = "auto", fp32_products: Optional[str] = None):
+                 device: Union[torch.device, str] = "auto", fp32_products: Optional[str] = None, augment=None):
+        """``augment`` (not in the reference, which augments offline): ``True`` or an ``augment.AugmenterVol`` -- the training batches of a
+        ``feed.TileStore`` are augmented on the device, fresh every epoch (``augment.py``, recipe ``"mo3d"``); validation batches never."""
         _set_fp32_products(fp32_products, three_d=True)             # see Trainer3D
         self.device = _pick_device(device)
+        augmenter = _resolve_augment(augment, dataset, self.device, "mo3d")
         self.network = network
         self.model = network(n_filter=n_filter, in_channels=in_channels, output_heads=output_heads,
                              use_interpolation=use_interpolation).to(self.device)
@@ -400,7 +404,7 @@ class TrainerMo3d(_MultiHeadLoop):
         else:
             self.criterion = _make_criterion(loss_function, loss_params)       # built but unused by the loop, as upstream
         self.criterion_time = nn.SmoothL1Loss()
-        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter,
+        self._setup(dataset, num_epochs, batch_size, lr, val_split, save_dir, save_name, save_iter, augmenter,
                     load_from=os.path.join(save_dir, save_name) if load_weights else None)
         self.params = {"optimizer": self.optimizer.state_dict(), "lr": lr, "loss_function": loss_function,
                        "loss_params": loss_params, "time_loss_weight": time_loss_weight, "n_filter": n_filter,
@@ -408,7 +412,7 @@ class TrainerMo3d(_MultiHeadLoop):
                        "augmentation": getattr(dataset, "aug_factor", None),
                        **self._data_attr("clip_threshold", "scale_limit", "rotate_limit", "gauss_noise_lims", "shot_noise_lims", "blur_limit",
                                          "random_rotate", "brightness_contrast"),
-                       "in_channels": in_channels, "output_heads": output_heads}
+                       "in_channels": in_channels, "output_heads": output_heads, **self._augment_entry()}
 
     @staticmethod
     def _get_loss_function(loss_name):

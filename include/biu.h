@@ -625,6 +625,39 @@ int biu_augment_f32(const void* src, int src_is_u8, float* dst, int n, int plane
                     int max_blur_k, unsigned long long seed, unsigned epoch, unsigned field_id, biu_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * On-the-fly training augmentation of float volumes: the 3-D multi-output family (multi_output_unet3d/data.py:152-178, which the
+ * reference runs offline through albumentations).  One launch per field per batch; the records are biu_augf_params unchanged.
+ *
+ * src [n, channels, depth, h, w]: float32, or uint8 (src_is_u8 != 0) widened on load as (float)byte / 255.0f.  dst: float32 of the same
+ * shape, never src.  Every z-plane of every channel gets the record's in-plane map m (any m; fp64 coordinates and weights).  Nothing
+ * wraps; `border` says what lies outside a plane:
+ *   BIU_AUGV_REFLECT  : reflect-101 (d c b | a b c d | c b a) at any distance from the image
+ *   BIU_AUGV_CONSTANT : taps outside the image read 0 and keep their bilinear weight
+ * kind:
+ *   BIU_AUGF_IMAGE  : bilinear gather, then BC -> BLUR -> SHOT -> GAUSS, each when its flag is set, in fp32:
+ *                       BC    : v = clip(v alpha + beta, 0, 1), product and sum rounded one after the other
+ *                       BLUR  : blur_k x blur_k box mean (odd, <= BIU_AUG_MAX_BLUR) of BC(gather).  Pixels outside the plane are the
+ *                               reflect-101 of that OUTPUT plane whatever `border` says (cv2.blur's default border); fp32 sums, first k
+ *                               along x, then k along y, times 1 / k^2
+ *                       SHOT, GAUSS : biu_augment_f32's arithmetic, samplers, stage ids and Philox counter; the element is the voxel's
+ *                               index inside the sample's channels x depth x h x w field
+ *   BIU_AUGF_MASK   : any scalar target: nearest gather floor(c + 0.5), nothing else
+ *   BIU_AUGF_VECTOR : channels even; the pair (c, s) is channels (2j, 2j + 1), depth x h x w apart.  Both are gathered nearest at one
+ *                     source voxel, then (c cos_t + s sin_t, s cos_t - c sin_t)
+ * The kernel reads flags (BLUR | SHOT | GAUSS | BC), blur_k, index, m, cos_t, sin_t, alpha, beta, shot_s and gauss_sigma.
+ * max_blur_k: as for biu_augment_f32.  2^31 elements or more, field_id >= 2^28 and every other argument error return a status and launch nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define BIU_AUGV_REFLECT 0   /* reflect-101: d c b | a b c d | c b a, any distance from the image */
+#define BIU_AUGV_CONSTANT 1  /* taps outside the image read 0 and keep their bilinear weight */
+int biu_augment_vol_f32(const void* src, int src_is_u8, float* dst, int n, int channels, int depth, int h, int w,
+                        int kind, int border, const biu_augf_params* params, int max_blur_k,
+                        unsigned long long seed, unsigned epoch, unsigned field_id, biu_stream stream);
+/* How that launch would be cut, without launching: the planes (VECTOR: pairs of planes) a lane walks with one set of taps, or, with
+ * max_blur_k > 1, a block of the blurring path walks; 1 .. 16, the last chunk of a field may be shorter.  dst_aligned16: dst % 16 == 0.
+ * 0 for dimensions, a kind or a max_blur_k the launch refuses.  For tests and tools, so that they can say which loop a shape ran. */
+int biu_augment_vol_chunk(int n, int channels, int depth, int h, int w, int kind, int max_blur_k, int dst_aligned16);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused multi-tensor Adam                                                              [K14]
  * replaces torch.optim.Adam(lr) step: unet/train.py:102,139 (betas 0.9/0.999, eps 1e-8, no decay).
  * One launch updates `n` parameter tensors; ptrs are device arrays of device pointers.

@@ -15,7 +15,7 @@ def set_fp32_products(mode: str) -> None:
     """How the fp32 2-D 3x3 convolution / ConvTranspose kernels multiply (the 3-D kernels: ``set_fp32_products_3d``):
 
     * ``"bf16x6"`` (default): every fp32 operand is split hi + mid + lo in bf16 (24 significant bits) and a product is the six bf16 MFMA terms
-      of order >= 2^-16, accumulated in fp32 -- <= 2^-23 relative per product, i.e. fp32-grade, at 2.7x the matrix-pipe rate of the fp32 MFMA;
+      of order >= 2^-16, accumulated in fp32 -- <= 2^-22 relative per product (measured worst 2^-22.6), i.e. fp32-grade, at 2.7x the matrix-pipe rate of the fp32 MFMA;
     * ``"exact"``: ``v_mfma_f32_32x32x2_f32`` (fp32 FMA chains);
     * ``"bf16x3"`` (opt-in): hi + lo, three terms, <= 2^-15 relative per product, another 2x -- the counterpart of
       ``torch.backends.cudnn.allow_tf32`` for the reference's fp32 trainers.
@@ -32,7 +32,7 @@ def set_fp32_products_3d(mode: str) -> None:
 
     * ``"exact"`` (default): ``v_mfma_f32_32x32x2_f32`` (fp32 FMA chains);
     * ``"bf16x6"`` (opt-in): every fp32 operand is split hi + mid + lo in bf16 and a product is the six bf16 MFMA terms of order >= 2^-16,
-      accumulated in fp32 -- <= 2^-23 relative per product, i.e. fp32-grade;
+      accumulated in fp32 -- <= 2^-22 relative per product (measured worst 2^-22.6), i.e. fp32-grade;
     * ``"bf16x3"`` (opt-in): hi + lo, three terms, <= 2^-15 relative per product -- the counterpart of ``torch.backends.cudnn.allow_tf32``.
 
     Launches with fewer than 16 (or a non-multiple of 16) reduction channels stay exact, as do 3x3x3 launches too wide for LDS (more than

@@ -64,7 +64,9 @@ int  biu_version(void);
 /* How fp32 tensors are multiplied by the 2-D 3x3 convolution and ConvTranspose kernels (forward, data gradient, weight gradient).
  *   2 "bf16x6" (default): every operand is split hi + mid + lo in bf16 while it is staged (24 significant bits: the split is exact up to
  *                2^-24), a product is the six terms of order >= 2^-16 -- hi*hi' + hi*mid' + mid*hi' + mid*mid' + hi*lo' + lo*hi' -- on the
- *                bf16 matrix pipe with fp32 accumulation: <= 2^-23 relative per product, i.e. as good as an fp32 product's own rounding, at
+ *                bf16 matrix pipe with fp32 accumulation: <= 2^-22 relative per product (what is dropped is <= 2^-23; summing the six terms in
+ *                the pipe's fp32 accumulator adds the rest: measured on single products worst 2^-22.6, median 2^-25.3, against 2^-24 / 2^-25.5
+ *                of the fp32 MFMA's own rounding to nearest -- tests/test_gpu_fp32_product_probes.py), i.e. fp32-grade, at
  *                2.7 x the matrix-pipe rate of the fp32 MFMA.  Tensors, accumulators and every other kernel stay fp32.
  *   0 "exact"  : v_mfma_f32_32x32x2_f32 -- IEEE fp32 products, fp32 accumulation.
  *   1 "bf16x3" : hi + lo, three terms: <= 2^-15 relative per product (32 x tighter than the TF32 products torch.backends.cudnn

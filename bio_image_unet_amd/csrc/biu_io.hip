@@ -1,7 +1,8 @@
-// Data formats on either side of the network: the reference feeds uint8 tiles scaled by 1/255
+// Data formats on either side of the network: the reference feeds uint8 tiles divided by 255
 // (unet/data.py:253-266, unet/predict.py:192-196) and re-quantises probabilities to uint8 before stitching overlapping
 // tiles (unet/predict.py:199-229; linear-ramp blending in multi_output_unet3d/predict.py:203-307).  These kernels keep
-// both ends on the device: uint8 batches are uploaded as they are and scaled while they are laid out channels-last, results
+// both ends on the device: uint8 batches are uploaded as they are and divided while they are laid out channels-last (the correctly
+// rounded fp32 quotient, `tile.astype('float32') / 255` bit for bit: byte * (1/255) differs from it in the last bit for 126 codes), results
 // are quantised, accumulated into the stitched volume and normalised without leaving HBM.  All of it is HBM-bound byte work.
 #include <hip/hip_runtime.h>
 
@@ -12,18 +13,18 @@ namespace {
 constexpr int TPB = 256;
 
 template <typename T>
-__global__ void k_from_nchw_u8(const uint8_t* __restrict__ src, float scale, DAct dst) {
+__global__ void k_from_nchw_u8(const uint8_t* __restrict__ src, float divisor, DAct dst) {
     const i64 S = (i64)dst.d * dst.h * dst.w;
     const i64 total = (i64)dst.n * S * dst.c;
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (i64)gridDim.x * blockDim.x) {
         const int c = (int)(i % dst.c);
         const i64 v = i / dst.c;
         const i64 n = v / S, s = v % S;
-        st_act<T>(dst, v, c, (float)src[(n * dst.c + c) * S + s] * scale);
+        st_act<T>(dst, v, c, (float)src[(n * dst.c + c) * S + s] / divisor);
     }
 }
-__global__ void k_u8_to_f32(const uint8_t* __restrict__ src, float scale, float* __restrict__ dst, i64 total) {
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (i64)gridDim.x * blockDim.x) dst[i] = (float)src[i] * scale;
+__global__ void k_u8_to_f32(const uint8_t* __restrict__ src, float divisor, float* __restrict__ dst, i64 total) {
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (i64)gridDim.x * blockDim.x) dst[i] = (float)src[i] / divisor;
 }
 // (p * 255).astype('uint8'): truncation toward zero of a value in [0, 255]
 __global__ void k_quantize_u8(const float* __restrict__ src, float scale, uint8_t* __restrict__ dst, i64 total) {
@@ -75,16 +76,16 @@ __global__ void k_stitch_finish(const float* __restrict__ acc, const float* __re
 }
 }  // namespace
 
-extern "C" int biu_from_nchw_u8(const uint8_t* src, float scale, const biu_act* dst, int dtype, biu_stream stream) {
-    BIU_REQUIRE(src && valid_act(dst), BIU_ERR_SHAPE, "from_nchw_u8: bad arguments");
+extern "C" int biu_from_nchw_u8(const uint8_t* src, float divisor, const biu_act* dst, int dtype, biu_stream stream) {
+    BIU_REQUIRE(src && valid_act(dst) && divisor > 0.f, BIU_ERR_SHAPE, "from_nchw_u8: bad arguments");
     BIU_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(k_from_nchw_u8<T>, dim3(grid_for(nvox(dst) * dst->c, TPB, 16384)), dim3(TPB), 0,
-                                                 (hipStream_t)stream, src, scale, dact(dst)));
+                                                 (hipStream_t)stream, src, divisor, dact(dst)));
     BIU_CHECK_LAUNCH("from_nchw_u8");
     return BIU_OK;
 }
-extern "C" int biu_u8_to_f32(const uint8_t* src, float scale, float* dst, long long n, biu_stream stream) {
-    BIU_REQUIRE(src && dst && n > 0, BIU_ERR_SHAPE, "u8_to_f32: bad arguments");
-    hipLaunchKernelGGL(k_u8_to_f32, dim3(grid_for(n, TPB, 8192)), dim3(TPB), 0, (hipStream_t)stream, src, scale, dst, (i64)n);
+extern "C" int biu_u8_to_f32(const uint8_t* src, float divisor, float* dst, long long n, biu_stream stream) {
+    BIU_REQUIRE(src && dst && n > 0 && divisor > 0.f, BIU_ERR_SHAPE, "u8_to_f32: bad arguments");
+    hipLaunchKernelGGL(k_u8_to_f32, dim3(grid_for(n, TPB, 8192)), dim3(TPB), 0, (hipStream_t)stream, src, divisor, dst, (i64)n);
     BIU_CHECK_LAUNCH("u8_to_f32");
     return BIU_OK;
 }

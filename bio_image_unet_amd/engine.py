@@ -1195,10 +1195,10 @@ class Engine:
         for act, x in zip(self.inputs, xs):
             x = x.detach()
             if x.dtype == torch.uint8:
-                # the reference's data contract: uint8 tiles scaled by 1/255 (unet/data.py:253-266, unet/predict.py:192-196);
-                # the scaling rides in the layout kernel, the batch crossed PCIe as bytes
+                # the reference's data contract: uint8 tiles divided by 255 (unet/data.py:253-266, unet/predict.py:192-196), the
+                # correctly rounded fp32 quotient; the division rides in the layout kernel, the batch crossed PCIe as bytes
                 x = x.contiguous()
-                check(lib.biu_from_nchw_u8(_ptr(x), 1.0 / 255.0, act.a(), self.dtype, st), "from_nchw_u8")
+                check(lib.biu_from_nchw_u8(_ptr(x), 255.0, act.a(), self.dtype, st), "from_nchw_u8")
                 continue
             if x.dtype != torch.float32:
                 x = x.float()

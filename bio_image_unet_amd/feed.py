@@ -11,7 +11,7 @@ flat uint8 file per field, mapped into memory:
   trip is exact).
 * ``DeviceFeeder`` -- what the Trainers iterate when handed a ``TileStore``: a background thread gathers the next batches out of
   the page cache into pinned buffers, a side HIP stream copies them to the device as BYTES (a quarter of the float32 traffic over
-  PCIe) while the current step computes, and the batch reaches the network as uint8 -- the 1/255 scaling rides in the input-layout
+  PCIe) while the current step computes, and the batch reaches the network as uint8 -- the division by 255 rides in the input-layout
   kernel (``biu_from_nchw_u8``), targets are widened by ``biu_u8_to_f32``.
 
 TIFF decoding and tiling stay out of scope (``DataProcess``): they run once, offline, and their output is what this store holds.
@@ -266,12 +266,13 @@ class DeviceFeeder:
             th.join()
 
 
-def u8_to_float(t: torch.Tensor, scale: float = 1.0 / 255.0) -> torch.Tensor:
-    """uint8 device tensor -> float32 * scale through ``biu_u8_to_f32`` (targets of the fused losses)."""
+def u8_to_float(t: torch.Tensor, divisor: float = 255.0) -> torch.Tensor:
+    """uint8 device tensor -> float32 / divisor through ``biu_u8_to_f32`` (targets of the fused losses): the correctly rounded quotient,
+    the value ``TileStore.__getitem__`` and the augmentation kernels give for the same byte."""
     import ctypes as C
     from ._lib import check, lib
     t = t.contiguous()
     out = torch.empty(t.shape, dtype=torch.float32, device=t.device)
-    check(lib.biu_u8_to_f32(C.c_void_p(t.data_ptr()), float(scale), C.c_void_p(out.data_ptr()), t.numel(),
+    check(lib.biu_u8_to_f32(C.c_void_p(t.data_ptr()), float(divisor), C.c_void_p(out.data_ptr()), t.numel(),
                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "u8_to_f32")
     return out

@@ -699,7 +699,7 @@ class Predict2D:
         return patches
 
     def _predict_and_stitch(self, patches, batch_size):
-        """uint8 patches up (scaled by 1/255 in the input-layout kernel), eval-mode forward in batches, ``(p * 255)`` truncated to
+        """uint8 patches up (divided by 255 in the input-layout kernel), eval-mode forward in batches, ``(p * 255)`` truncated to
         uint8 and added into the stitched image on the device; nan-mean of the overlapping uint8 tiles followed by the uint8
         cast == floor(sum / count) (``unet/predict.py:184-229``).  One download per stack."""
         n_img, h, w = self.imgs_shape

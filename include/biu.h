@@ -510,9 +510,12 @@ int biu_gate_bwd(const biu_act* e, const biu_xform* xe, const biu_act* psi, cons
 
 /* ------------------------------------------------------------------------------------------------
  * Data formats either side of the network, kept on the device
- *   biu_from_nchw_u8 : uint8 NC[D]HW batch * scale -> channels-last activation; replaces `batch / 255` + `.to(device)` of float32
- *                      (unet/data.py:253-266 items, unet/predict.py:192-196 patches): a quarter of the H2D bytes, no float copy
- *   biu_u8_to_f32    : uint8 * scale -> fp32 (targets: masks are stored 0 / 255)
+ *   biu_from_nchw_u8 : uint8 NC[D]HW batch / divisor -> channels-last activation; replaces `batch / 255` + `.to(device)` of float32
+ *                      (unet/data.py:253-266 items, unet/predict.py:192-196 patches): a quarter of the H2D bytes, no float copy.
+ *                      The fp32 value is the correctly rounded quotient (float)byte / divisor, `tile.astype('float32') / 255` bit for
+ *                      bit -- the value the augmentation kernels and TileStore.__getitem__ give too; byte * (1/255) is not (126 codes
+ *                      differ in the last bit).  bf16 storage rounds that quotient to nearest even.  divisor > 0.
+ *   biu_u8_to_f32    : uint8 / divisor -> fp32, the same quotient (targets: masks are stored 0 / 255, and 255 / 255 is exactly 1)
  *   biu_quantize_u8  : (p * scale) truncated to uint8 -- `(res * 255).astype('uint8')`, unet/predict.py:200
  *   biu_stitch_add   : one patch [channels, pd, ph, pw] (uint8 or fp32) times an optional weight [pd, ph, pw] added into (set != 0:
  *                      written over) acc [channels, D, H, W] / wsum [D, H, W] at origin (z0, y0, x0); 2-D: D = pd = 1
@@ -520,8 +523,8 @@ int biu_gate_bwd(const biu_act* e, const biu_xform* xe, const biu_act* psi, cons
  *                      floor(sum_layers acc / sum_layers wsum) as uint8 (the nan-mean of overlapping uint8 tiles cast to uint8,
  *                      unet/predict.py:204-229; `layers` = 3 reproduces unet3d/predict.py:173-195)
  * ---------------------------------------------------------------------------------------------- */
-int biu_from_nchw_u8(const uint8_t* src, float scale, const biu_act* dst, int dtype, biu_stream stream);
-int biu_u8_to_f32(const uint8_t* src, float scale, float* dst, long long n, biu_stream stream);
+int biu_from_nchw_u8(const uint8_t* src, float divisor, const biu_act* dst, int dtype, biu_stream stream);
+int biu_u8_to_f32(const uint8_t* src, float divisor, float* dst, long long n, biu_stream stream);
 int biu_quantize_u8(const float* src, float scale, uint8_t* dst, long long n, biu_stream stream);
 int biu_stitch_add(const void* patch, int patch_is_u8, const float* weight, int channels, int pd, int ph, int pw, float* acc, float* wsum,
                    int D, int H, int W, int z0, int y0, int x0, int set, biu_stream stream);

@@ -1401,3 +1401,85 @@ def test_conv_split_workspace_is_the_callers(nd, n, cin, cout, sp):
     yy = yref.transpose(0, 1).flatten(1).double()
     torch.testing.assert_close(st_[:, 0], yy.sum(1), rtol=1e-4, atol=1e-3)
     torch.testing.assert_close(st_[:, 1], (yy * yy).sum(1), rtol=1e-4, atol=1e-3)
+
+
+def _canaries_intact(dev):
+    """A padded Dev is NaN outside its channel slice; a kernel that writes past the slice overwrites that."""
+    out = torch.cat([dev.buf[..., :dev.c0], dev.buf[..., dev.c0 + dev.c:]], dim=-1)
+    return out.numel() > 0 and bool(torch.isnan(out).all())
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_gate_and_add_relu_off_the_model_shapes(dtype):
+    """biu_add_relu_fwd/bwd and biu_gate_fwd/bwd (AttentionUnet's gate, unet/attention_unet.py:177-179) away from the model's channel counts,
+    against float64 autograd of relu(a + b) and skip * sigmoid(psi) on the stored operands: sums planted at exactly 0, the gate's 64-lane
+    channel loop at and across its boundary, consumer transforms, de = NULL, accumulate 0 and 1, padded buffers with canaries."""
+    code = DT[dtype][1]
+    # ---- add_relu: identity transforms with sums planted at exactly 0 (b = -a as stored), then consumer transforms on both operands
+    shape = (2, 5, 1, 3, 7)
+    for planted in (True, False):
+        a = Dev(rnd(*shape, seed=1), dtype=dtype, pitch=8, c0=2)
+        b0 = rnd(*shape, seed=2)
+        zero = torch.zeros(shape, dtype=torch.bool)
+        if planted:
+            zero.view(-1)[::3] = True
+            b0 = torch.where(zero, -a.ref(), b0)                     # the stored a, negated: exact in either dtype
+        b = Dev(b0, dtype=dtype, pitch=6, c0=1)
+        xa, xb = (XF(5, identity=True), XF(5, identity=True)) if planted else (XF(5, seed=3), XF(5, seed=4))
+        ta, tb = xa.apply(a.ref().double()).requires_grad_(True), xb.apply(b.ref().double()).requires_grad_(True)
+        s = ta + tb
+        if planted:
+            assert bool((s[zero] == 0).all()) and int(zero.sum()) > 60
+        ref = torch.relu(s)
+        out = Dev(shape=shape, dtype=dtype, pitch=9, c0=3)
+        check(lib.biu_add_relu_fwd(a.a(), xa.x(), b.a(), xb.x(), out.a(), code, stream()), "add_relu_fwd")
+        assert_close(out.get(), ref.detach().float(), dtype, "add_relu_fwd")
+        assert _canaries_intact(out)
+        if planted:
+            assert bool((out.get()[zero] == 0).all())
+        g = Dev(rnd(*shape, seed=5), dtype=dtype, pitch=7, c0=1)
+        # the backward reads the STORED output (nn.ReLU(inplace=True)): the reference masks with it
+        want = torch.where(out.ref() > 0, g.ref(), torch.zeros(shape))
+        # ... and float64 autograd of relu(a + b) agrees with it wherever the float64 sum is not within rounding of 0 (the kernel forms the
+        # transforms and the sum in fp32: 2^-20 of the operands' magnitude covers their roundings; the planted sums are exact zeros and stay in)
+        ref.backward(g.ref().double())
+        clear = (s.detach().abs() > 2.0 ** -20 * (ta.detach().abs() + tb.detach().abs())) | (zero & (s.detach() == 0))
+        assert float(clear.double().mean()) > 0.99
+        assert torch.equal(want.double()[clear], ta.grad[clear]) and torch.equal(ta.grad, tb.grad)
+        for accumulate in (0, 1):
+            base_a, base_b = rnd(*shape, seed=6), rnd(*shape, seed=7)
+            da, db = Dev(base_a, dtype=dtype, pitch=8, c0=2), Dev(base_b, dtype=dtype, pitch=6, c0=0)
+            wa, wb = (da.ref() + want, db.ref() + want) if accumulate else (want, want)
+            check(lib.biu_add_relu_bwd(out.a(), g.a(), da.a(), db.a(), accumulate, code, stream()), "add_relu_bwd")
+            assert_close(da.get(), wa, dtype, f"add_relu_bwd da acc={accumulate}")
+            assert_close(db.get(), wb, dtype, f"add_relu_bwd db acc={accumulate}")
+            assert _canaries_intact(da) and _canaries_intact(db)
+            if planted and not accumulate:
+                assert bool((da.get()[zero] == 0).all()) and bool((db.get()[zero] == 0).all())
+    # ---- gate: C at and across the 64-lane channel loop's boundary
+    for c in (1, 5, 64, 65, 130):
+        shape, pshape = (2, c, 1, 3, 5), (2, 1, 1, 3, 5)
+        e = Dev(rnd(*shape, seed=10 + c), dtype=dtype, pitch=c + 3, c0=1)
+        psi = Dev(rnd(*pshape, seed=11 + c) * 2, dtype=dtype, pitch=3, c0=1)
+        xe, xp = XF(c, seed=12), XF(1, seed=13)
+        te, tp = xe.apply(e.ref().double()).requires_grad_(True), xp.apply(psi.ref().double()).requires_grad_(True)
+        ref = te * torch.sigmoid(tp)
+        out = Dev(shape=shape, dtype=dtype, pitch=c + 2, c0=2)
+        check(lib.biu_gate_fwd(e.a(), xe.x(), psi.a(), xp.x(), out.a(), code, stream()), "gate_fwd")
+        assert_close(out.get(), ref.detach().float(), dtype, f"gate_fwd C={c}")
+        assert _canaries_intact(out)
+        g = Dev(rnd(*shape, seed=14 + c), dtype=dtype, pitch=c + 1, c0=0)
+        ref.backward(g.ref().double())
+        for accumulate in (0, 1):
+            base = rnd(*shape, seed=15 + c)
+            de = Dev(base, dtype=dtype, pitch=c + 4, c0=3)
+            dpsi = Dev(shape=pshape, dtype=dtype, pitch=2, c0=1)
+            want_e = (de.ref().double() + te.grad if accumulate else te.grad).float()
+            check(lib.biu_gate_bwd(e.a(), xe.x(), psi.a(), xp.x(), g.a(), de.a(), accumulate, dpsi.a(), code, stream()), "gate_bwd")
+            assert_close(de.get(), want_e, dtype, f"gate_bwd de C={c} acc={accumulate}")
+            assert_close(dpsi.get(), tp.grad.float(), dtype, f"gate_bwd dpsi C={c} acc={accumulate}")
+            assert _canaries_intact(de) and _canaries_intact(dpsi)
+        dpsi = Dev(shape=pshape, dtype=dtype, pitch=2, c0=1)
+        check(lib.biu_gate_bwd(e.a(), xe.x(), psi.a(), xp.x(), g.a(), None, 0, dpsi.a(), code, stream()), "gate_bwd de=NULL")
+        assert_close(dpsi.get(), tp.grad.float(), dtype, f"gate_bwd dpsi C={c} de=NULL")
+        assert _canaries_intact(dpsi)

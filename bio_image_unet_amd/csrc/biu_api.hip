@@ -7,12 +7,12 @@
 #include <stdlib.h>
 #include <string.h>
 
-// Every token BIU_DISABLE takes: INTEGRATION.md's table (sidechain, prepack and capturefork are read by engine.py alone)
+// Every token BIU_DISABLE takes: INTEGRATION.md's table (sidechain, prepack, capturefork and headrank1 are read by the Python side alone)
 static const char* const kOffTokens[] = {
     "conv_fwd", "conv_dgrad", "conv_wgrad", "convt_fwd", "convt_dgrad", "convt_wgrad", "convt_all", "c1", "c1_mfma", "cat",
     "fused_stats", "wgrad_bn", "dgrad_bnred", "pool_pair", "pool_pipe", "pool_bnred", "head_bnred", "ksplit", "m16", "m16x2", "rr16",
     "wroll", "wroll16", "wroll2d", "upconv", "foldt", "foldall", "foldck8", "foldgemm", "croll", "froll", "prepack", "wsplitbn",
-    "capturefork", "sidechain",
+    "capturefork", "sidechain", "headrank1",
 };
 constexpr int kNumOffTokens = sizeof(kOffTokens) / sizeof(kOffTokens[0]);
 static_assert(kNumOffTokens <= 64, "BiuEnv::off holds one bit per token");
@@ -321,6 +321,31 @@ extern "C" int biu_conv_bwd_weight_bn(const biu_act* x, const biu_xform* xf, con
     int rc = biu_bn_bwd_apply(da, y, scale, shift, slope, coefA, coefB, coefC, da, dtype, stream);
     if (rc != BIU_OK) return rc;
     return biu_conv_bwd_weight(x, xf, da, kd, kh, kw, dilation, dw, nullptr, ws, ws_bytes, dtype, stream);
+}
+
+// Weight gradient of the block in front of a one-channel 1x1 head whose backward did not store its data gradient (biu_head_bwd_bnred with
+// dx = NULL): da[v][c] = bf16(dlogits[v] * w_head[c]) is rebuilt in the kernel's loader.  `dy` is only written.
+static bool rank1_y_ok(const biu_act* y, int dtype) {
+    const size_t es = dsize(dtype);
+    return ((uintptr_t)y->p % 16) == 0 && ((size_t)y->pitch * es) % 16 == 0 && (i64)y->d * y->h * y->w * y->pitch * (i64)es < (1LL << 32) - 65536;
+}
+extern "C" int biu_conv_bwd_weight_bn_rank1_ok(const biu_act* x, const biu_act* dy, const biu_act* y, int head_cout, int kd, int kh, int kw,
+                                               int dilation, int dtype) {
+    if (!x || !dy || !y || !conv_args_ok(x, dy, kd, kh, kw, dilation) || !valid_act(y) || !same_space(y, dy) || y->c != dy->c) return 0;
+    if (head_cout != 1 || biu_off("conv_wgrad") || biu_off("wgrad_bn") || !rank1_y_ok(y, dtype)) return 0;
+    return biu_mfma_wgrad_rank1_ok(x, dy, kd, kh, kw, dilation, dtype) ? 1 : 0;
+}
+extern "C" int biu_conv_bwd_weight_bn_rank1(const biu_act* x, const biu_xform* xf, const float* dlogits, const float* w_head, int head_cout,
+                                            const biu_act* dy, const biu_act* y, const float* scale, const float* shift, const float* slope,
+                                            const float* coefA, const float* coefB, const float* coefC, int kd, int kh, int kw, int dilation,
+                                            float* dw, void* ws, size_t ws_bytes, int dtype, biu_stream stream) {
+    BIU_REQUIRE(biu_conv_bwd_weight_bn_rank1_ok(x, dy, y, head_cout, kd, kh, kw, dilation, dtype), BIU_ERR_UNSUPPORTED,
+                "conv_bwd_weight_bn_rank1: shapes not served by the rank-one loader (ask biu_conv_bwd_weight_bn_rank1_ok)");
+    BIU_REQUIRE(dlogits && w_head && dw && scale && shift && coefA && coefB && coefC, BIU_ERR_SHAPE, "conv_bwd_weight_bn_rank1: null pointer");
+    BIU_REQUIRE(ws && ws_bytes >= biu_mfma_wgrad_workspace(x->c, dy->c, kd, kh, kw, dtype), BIU_ERR_WORKSPACE,
+                "conv_bwd_weight_bn_rank1: workspace too small");
+    BnBwdFuse bn{y, scale, shift, slope, coefA, coefB, coefC, dlogits, w_head};
+    return biu_mfma_wgrad(x, xf, dy, kd, kh, kw, dw, nullptr, ws, ws_bytes, dtype, (hipStream_t)stream, &bn);
 }
 
 // ---- conv block on a channel concatenation (x0 | x1) held in two buffers ------------------------------------------------

@@ -2630,6 +2630,10 @@ struct WgradArgs {
     int ypitch;
     const float* bn_scale; const float* bn_shift; const float* bn_slope;
     const float* bn_cA; const float* bn_cB; const float* bn_cC;
+    // k_wgrad_roll<true, false, true, true> ("rank one"): da is not read but rebuilt in the loader as bf16(dl[v] * r1_w[c]) from the fp32
+    // gradient of a one-channel 1x1 head (dl: [N][1][D][H][W]) and its 16 weights -- what the head's backward would have stored; pa is
+    // only written (dy)
+    const float* r1_dl = nullptr; const float* r1_w = nullptr;
     // ConvTranspose launches (S == 2: the tapped tile holds every fine voxel of the brick exactly once): per-channel sums of the tapped
     // operand (= d bias), accumulated while its pieces are committed to LDS, by the blocks of the first plain-operand tile; zeroed by the host
     float* dbias_out;
@@ -3420,7 +3424,7 @@ constexpr int WR_BV = WR_TD * WR_TH * WR_TW;                                    
 constexpr int WR_AB = WR_BV * WR_RS;                                            // 16 KiB
 constexpr int WR_NAI = WR_AB / 1024;                                            // 16
 constexpr int WR_NABUF = 3;
-constexpr size_t WR_LDS = (size_t)WR_NPAIR * WR_PAIRB + WR_NABUF * WR_AB + 9 * 32 * sizeof(float);
+constexpr size_t WR_LDS = (size_t)WR_NPAIR * WR_PAIRB + WR_NABUF * WR_AB + 10 * 32 * sizeof(float);
 
 // A wave-uniform value the optimiser must not see through: keeps per-step offsets (plane * bytes, ring pair * bytes) out of strength
 // reduction / loop-invariant hoisting, which turned every (piece, step parity, ring slot) combination into a live VGPR and spilled.
@@ -3437,9 +3441,13 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // MFMA's result belong to plane 0 and rows 16-31 to plane 1: against halo plane j of the tapped operand that is depth tap kd = j for the upper
 // half and kd = j - 1 for the lower one.  Four halo planes x 9 (kh, kw) = 36 accumulators cover all 27 taps of both planes with 288 MFMAs per
 // step instead of 432; unit (j, kw): waves 0-3 own (w, 0) and (w, 2), waves 4-7 own (w - 4, 1) -- 72 MFMAs per SIMD and step.
-template <bool BNF, bool K2D, bool A16 = false>
+// R1 (with BNF and A16): the plain operand da is the rank-one product of a one-channel head's gradient and its weights; the loader fetches
+// dl[v] (4 bytes, still ONE vector-memory instruction per piece: the counted waits hold) and rebuilds da[v][c] = bf16(dl[v] * w[c]) with the
+// head backward's own product and rounding, so dy and dW are what the two-call sequence gives.
+template <bool BNF, bool K2D, bool A16 = false, bool R1 = false>
 __global__ __launch_bounds__(512, 2) void k_wgrad_roll(WgradArgs a) {
     static_assert(!(K2D && A16), "the 16-channel plain operand form exists for volumes only");
+    static_assert(!R1 || (BNF && A16), "the rank-one loader belongs to the fused 16-channel form");
     using T = bf16_t;
     using F = Frag<T>;
     constexpr int TD = WR_TD, TH = WR_TH, TW = WR_TW, HW = WR_HW, PL = WR_PL, RS = WR_RS, PLB = WR_PLB, PAIRB = WR_PAIRB;
@@ -3450,8 +3458,8 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_roll(WgradArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint4 lds[];
     char* bring = (char*)lds;                          // [4][PAIRB]: pair p holds the halo planes gp with ((gp + 1) / 2) % 4 == p
     char* abuf = bring + WR_NPAIR * PAIRB;             // [3][WR_AB]: plain-operand tile of step s in buffer s % 3, rows [voxel][32 ch]
-    float* lxf = (float*)(abuf + WR_NABUF * WR_AB);    // [3][CT] transform of B, [6][CT] BatchNorm backward of A
-    constexpr int LB = 0, LBN = 3 * CT;
+    float* lxf = (float*)(abuf + WR_NABUF * WR_AB);    // [3][CT] transform of B, [6][CT] BatchNorm backward of A, [CT] head weights (R1)
+    constexpr int LB = 0, LBN = 3 * CT, LR1 = 9 * CT;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -3488,6 +3496,9 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_roll(WgradArgs a) {
         lxf[LB + 2 * CT + tid] = (b_xf && cb < a.CB) ? bl_[cbl] : 1.f;
     }
 
+    if constexpr (R1) {
+        if (tid < CT) lxf[LR1 + tid] = (it * CT + tid < a.CA) ? a.r1_w[it * CT + tid] : 0.f;
+    }
     floatx16 acc[NACC];
 #pragma unroll
     for (int t = 0; t < NACC; ++t)
@@ -3530,15 +3541,15 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_roll(WgradArgs a) {
     // column state
     int cn = 0, ch0 = 0, cw0 = 0;
     v4u_t rsB, rsA;
-    __amdgpu_buffer_rsrc_t rsAr, rsYr;
+    __amdgpu_buffer_rsrc_t rsAr, rsYr, rsLr;
     // two fetches are in flight at any time (steps s + 1 and s + 2): the fetch of step k keeps its masks / staging registers in slot k & 1
     struct Slot { unsigned bmask, amask; uint4 pa[BNF ? NAK : 1], pyv[BNF ? NAK : 1]; };
     Slot sl0, sl1;
     sl0.bmask = sl0.amask = sl1.bmask = sl1.amask = 0;
     // per column and piece: byte offset of the piece at plane 0 of its kind (tapped: halo plane gp = 0; plain: d = 0) inside the sample, or
     // 0xffffffff when the piece lies outside the volume in (H, W) / has no channels -- a fetch then only adds plane * (bytes per plane)
-    unsigned bbase[NBK], abase_[NAK], ybase_[BNF ? NAK : 1];
-    unsigned planeB = 0, planeA = 0, planeY = 0;
+    unsigned bbase[NBK], abase_[NAK], ybase_[BNF ? NAK : 1], lbase_[R1 ? NAK : 1];
+    unsigned planeB = 0, planeA = 0, planeY = 0, planeL = 0;
     auto set_column = [&](int col) __attribute__((always_inline)) {
         int c = col;
         const int wb_ = c % a.nbw; c /= a.nbw;
@@ -3550,6 +3561,11 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_roll(WgradArgs a) {
         rsAr = __builtin_amdgcn_make_buffer_rsrc((void*)(a.pa + (size_t)cn * sampA), 0, (int)(unsigned)sampA, 0x00020000);
         rsYr = __builtin_amdgcn_make_buffer_rsrc((void*)(a.py + (size_t)cn * sampY), 0, bn_fused ? (int)(unsigned)sampY : 0, 0x00020000);
         planeB = (unsigned)(a.BH * a.BW) * rowB; planeA = (unsigned)(a.GH * a.GW) * rowA; planeY = (unsigned)(a.GH * a.GW) * rowY;
+        if constexpr (R1) {
+            const size_t sampL = (size_t)a.GD * a.GH * a.GW * 4;
+            rsLr = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.r1_dl + (size_t)cn * sampL), 0, (int)(unsigned)sampL, 0x00020000);
+            planeL = (unsigned)(a.GH * a.GW) * 4u;
+        }
 #pragma unroll
         for (int k = 0; k < NBK; ++k) {
             const unsigned x = bco[k];
@@ -3565,13 +3581,14 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_roll(WgradArgs a) {
             const unsigned vox = (unsigned)(gh * a.GW + gw);
             abase_[k] = ok ? vox * rowA + (unsigned)ac0 * 2u + (x & 1023u) * planeA : 0xffffffffu;
             if constexpr (BNF) ybase_[k] = ok ? vox * rowY + (unsigned)ac0 * 2u + (x & 1023u) * planeY : 0xffffffffu;
+            if constexpr (R1) lbase_[k] = ok ? vox * 4u + (x & 1023u) * planeL : 0xffffffffu;
         }
     };
     // A fetch = NBK pieces of the tapped operand (halo planes gp0, gp0 + 1 -> ring pair `pair`) + NAK pieces of the plain operand (planes
     // d0, d0 + 1 -> A buffer `buf` by LDS-DMA, or -- fused BatchNorm backward -- (da, y) into the slot's registers).  Piece by piece, so that
     // a step can spread them over its MFMA rows: issued back to back at the head of the step the 5 DMA instructions of each of the 8 waves
     // took ~1000 cycles during which no wave multiplied (in-kernel stamps, profiles/r03_wgrad_roll.md).
-    struct FetchCtx { int pair, buf; bool bd0, bd1, ad0, ad1; unsigned dofB, dofA, dofY; };
+    struct FetchCtx { int pair, buf; bool bd0, bd1, ad0, ad1; unsigned dofB, dofA, dofY, dofL; };
     auto fetch_ctx = [&](int pair, int gp0, int buf, int d0) __attribute__((always_inline)) -> FetchCtx {
         FetchCtx f;
         f.pair = pair; f.buf = buf;
@@ -3579,6 +3596,7 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_roll(WgradArgs a) {
         f.ad0 = d0 < a.GD; f.ad1 = d0 + 1 < a.GD;
         f.dofB = opaque_s((unsigned)gp0 * planeB);            // (mod 2^32: gp0 = -1 pairs with plane index 1 or an invalid plane)
         f.dofA = opaque_s((unsigned)d0 * planeA); f.dofY = opaque_s((unsigned)d0 * planeY);
+        if constexpr (R1) f.dofL = opaque_s((unsigned)d0 * planeL); else f.dofL = 0;
         f.pair = (int)opaque_s((unsigned)pair); f.buf = (int)opaque_s((unsigned)buf);
         return f;
     };
@@ -3592,9 +3610,13 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_roll(WgradArgs a) {
             const int k = i - NBK;
             const bool ok = abase_[k] != 0xffffffffu && ((aco[k] & 1u) ? f.ad1 : f.ad0);
             if constexpr (BNF) {
-                const auto v0 = __builtin_amdgcn_raw_buffer_load_b128(rsAr, ok ? (int)(abase_[k] + f.dofA) : -1, 0, 0);
+                if constexpr (R1) {
+                    sl.pa[k].x = __builtin_amdgcn_raw_buffer_load_b32(rsLr, ok ? (int)(lbase_[k] + f.dofL) : -1, 0, 0);      // dl[v]
+                } else {
+                    const auto v0 = __builtin_amdgcn_raw_buffer_load_b128(rsAr, ok ? (int)(abase_[k] + f.dofA) : -1, 0, 0);
+                    sl.pa[k] = make_uint4(v0[0], v0[1], v0[2], v0[3]);
+                }
                 const auto v1 = __builtin_amdgcn_raw_buffer_load_b128(rsYr, ok ? (int)(ybase_[k] + f.dofY) : -1, 0, 0);
-                sl.pa[k] = make_uint4(v0[0], v0[1], v0[2], v0[3]);
                 sl.pyv[k] = make_uint4(v1[0], v1[1], v1[2], v1[3]);
             } else {
                 bload_lds16(ok ? abase_[k] + f.dofA : 0xffffffffu, rsA, lds0 + (unsigned)(WR_NPAIR * PAIRB + f.buf * WR_AB + (wave + 8 * k) * 1024));
@@ -3636,7 +3658,13 @@ __global__ __launch_bounds__(512, 2) void k_wgrad_roll(WgradArgs a) {
                 for (int k = 0; k < NAK; ++k) {
                     if ((sl.amask >> k) & 1u) {
                         float g[PE], yy[PE];
-                        F::unpack(sl.pa[k], g);
+                        if constexpr (R1) {                  // da[v][c] as k_head_bwd_fused stores it: the fp32 product, rounded to the storage type
+                            const float dlv = __uint_as_float(sl.pa[k].x);
+#pragma unroll
+                            for (int e = 0; e < PE; ++e) g[e] = (float)(T)fmaf(dlv, lxf[LR1 + apc * PE + e], 0.f);
+                        } else {
+                            F::unpack(sl.pa[k], g);
+                        }
                         F::unpack(sl.pyv[k], yy);
 #pragma unroll
                         for (int e = 0; e < PE; ++e) g[e] *= (fmaf(ks[e], yy[e], kh[e]) > 0.f ? 1.f : kl[e]);
@@ -3899,6 +3927,7 @@ static bool wroll2d_fits(const WgradArgs& a, i64 bytesA, i64 bytesB, i64 bytesY)
 static int launch_wgrad_roll(WgradArgs a, hipStream_t st, bool k2d = false) {
     if (k2d) { a.GD = a.BD = a.N; a.N = 1; }
     const bool a16 = !k2d && a.CA == 16 && !biu_off("wroll16");      // 16-channel plain operand: both planes of a step share the tile's 32 rows
+    if (a.r1_dl && !(a16 && a.py)) return biu_fail(BIU_ERR_UNSUPPORTED, "wgrad_roll: the rank-one loader exists for the fused 16-channel form only");
     a.nbd = 1;
     a.nbh = (a.GH + WR_TH - 1) / WR_TH;
     a.nbw = (a.GW + WR_TW - 1) / WR_TW;
@@ -3919,7 +3948,8 @@ static int launch_wgrad_roll(WgradArgs a, hipStream_t st, bool k2d = false) {
             hipFuncSetAttribute((const void*)k_wgrad_roll<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WR_LDS) != hipSuccess ||
             hipFuncSetAttribute((const void*)k_wgrad_roll<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WR_LDS) != hipSuccess ||
             hipFuncSetAttribute((const void*)k_wgrad_roll<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WR_LDS) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_wgrad_roll<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WR_LDS) != hipSuccess)
+            hipFuncSetAttribute((const void*)k_wgrad_roll<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WR_LDS) != hipSuccess ||
+            hipFuncSetAttribute((const void*)k_wgrad_roll<true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WR_LDS) != hipSuccess)
             return biu_fail(BIU_ERR_LAUNCH, "wgrad_roll: cannot reserve %zu bytes of LDS", WR_LDS);
         attr_set = true;
     }
@@ -3936,7 +3966,8 @@ static int launch_wgrad_roll(WgradArgs a, hipStream_t st, bool k2d = false) {
             if (with_bn) hipLaunchKernelGGL((k_wgrad_roll<true, true>), dim3(g, pairs), dim3(512), WR_LDS, st, b);
             else hipLaunchKernelGGL((k_wgrad_roll<false, true>), dim3(g, pairs), dim3(512), WR_LDS, st, b);
         } else if (a16) {
-            if (with_bn) hipLaunchKernelGGL((k_wgrad_roll<true, false, true>), dim3(g, pairs), dim3(512), WR_LDS, st, b);
+            if (with_bn && b.r1_dl) hipLaunchKernelGGL((k_wgrad_roll<true, false, true, true>), dim3(g, pairs), dim3(512), WR_LDS, st, b);
+            else if (with_bn) hipLaunchKernelGGL((k_wgrad_roll<true, false, true>), dim3(g, pairs), dim3(512), WR_LDS, st, b);
             else hipLaunchKernelGGL((k_wgrad_roll<false, false, true>), dim3(g, pairs), dim3(512), WR_LDS, st, b);
         } else {
             if (with_bn) hipLaunchKernelGGL((k_wgrad_roll<true, false>), dim3(g, pairs), dim3(512), WR_LDS, st, b);
@@ -4076,6 +4107,18 @@ static int wgrad_xf(const biu_xform* xf, const float** s, const float** b, const
     return BIU_OK;
 }
 
+// Does the fused weight gradient of (x, dy) run as k_wgrad_roll's 16-channel form -- the one whose loader can rebuild da from a one-channel
+// head's gradient?  The conditions biu_mfma_wgrad dispatches on (BIU_ROLL=always waives the size rule, as for the rolling convolution).
+bool biu_mfma_wgrad_rank1_ok(const biu_act* x, const biu_act* dy, int kd, int kh, int kw, int dilation, int dtype) {
+    if (dtype != BIU_BF16 || kd != 3 || dy->c != 16 || !biu_mfma_wgrad_ok(x, dy, kd, kh, kw, dilation, dtype)) return false;
+    if (biu_off("wroll") || biu_off("wroll16") || (x->c == 16 && !biu_off("rr16"))) return false;
+    if (!biu_off("wsplitbn") && x->c > 32 && nvox(dy) <= 4 * 32 * 32 * 32) return false;        // (that form runs the BatchNorm backward as a pass of its own)
+    if ((i64)x->d * x->h * x->w * 4 >= (1LL << 32)) return false;                                // dl of one sample behind a 32-bit buffer offset
+    WgradArgs a;
+    a.N = x->n; a.GD = x->d; a.GH = x->h; a.GW = x->w;
+    return biu_env().roll_always || wroll_fits(a);
+}
+
 int biu_mfma_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* dy, int kd, int kh, int kw, float* dw, float* dbias,
                    void* ws, size_t ws_bytes, int dtype, hipStream_t st, const BnBwdFuse* bn, const biu_act* x1, const biu_xform* xf1,
                    int dw_ld_cols, int dw_c_off) {
@@ -4093,6 +4136,7 @@ int biu_mfma_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* dy, int
         a.py = (const char*)bn->y->p; a.ypitch = bn->y->pitch;
         a.bn_scale = bn->scale; a.bn_shift = bn->shift; a.bn_slope = bn->slope;
         a.bn_cA = bn->cA; a.bn_cB = bn->cB; a.bn_cC = bn->cC;
+        a.r1_dl = bn->r1_dl; a.r1_w = bn->r1_w;
     } else {
         a.py = nullptr; a.ypitch = 0;
         a.bn_scale = a.bn_shift = a.bn_slope = a.bn_cA = a.bn_cB = a.bn_cC = nullptr;
@@ -4117,7 +4161,8 @@ int biu_mfma_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* dy, int
     const size_t need = wgrad_acc_bytes(a.CA, a.CB, taps);
     BIU_REQUIRE(ws_bytes >= need + (dbias ? biu_chan_sum_workspace(dy->c) : 0), BIU_ERR_WORKSPACE, "wgrad_mfma: workspace %zu too small", ws_bytes);
     if (int zr = zero_ws(ws, need, nullptr, 0, st)) return zr;
-    if (dtype == BIU_BF16 && kd == 3 && a.CB == 16 && !x1 && !biu_off("rr16")) rc = launch_wgrad<bf16_t, 3, 3, 1, 4, 8, 16, 1, 1, true>(a, st);   // paired taps
+    if (a.r1_dl) rc = launch_wgrad_roll(a, st);                 // (the caller asked biu_mfma_wgrad_rank1_ok)
+    else if (dtype == BIU_BF16 && kd == 3 && a.CB == 16 && !x1 && !biu_off("rr16")) rc = launch_wgrad<bf16_t, 3, 3, 1, 4, 8, 16, 1, 1, true>(a, st);   // paired taps
     else if (dtype == BIU_BF16 && kd == 3 && !biu_off("wroll") && wroll_fits(a)) rc = launch_wgrad_roll(a, st);      // rolling window + LDS-DMA
     else if (dtype == BIU_BF16 && kd == 1 && !biu_off("wroll") && !biu_off("wroll2d") &&
              wroll2d_fits(a, (i64)nvox(dy) * dy->pitch * 2, (i64)nvox(x) * x->pitch * 2 > (x1 ? (i64)nvox(x1) * x1->pitch * 2 : 0) ? (i64)nvox(x) * x->pitch * 2 : (i64)nvox(x1) * x1->pitch * 2,

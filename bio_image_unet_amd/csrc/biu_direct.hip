@@ -1240,12 +1240,15 @@ extern "C" int biu_head_bwd_bnred(const biu_act* x, const biu_xform* xf, const f
                                   const biu_act* dx, float* dw, float* dbias, void* ws, size_t ws_bytes, const float* mean,
                                   const float* invstd, float* partial, size_t partial_floats, int* nblk, int dtype,
                                   biu_stream stream) {
-    BIU_REQUIRE(valid_act(x) && w && dlogits && dx && valid_act(dx) && same_space(x, dx) && dx->c == x->c && cout > 0 &&
+    BIU_REQUIRE(valid_act(x) && w && dlogits && (!dx || (valid_act(dx) && same_space(x, dx) && dx->c == x->c)) && cout > 0 &&
                     cout <= HEAD_MAX_COUT, BIU_ERR_SHAPE, "head_bwd_bnred: bad arguments");
     BIU_REQUIRE(xf && xf->scale && xf->shift && mean && invstd && partial && nblk, BIU_ERR_SHAPE, "head_bwd_bnred: null vector");
     BIU_REQUIRE(partial_floats >= (size_t)BIU_BN_MAX_PARTIALS * x->c * 2, BIU_ERR_WORKSPACE, "head_bwd_bnred: partial buffer too small");
     if (!biu_off("head_bnred") && biu_head_bwd_bnred_ok(x, dx, cout, dtype) && ws && ws_bytes >= biu_head_bwd_fused_workspace(x->c))
         return biu_head_bwd_bnred_fused(x, xf, w, cout, dlogits, dx, dw, dbias, ws, mean, invstd, partial, nblk, dtype, (hipStream_t)stream);
+    // dx = NULL (the caller rebuilds it where it is consumed: biu_conv_bwd_weight_bn_rank1): the fused kernel with its store compiled out;
+    // the sums are still taken from the value as the storage type would hold it
+    BIU_REQUIRE(dx, BIU_ERR_UNSUPPORTED, "head_bwd_bnred: dx = NULL needs the fused kernel (C <= 32, cout <= 2, 16-byte rows)");
     int rc = biu_head_bwd(x, xf, w, cout, dlogits, dx, dw, dbias, ws, ws_bytes, dtype, stream);
     if (rc != BIU_OK) return rc;
     return biu_bn_bwd_reduce(dx, x, xf->scale, xf->shift, xf->slope, mean, invstd, partial, nblk, dtype, stream);

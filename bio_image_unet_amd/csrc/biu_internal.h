@@ -81,7 +81,11 @@ bool biu_mfma_wgrad_ok(const biu_act* x, const biu_act* dy, int kd, int kh, int 
 struct BnBwdFuse {            // BatchNorm(+LeakyReLU) backward fused into the weight-gradient loader
     const biu_act* y;
     const float *scale, *shift, *slope, *cA, *cB, *cC;
+    // rank one: da is not read but rebuilt as bf16(r1_dl[v] * r1_w[c]) (a one-channel 1x1 head's gradient and weights); see biu_mfma_wgrad_rank1_ok
+    const float* r1_dl = nullptr;
+    const float* r1_w = nullptr;
 };
+bool biu_mfma_wgrad_rank1_ok(const biu_act* x, const biu_act* dy, int kd, int kh, int kw, int dilation, int dtype);
 int biu_mfma_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* dy, int kd, int kh, int kw, float* dw,
                    float* dbias, void* ws, size_t ws_bytes, int dtype, hipStream_t st, const BnBwdFuse* bn = nullptr,
                    const biu_act* x1 = nullptr, const biu_xform* xf1 = nullptr, int dw_ld_cols = 0, int dw_c_off = 0);

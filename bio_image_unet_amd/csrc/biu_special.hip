@@ -539,7 +539,8 @@ int biu_chan_sum_vec(const biu_act* a, float* out, void* ws, int dtype, hipStrea
 // =====================================================================================================================
 // RED: also the BatchNorm-backward sums (sum dz, sum dz * yhat) of the block that produced x, reduced from the dx values this
 //      kernel writes (the head is that tensor's only reader): bn_partial[block][C][2]
-template <typename T, int C, int O, bool RED>
+// STORE = false (RED only): dx is not written -- the caller rebuilds it where it is consumed; every sum is what the storing form gives
+template <typename T, int C, int O, bool RED, bool STORE = true>
 __global__ __launch_bounds__(TPB) void k_head_bwd_fused(DAct x, DXf xf, const float* __restrict__ w, int cout,
                                                         const float* __restrict__ dl, DAct dx, int want_dx,
                                                         float* __restrict__ partial /* [nblk][O*C + O] */,
@@ -579,7 +580,7 @@ __global__ __launch_bounds__(TPB) void k_head_bwd_fused(DAct x, DXf xf, const fl
             ab[o] += g[o];
         }
         const T* src = (const T*)x.p + v * x.pitch;
-        T* dst = want_dx ? (T*)dx.p + v * dx.pitch : nullptr;
+        T* dst = (STORE && want_dx) ? (T*)dx.p + v * dx.pitch : nullptr;
 #pragma unroll
         for (int c0 = 0; c0 < C; c0 += G) {
             Pack<T, G> in = *(const Pack<T, G>*)(src + c0);
@@ -603,7 +604,7 @@ __global__ __launch_bounds__(TPB) void k_head_bwd_fused(DAct x, DXf xf, const fl
                     r2[c] = fmaf(dz, yv, r2[c]);          // raw; centred below
                 }
             }
-            if (want_dx) *(Pack<T, G>*)(dst + c0) = od;
+            if (STORE && want_dx) *(Pack<T, G>*)(dst + c0) = od;
         }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -683,7 +684,10 @@ static int head_fused_t(const biu_act* x, const biu_xform* xf, const float* w, i
     const int O = cout == 3 ? 4 : cout;
     if (bn_partial) {
         if constexpr (C <= 32) {
-            if (O == 2) hipLaunchKernelGGL((k_head_bwd_fused<T, C, 2, true>), dim3(nblk), dim3(TPB), 0, st, dact(x), dxf(xf), w, cout, dl, dxa, 1, (float*)ws, mean, invstd, bn_partial);
+            if (!dx) {
+                if (O == 2) hipLaunchKernelGGL((k_head_bwd_fused<T, C, 2, true, false>), dim3(nblk), dim3(TPB), 0, st, dact(x), dxf(xf), w, cout, dl, dxa, 0, (float*)ws, mean, invstd, bn_partial);
+                else hipLaunchKernelGGL((k_head_bwd_fused<T, C, 1, true, false>), dim3(nblk), dim3(TPB), 0, st, dact(x), dxf(xf), w, cout, dl, dxa, 0, (float*)ws, mean, invstd, bn_partial);
+            } else if (O == 2) hipLaunchKernelGGL((k_head_bwd_fused<T, C, 2, true>), dim3(nblk), dim3(TPB), 0, st, dact(x), dxf(xf), w, cout, dl, dxa, 1, (float*)ws, mean, invstd, bn_partial);
             else hipLaunchKernelGGL((k_head_bwd_fused<T, C, 1, true>), dim3(nblk), dim3(TPB), 0, st, dact(x), dxf(xf), w, cout, dl, dxa, 1, (float*)ws, mean, invstd, bn_partial);
             *bn_nblk = nblk;
         }
@@ -699,9 +703,9 @@ static int head_fused_t(const biu_act* x, const biu_xform* xf, const float* w, i
     BIU_CHECK_LAUNCH("head_bwd_finalize");
     return BIU_OK;
 }
-// fused head backward + BatchNorm-backward sums of x's producer: C <= 32, cout <= 2, dx required; partial rows <= 1024
+// fused head backward + BatchNorm-backward sums of x's producer: C <= 32, cout <= 2; partial rows <= 1024.  dx = NULL: not stored.
 bool biu_head_bwd_bnred_ok(const biu_act* x, const biu_act* dx, int cout, int dtype) {
-    return dx && x->c <= 32 && cout <= 2 && biu_head_bwd_fused_ok(x, dx, cout, dtype);
+    return x->c <= 32 && cout <= 2 && biu_head_bwd_fused_ok(x, dx, cout, dtype);
 }
 int biu_head_bwd_bnred_fused(const biu_act* x, const biu_xform* xf, const float* w, int cout, const float* dl, const biu_act* dx, float* dw,
                              float* db, void* ws, const float* mean, const float* invstd, float* bn_partial, int* bn_nblk, int dtype,

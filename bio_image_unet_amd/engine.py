@@ -48,6 +48,7 @@ def _disabled(token: str, env: Optional[str] = None) -> bool:
 _NO_CAPTURE_FORK = _disabled("capturefork")
 _NO_SIDE_CHAIN = _disabled("sidechain")      # the chain rule of the folded weight gradients in line (chain_stream)
 _NO_PREPACK = _disabled("prepack")           # composed weights packed where the decoder needs them (_prepack_folds)
+_NO_HEAD_RANK1 = _disabled("headrank1") or _disabled("head_bnred")      # a one-channel head's data gradient is rebuilt in the trunk's weight-gradient loader
 # voxels up to which a 3-D block's weight gradient runs on the side stream beside its data gradient (BIU_SIDE_WGRAD_VOX=0: never)
 _SIDE_WGRAD_VOX = int(os.environ.get("BIU_SIDE_WGRAD_VOX", str(4 * 32 ** 3)))
 
@@ -301,6 +302,7 @@ class ConvBlockNode(Node):
             yout.buf.producer[yout.leaves[0]] = self
         self.red_partial: Optional[torch.Tensor] = None      # BatchNorm-backward sums delivered by the consumer's dgrad
         self.red_nblk = 0
+        self.rank1 = None            # (d logits, head weights) of a one-channel head that did not store d loss / d a: bwd() rebuilds it (rank1_ok)
         self.kd, self.kh, self.kw = _ksize(conv.weight)
         self.dil = int(conv.dilation[0])
         drop = seq[3] if len(seq) > 3 else None
@@ -512,7 +514,21 @@ class ConvBlockNode(Node):
         skip.mark_g()
         return deferred
 
+    def rank1_ok(self, eng, head_cout: int) -> bool:
+        """Will bwd() take the plain fused weight gradient in the form whose loader can rebuild the data gradient of a ``head_cout``-channel
+        1x1 head (``biu_conv_bwd_weight_bn_rank1``: bf16, one head channel, 16 output channels, rolling window)?  Never under a trace hook,
+        which reads the stored gradient."""
+        if eng.trace or _NO_HEAD_RANK1 or eng.tdtype != torch.bfloat16 or not self.batch_stats:
+            return False
+        if self.foldt is not None or isinstance(self.xin, CatAct) or self.fold_wg:
+            return False
+        if self.kd == 3 and self.y.nvox <= _SIDE_WGRAD_VOX and eng.chain_stream() is not None:
+            return False      # (the side-stream form applies the BatchNorm backward in a pass of its own)
+        return bool(lib.biu_conv_bwd_weight_bn_rank1_ok(self.xin.a(), self.y.g(), self.y.a(), head_cout, self.kd, self.kh, self.kw, self.dil,
+                                                        eng.dtype))
+
     def bwd(self, eng):
+        rank1, self.rank1 = self.rank1, None
         if not self.y.g_written():
             return            # no gradient reaches this block (e.g. Siam 'control' branch)
         st = _stream()
@@ -584,6 +600,11 @@ class ConvBlockNode(Node):
             lib.label = label
             eng.defer_grads(done, [(self.conv.weight, dw)])
             dw = None
+        elif rank1 is not None:
+            # the head in front did not store d loss / d a (rank one: d logits x head weights): the loader rebuilds it, dy is written as usual
+            check(lib.biu_conv_bwd_weight_bn_rank1(self.xin.a(), self.xin.xf(), _ptr(rank1[0]), _ptr(rank1[1]), 1, y.g(), y.a(), scale, shift,
+                                                   slope, _ptr(A), _ptr(B), _ptr(Cc), self.kd, self.kh, self.kw, self.dil, _ptr(dw),
+                                                   _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "conv_bwd_weight_bn_rank1")
         else:
             check(lib.biu_conv_bwd_weight_bn(self.xin.a(), self.xin.xf(), y.g(), y.a(), scale, shift, slope, _ptr(A), _ptr(B),
                                              _ptr(Cc), self.kd, self.kh, self.kw, self.dil, _ptr(dw), _ptr(eng.ws), eng.ws_bytes,
@@ -949,7 +970,8 @@ class HeadNode(Node):
                                    _ptr(dst), ctot, c0, _stream()), "head_dlogits")
         return dst
 
-    def bwd_with(self, eng, dl: Optional[torch.Tensor]):
+    def bwd_with(self, eng, dl: Optional[torch.Tensor], logits_only: bool = False):
+        """``logits_only``: ``dl`` is the caller's gradient on the logits, no activation gradient folded in."""
         if dl is None:
             return
         dl = dl.contiguous().float()
@@ -962,8 +984,12 @@ class HeadNode(Node):
             # the head is the only reader of its input: its dx pass also reduces the producer's BatchNorm-backward sums
             part = up.red_buffer(eng, up.kd, 0)
             n_up = C.c_int(0)
+            # one output channel: d x = d logits (x) w is rank one -- not stored; the trunk's weight gradient rebuilds it in its loader
+            rank1 = logits_only and self.cout == 1 and up.rank1_ok(eng, self.cout)
+            if rank1:
+                up.rank1 = (dl, self.conv.weight.data)
             check(lib.biu_head_bwd_bnred(self.xin.a(), self.xin.xf(), _ptr(self.conv.weight.data), self.cout, _ptr(dl),
-                                         self.xin.g(), _ptr(dw), _ptr(db), _ptr(eng.ws), eng.ws_bytes, _ptr(up.save_mean),
+                                         None if rank1 else self.xin.g(), _ptr(dw), _ptr(db), _ptr(eng.ws), eng.ws_bytes, _ptr(up.save_mean),
                                          _ptr(up.save_invstd), _ptr(part), part.numel(), C.byref(n_up), eng.dtype, st),
                   "head_bwd_bnred")
             up.red_nblk = n_up.value
@@ -1317,7 +1343,7 @@ class Engine:
         """The live heads of one trunk."""
         if len(live) == 1:
             h, (gl, ga, a) = live[0]
-            h.bwd_with(self, h.dlogits(self, gl, ga, a))
+            h.bwd_with(self, h.dlogits(self, gl, ga, a), logits_only=ga is None)
             return
         # several heads read the same trunk output: one fused (cout-stacked) backward keeps d x single-pass; every head's
         # d logits goes straight into its channel slice of the stacked operand
@@ -1411,6 +1437,9 @@ class _NetFn(torch.autograd.Function):
         # save_for_backward (a plain reference from the engine would keep the node -- and its claim on the engine -- alive)
         ctx.act_slot = {hi: i for i, (hi, kind) in enumerate(out_spec) if kind == "act"}
         ctx.save_for_backward(*[outs[i] for i in ctx.act_slot.values()])
+        # an output the loss does not use gets no gradient at all (None in backward's gouts) instead of a zero tensor the size of the output:
+        # HeadNode.dlogits then takes a gradient on the logits alone as it is
+        ctx.set_materialize_grads(False)
         for h in eng.heads:
             h.logits = h.activated = None
         return tuple(outs)

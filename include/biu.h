@@ -170,6 +170,18 @@ int biu_conv_bwd_weight_bn(const biu_act* x, const biu_xform* xf, const biu_act*
                            const float* scale, const float* shift, const float* slope, const float* coefA,
                            const float* coefB, const float* coefC, int kd, int kh, int kw, int dilation,
                            float* dw, void* ws, size_t ws_bytes, int dtype, biu_stream stream);
+/* The block in front of a ONE-channel 1x1 head, when that head is the block's only reader: the head's data gradient
+ * da[v][c] = bf16(dlogits[v] * w_head[c]) need not be stored by biu_head_bwd_bnred (dx = NULL) and loaded back here -- the loader
+ * rebuilds it from dlogits (fp32 [N,1,D,H,W]) and w_head[C] with the head kernel's own product and rounding.  `dy` is only
+ * written (d loss / d y, as biu_conv_bwd_weight_bn leaves it in `da`).  Served: bf16, 3x3x3, 16 output channels, the
+ * rolling-window form of the weight gradient; biu_conv_bwd_weight_bn_rank1_ok says (1 / 0), and the call returns
+ * BIU_ERR_UNSUPPORTED without launching where it says 0.                                                                      */
+int biu_conv_bwd_weight_bn_rank1_ok(const biu_act* x, const biu_act* dy, const biu_act* y, int head_cout, int kd, int kh, int kw,
+                                    int dilation, int dtype);
+int biu_conv_bwd_weight_bn_rank1(const biu_act* x, const biu_xform* xf, const float* dlogits, const float* w_head, int head_cout,
+                                 const biu_act* dy, const biu_act* y, const float* scale, const float* shift, const float* slope,
+                                 const float* coefA, const float* coefB, const float* coefC, int kd, int kh, int kw, int dilation,
+                                 float* dw, void* ws, size_t ws_bytes, int dtype, biu_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BatchNorm (training: batch statistics) + LeakyReLU(0.1)                          [K3, K4]
@@ -469,7 +481,9 @@ int biu_head_bwd(const biu_act* x, const biu_xform* xf, const float* w, int cout
                  const biu_act* dx, float* dw, float* dbias, void* ws, size_t ws_bytes, int dtype,
                  biu_stream stream);
 /* biu_head_bwd that also emits biu_bn_bwd_reduce's partial sums of the conv block that produced x (xf = its BatchNorm transform,
- * mean / invstd its saved statistics); valid when the head is x's only reader.  partial: >= BIU_BN_MAX_PARTIALS * C * 2 floats. */
+ * mean / invstd its saved statistics); valid when the head is x's only reader.  partial: >= BIU_BN_MAX_PARTIALS * C * 2 floats.
+ * dx = NULL (C <= 32, cout <= 2, 16-byte rows): dx is not stored, dw / dbias / partial are bit for bit what the storing call
+ * gives (the sums are taken from the value rounded to the storage type) -- for biu_conv_bwd_weight_bn_rank1.                  */
 int biu_head_bwd_bnred(const biu_act* x, const biu_xform* xf, const float* w, int cout, const float* dlogits, const biu_act* dx,
                        float* dw, float* dbias, void* ws, size_t ws_bytes, const float* mean, const float* invstd,
                        float* partial, size_t partial_floats, int* nblk, int dtype, biu_stream stream);

@@ -14,6 +14,7 @@ in place (BatchNorm backward), then runs the weight- and data-gradient kernels.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -154,8 +155,9 @@ class Act:
                                 self.buf.slope.data_ptr() + o)
         return C.byref(self._x)
 
-    def vec(self, name):   # view of a transform vector restricted to this slice
-        return getattr(self.buf, name)[self.c0:self.c0 + self.c]
+    def vec(self, name):   # view of a transform vector ("scale", "shift", "slope") restricted to this slice
+        buf = self.buf
+        return getattr(buf, name)[self.c0:self.c0 + self.c]
 
     # gradient bookkeeping -------------------------------------------------------------------------
     def g_written(self) -> bool:
@@ -182,27 +184,25 @@ class Act:
             self.buf.leaves[k] = True
             self.buf.nwr[k] = self.buf.nwr.get(k, 0) + 1
 
-    def last_writer_producer(self):
-        """ConvBlockNode that produced this slice if the caller is the last reader still to contribute its gradient."""
+    def completed_producer(self, k: int = 1, unwritten: bool = False):
+        """The caller's kernel delivers ``k`` of the gradient contributions still owed to this slice.  If they are the last ones, and the
+        slice is exactly the output of a ConvBlockNode that normalised with batch statistics, that node: its d loss / d a is complete
+        after this call, so the kernel can reduce the BatchNorm-backward sums on the way (ConvBlockNode.red_from).  Else None.
+        ``unwritten``: the kernel only writes, so the gradient must not have been written either (the caller is the only reader; a kernel
+        that may accumulate -- max-pool, a head -- only has to be the last of several)."""
         if len(self.leaves) != 1:
             return None
-        k = self.leaves[0]
-        if self.buf.ncons.get(k, 0) - self.buf.nwr.get(k, 0) != 1:
+        key = self.leaves[0]
+        if self.buf.ncons.get(key, 0) - self.buf.nwr.get(key, 0) != k or (unwritten and self.buf.leaves[key]):
             return None
-        up = self.buf.producer.get(k)
-        if up is None or not getattr(up, "batch_stats", False) or up.y.c != self.c or up.y.c0 != self.c0:
+        up = self.buf.producer.get(key)
+        if up is None or not up.batch_stats or up.y.c != self.c or up.y.c0 != self.c0:
             return None
         return up
 
     def consumed(self):
         for k in self.leaves:
             self.buf.ncons[k] = self.buf.ncons.get(k, 0) + 1
-
-    def sole_conv_block_producer(self):
-        """The ConvBlockNode whose output this Act is, if this Act is one slice with exactly one reader."""
-        if len(self.leaves) != 1 or self.buf.ncons.get(self.leaves[0], 0) != 1:
-            return None
-        return self.buf.producer.get(self.leaves[0])
 
 
 class CatAct:
@@ -249,6 +249,40 @@ class CatBuf:
         return CatAct(self.acts[0], self.acts[1])
 
 
+class Packed:
+    """Device image of some parameters in the layout a kernel family reads (MFMA weight packing, the composed weights of a folded decoder
+    level).  Stale when the ``(data_ptr, _version)`` of one of the parameters changes; a raw ``param.data`` write changes neither and
+    needs ``Engine.invalidate_packed``, which reaches every image through the engine's list."""
+
+    def __init__(self, eng: "Engine", nbytes: int, params, what: str, pack, job=None):
+        """``pack(dst, stream)``: the library call that writes the image (status returned); ``job``: its (transposed, kind, cin, cout,
+        kd, kh, kw) entry for ``biu_pack_batch`` if ``Engine.pack_all`` may refresh it in a batch.  No image at all (``ptr()`` is NULL)
+        where the library asks for zero bytes: no packed form serves the layer."""
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=eng.device) if nbytes else None
+        self.params = [p for p in params if p is not None]
+        self.what, self.pack, self.job = what, pack, job
+        self.ver = None
+        self.used = False            # pack_all leaves an image alone until its reader asked for it once
+        eng.images.append(self)
+
+    def version(self):
+        return tuple((p.data_ptr(), p._version) for p in self.params)
+
+    def ptr(self, ahead=None):
+        """Pointer to the up-to-date image, packed on the current stream if stale.  ``ahead``: event behind which a fresh image was
+        packed on another stream (Engine._prepack_folds): the current stream is ordered behind it."""
+        if self.buf is None:
+            return None
+        self.used = True
+        ver = self.version()
+        if self.ver != ver:
+            check(self.pack(_ptr(self.buf), _stream()), self.what)
+            self.ver = ver
+        elif ahead is not None:
+            torch.cuda.current_stream().wait_event(ahead)
+        return _ptr(self.buf)
+
+
 # ======================================================================================================
 # nodes
 # ======================================================================================================
@@ -278,21 +312,20 @@ class ConvBlockNode(Node):
 
     def __init__(self, eng, seq: nn.Sequential, xin: Act, yout: Act, dropout_follows: bool = False, fold_src: Optional[Act] = None,
                  convt: Optional["ConvTNode"] = None):
-        """``fold_src``: ``xin`` is the nearest-neighbour up-sampling (x2) of this coarse activation
-        (multi_output_unet3d/multi_output_unet3d.py:138-139).  The forward then runs folded on the coarse tensor
-        (``biu_upconv_fwd``: 8 parity classes x 2x2x2 taps instead of 27 taps, include/biu.h) when the kernel serves the shape, and
-        the data gradient goes straight to ``fold_src`` (``biu_upconv_bwd_data``) and the weight gradient reads ``fold_src``
-        (``biu_upconv_bwd_weight_bn``): with all three (``fold_all``) the up-sampled tensor ``xin`` is never needed and the up-sampling
-        node is skipped."""
+        """Which of four forms the block is, is settled here once (``form``); fwd and bwd dispatch on it.
+          "plain"   one input tensor.
+          "cat"     ``xin`` is a CatAct: the decoder's concatenation, read from its two buffers by the two-source kernels.
+          "upconv"  ``fold_src``: ``xin`` is the nearest-neighbour up-sampling (x2) of this coarse activation
+                    (multi_output_unet3d/multi_output_unet3d.py:138-139).  The forward then runs folded on the coarse tensor
+                    (``biu_upconv_fwd``: 8 parity classes x 2x2x2 taps instead of 27 taps, include/biu.h) when the kernel serves the shape,
+                    the data gradient goes straight to ``fold_src`` (``biu_upconv_bwd_data``, where ``fold_dg_slot`` exists) and the weight
+                    gradient reads ``fold_src`` (``biu_upconv_bwd_weight_bn``, where ``fold_wg``): with all three (``fold_all``) the
+                    up-sampled tensor ``xin`` is never needed and the up-sampling node is skipped.
+          "foldt"   ``convt``: xin = concat(convt's output, skip) (unet3d/unet3d.py:84-90).  ConvTranspose + concat + this conv then run as
+                    ONE op with the up half folded onto convt's coarse input (include/biu.h: biu_foldt_*), forward and backward; the ConvT
+                    node (``foldt``) is skipped altogether and this node delivers the gradients of its parameters too."""
         conv, bn = seq[0], seq[1]
         self.conv, self.bn, self.xin, self.y = conv, bn, xin, yout
-        self.fold_src, self.fold_slot, self.fold_dg_slot, self.fold_wg, self.fold_all = None, None, None, False, False
-        # ``convt``: xin = concat(convt's output, skip) (unet3d/unet3d.py:84-90).  ConvTranspose + concat + this conv then run as ONE op with the up
-        # half folded onto convt's coarse input (include/biu.h: biu_foldt_*), forward and backward; the ConvT node is skipped altogether and
-        # this node delivers the gradients of its parameters too.
-        self.foldt, self.foldt_blob, self.foldt_ver = None, None, None
-        self.fold_ws, self.fold_ev = None, None      # own workspace + events of the folded weight gradient's side-stream chain rule
-        self.wg_ws, self.wg_ev = None, None          # ... of a small layer's side-stream weight gradient
         # the block's activation as a leaky slope: LeakyReLU(s) -> s, ReLU -> 0 (Unet_v0 / BabyUnet), none or a later
         # non-piecewise-linear one (the attention gate's Sigmoid, applied by GateNode) -> 1
         act = seq[2] if len(seq) > 2 else None
@@ -300,9 +333,12 @@ class ConvBlockNode(Node):
         xin.consumed()
         if len(yout.leaves) == 1:
             yout.buf.producer[yout.leaves[0]] = self
-        self.red_partial: Optional[torch.Tensor] = None      # BatchNorm-backward sums delivered by the consumer's dgrad
+        self.batch_stats = False     # the last forward normalised with batch statistics (else: with the running ones)
+        self.red_partial: Optional[torch.Tensor] = None      # BatchNorm-backward sums delivered by the consumer's dgrad (red_from)
         self.red_nblk = 0
         self.rank1 = None            # (d logits, head weights) of a one-channel head that did not store d loss / d a: bwd() rebuilds it (rank1_ok)
+        self.fold_ws, self.fold_ev = None, None      # own workspace + events of the folded weight gradient's side-stream chain rule
+        self.wg_ws, self.wg_ev = None, None          # ... of a small layer's side-stream weight gradient
         self.kd, self.kh, self.kw = _ksize(conv.weight)
         self.dil = int(conv.dilation[0])
         drop = seq[3] if len(seq) > 3 else None
@@ -311,219 +347,127 @@ class ConvBlockNode(Node):
         assert tuple(conv.weight.shape[:2]) == (yout.c, xin.c), (conv.weight.shape, yout.c, xin.c)
         assert xin.space == yout.space
         self.params = [conv.weight, conv.bias, bn.weight, bn.bias]
-        cout = yout.c
-        dev = eng.device
+        w, cout, dt, dev = conv.weight, yout.c, eng.dtype, eng.device
         self.save_mean = torch.empty(cout, dtype=torch.float32, device=dev)
         self.save_invstd = torch.empty(cout, dtype=torch.float32, device=dev)
         yout.vec("slope").fill_(self.slope)
         eng.need_partial(cout)
         eng.need_partial_floats(lib.biu_conv_fwd_stats_floats(yout.a(), self.kd))
-        if (convt is not None and isinstance(xin, CatAct) and len(xin.parts) == 2 and xin.parts[0] is convt.y and convt.kd == 2
-                and (self.kd, self.kh, self.kw, self.dil) == (3, 3, 3, 1) and convt.up.bias is not None
-                and lib.biu_foldt_ok(convt.xin.a(), xin.parts[1].a(), yout.a(), eng.dtype)
-                and lib.biu_foldt_bwd_weight_workspace(convt.xin.c, xin.parts[1].c, cout, eng.dtype) > 0):
-            self.foldt = convt
-            lo, skip = convt.xin, xin.parts[1]
-            self.foldt_blob = torch.empty(lib.biu_foldt_packed_bytes(lo.c, skip.c, cout, eng.dtype), dtype=torch.uint8, device=dev)
+        parts = xin.parts if isinstance(xin, CatAct) else (xin,)
+        k333 = (self.kd, self.kh, self.kw, self.dil) == (3, 3, 3, 1)
+        self.form = "cat" if len(parts) == 2 else "plain"
+        self.foldt, self.foldt_img = None, None
+        self.fold_src, self.fold_slot, self.fold_dg_slot, self.fold_wg, self.fold_all = None, None, None, False, False
+        if (convt is not None and len(parts) == 2 and parts[0] is convt.y and convt.kd == 2 and k333 and convt.up.bias is not None
+                and lib.biu_foldt_ok(convt.xin.a(), parts[1].a(), yout.a(), dt)
+                and lib.biu_foldt_bwd_weight_workspace(convt.xin.c, parts[1].c, cout, dt) > 0):
+            self.form, self.foldt = "foldt", convt
+            lo, skip, up = convt.xin, parts[1], convt.up
+            self.foldt_img = Packed(eng, lib.biu_foldt_packed_bytes(lo.c, skip.c, cout, dt), (w, conv.bias, up.weight, up.bias), "foldt_pack",
+                                    lambda dst, st: lib.biu_foldt_pack(_ptr(w.data), _ptr(conv.bias.data) if conv.bias is not None else None,
+                                                                       _ptr(up.weight.data), _ptr(up.bias.data), lo.c, convt.y.c, skip.c, cout, dt, dst, st))
             eng.need_partial_floats(lib.biu_foldt_fwd_stats_floats(lo.a(), yout.a()))
-            eng.need_ws(lib.biu_foldt_bwd_weight_workspace(lo.c, skip.c, cout, eng.dtype))
-            self.params = [conv.weight, conv.bias, bn.weight, bn.bias]
-        if (fold_src is not None and (self.kd, self.kh, self.kw, self.dil) == (3, 3, 3, 1) and not isinstance(xin, CatAct)
-                and fold_src.c == xin.c and lib.biu_upconv_ok(fold_src.a(), yout.a(), eng.dtype)):
-            self.fold_src = fold_src
-            self.fold_slot = {"buf": torch.empty(lib.biu_upconv_packed_bytes(0, xin.c, cout, eng.dtype), dtype=torch.uint8, device=dev), "ver": None}
-            nb1 = lib.biu_upconv_packed_bytes(1, xin.c, cout, eng.dtype)
+            eng.need_ws(lib.biu_foldt_bwd_weight_workspace(lo.c, skip.c, cout, dt))
+        elif (fold_src is not None and k333 and len(parts) == 1 and fold_src.c == xin.c and lib.biu_upconv_ok(fold_src.a(), yout.a(), dt)):
+            self.form, self.fold_src = "upconv", fold_src
+
+            def folded(kind, nbytes):       # the weights folded per parity class, forward (0) / data gradient (1): once per version
+                return Packed(eng, nbytes, (w,), "upconv_pack", lambda dst, st: lib.biu_upconv_pack(kind, _ptr(w.data), xin.c, cout, dt, dst, st))
+            self.fold_slot = folded(0, lib.biu_upconv_packed_bytes(0, xin.c, cout, dt))
+            nb1 = lib.biu_upconv_packed_bytes(1, xin.c, cout, dt)
             if nb1:
-                self.fold_dg_slot = {"buf": torch.empty(nb1, dtype=torch.uint8, device=dev), "ver": None}
-            wsf = lib.biu_upconv_bwd_weight_workspace(xin.c, cout, eng.dtype)
+                self.fold_dg_slot = folded(1, nb1)
+            wsf = lib.biu_upconv_bwd_weight_workspace(xin.c, cout, dt)
             if wsf:
                 self.fold_wg = True
                 eng.need_ws(wsf)
             self.fold_all = self.fold_dg_slot is not None and self.fold_wg
             eng.need_partial_floats(lib.biu_upconv_fwd_stats_floats(fold_src.a(), yout.a()))
-        self.pk_f = eng.packed_slot(0, xin.c, cout, self.kd, self.kh, self.kw, self.dil)
-        self.pk_b = eng.packed_slot(1, xin.c, cout, self.kd, self.kh, self.kw, self.dil)
-        self.ws_bytes = lib.biu_conv_bwd_weight_workspace(xin.c, cout, self.kd, self.kh, self.kw, eng.dtype)
-        eng.need_ws(self.ws_bytes)
+        geom = (xin.c, cout, self.kd, self.kh, self.kw)
+        self.pk_f, self.pk_b = (Packed(eng, lib.biu_conv_packed_bytes(kind, *geom, self.dil, dt), (w,), "conv_pack",
+                                       lambda dst, st, kind=kind: lib.biu_conv_pack(kind, _ptr(w.data), *geom, dt, dst, st), job=(0, kind) + geom)
+                                for kind in (0, 1))
+        eng.need_ws(lib.biu_conv_bwd_weight_workspace(*geom, dt))
         # scratch of the input-channel split (small fp32 grids): the forward writes y, the data gradient the input's gradient(s).
         # Sized here into the engine's one workspace -- the library owns no memory (include/biu.h, biu_conv_split_workspace)
-        eng.need_ws(lib.biu_conv_split_workspace(xin.c, yout.a(), None, self.kd, self.kh, self.kw, self.dil, eng.dtype))
-        if isinstance(xin, CatAct):
-            eng.need_ws(lib.biu_conv_split_workspace(cout, xin.parts[0].a(), xin.parts[1].a(), self.kd, self.kh, self.kw, self.dil, eng.dtype))
-        else:
-            eng.need_ws(lib.biu_conv_split_workspace(cout, xin.a(), None, self.kd, self.kh, self.kw, self.dil, eng.dtype))
+        eng.need_ws(lib.biu_conv_split_workspace(xin.c, yout.a(), None, self.kd, self.kh, self.kw, self.dil, dt))
+        eng.need_ws(lib.biu_conv_split_workspace(cout, parts[0].a(), parts[1].a() if len(parts) == 2 else None, self.kd, self.kh, self.kw, self.dil, dt))
 
     def fwd(self, eng):
-        st = _stream()
+        st, y, train = _stream(), self.y, eng.bn_training(self.bn)
         w, b = self.conv.weight.data, self.conv.bias.data if self.conv.bias is not None else None
-        packed = eng.pack(self.pk_f, 0, self.conv.weight, self.xin.c, self.y.c, self.kd, self.kh, self.kw)
-        bn = self.bn
-        scale, shift = self.y.vec("scale"), self.y.vec("shift")
-        cat = self.xin.parts if isinstance(self.xin, CatAct) else None
-        if self.foldt is not None:
-            return self._fwd_foldt(eng, st)
-        folded = None
-        if self.fold_src is not None:                       # up-sampling + conv on the coarse tensor: weights folded once per version
-            ver = (self.conv.weight.data_ptr(), self.conv.weight._version)
-            if self.fold_slot["ver"] != ver:
-                check(lib.biu_upconv_pack(0, _ptr(w), self.xin.c, self.y.c, eng.dtype, _ptr(self.fold_slot["buf"]), st), "upconv_pack")
-                self.fold_slot["ver"] = ver
-            folded = _ptr(self.fold_slot["buf"])
-        if eng.bn_training(bn):
-            # convolution + BatchNorm statistics in one call (the MFMA kernel reduces them in its epilogue)
-            nblk = C.c_int(0)
-            if folded:
-                check(lib.biu_upconv_fwd(self.fold_src.a(), self.fold_src.xf(), folded, _ptr(b), self.y.a(), _ptr(eng.partial),
-                                         eng.partial.numel(), C.byref(nblk), eng.dtype, st), "upconv_fwd")
-            elif cat:
-                check(lib.biu_conv_fwd_cat(cat[0].a(), cat[0].xf(), cat[1].a(), cat[1].xf(), _ptr(w), packed, _ptr(b), self.kd,
-                                           self.kh, self.kw, self.dil, self.y.a(), _ptr(eng.partial), eng.partial.numel(),
-                                           C.byref(nblk), _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "conv_fwd_cat")
-            else:
-                check(lib.biu_conv_fwd_stats(self.xin.a(), self.xin.xf(), _ptr(w), packed, _ptr(b), self.kd, self.kh, self.kw,
-                                             self.dil, self.y.a(), _ptr(eng.partial), eng.partial.numel(), C.byref(nblk), _ptr(eng.ws), eng.ws_bytes,
-                                             eng.dtype, st), "conv_fwd_stats")
+        packed = self.pk_f.ptr()
+        # convolution + BatchNorm statistics in one call (the MFMA kernel reduces them in its epilogue); no statistics: eval mode
+        nblk = C.c_int(0)
+        stats = (_ptr(eng.partial), eng.partial.numel(), C.byref(nblk)) if train else (None, 0, None)
+        if self.form == "foldt":
+            lo, skip = self.foldt.xin, self.xin.parts[1]
+            blob = self.foldt_img.ptr(ahead=eng._fold_ev)
+            check(lib.biu_foldt_fwd(lo.a(), lo.xf(), skip.a(), skip.xf(), blob, y.a(), *stats, eng.dtype, st), "foldt_fwd")
+        elif self.form == "upconv":                         # up-sampling + conv on the coarse tensor
+            src, folded = self.fold_src, self.fold_slot.ptr()
+            check(lib.biu_upconv_fwd(src.a(), src.xf(), folded, _ptr(b), y.a(), *stats, eng.dtype, st), "upconv_fwd")
+        elif self.form == "cat":
+            p0, p1 = self.xin.parts
+            check(lib.biu_conv_fwd_cat(p0.a(), p0.xf(), p1.a(), p1.xf(), _ptr(w), packed, _ptr(b), self.kd, self.kh, self.kw, self.dil, y.a(),
+                                       *stats, _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "conv_fwd_cat")
+        elif train:
+            check(lib.biu_conv_fwd_stats(self.xin.a(), self.xin.xf(), _ptr(w), packed, _ptr(b), self.kd, self.kh, self.kw, self.dil, y.a(),
+                                         *stats, _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "conv_fwd_stats")
+        else:                                               # (the one entry point without the statistics arguments)
+            check(lib.biu_conv_fwd(self.xin.a(), self.xin.xf(), _ptr(w), packed, _ptr(b), self.kd, self.kh, self.kw, self.dil, y.a(),
+                                   _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "conv_fwd")
+        self._fwd_bn(eng, train, nblk.value, st)
+
+    def _fwd_bn(self, eng, train: bool, nblk: int, st):
+        """(scale, shift) of the consumer transform: from the ``nblk`` partial sums of the convolution's epilogue, or from the running
+        statistics."""
+        bn, y = self.bn, self.y
+        scale, shift = y.vec("scale"), y.vec("shift")
+        if train:
             mom = bn.momentum if bn.momentum is not None else 0.1
             track = bn.track_running_stats and bn.running_mean is not None
-            check(lib.biu_bn_finalize(_ptr(eng.partial), nblk.value, self.y.c, float(self.y.nvox), _ptr(bn.weight.data),
+            check(lib.biu_bn_finalize(_ptr(eng.partial), nblk, y.c, float(y.nvox), _ptr(bn.weight.data),
                                       _ptr(bn.bias.data), _ptr(bn.running_mean) if track else None,
                                       _ptr(bn.running_var) if track else None, mom, bn.eps, _ptr(scale), _ptr(shift),
                                       _ptr(self.save_mean), _ptr(self.save_invstd), st), "bn_finalize")
             if track and bn.num_batches_tracked is not None:
                 eng.nbt_bump.append(bn.num_batches_tracked)
-            self.batch_stats = True
         else:
-            if folded:
-                check(lib.biu_upconv_fwd(self.fold_src.a(), self.fold_src.xf(), folded, _ptr(b), self.y.a(), None, 0, None, eng.dtype, st),
-                      "upconv_fwd")
-            elif cat:
-                check(lib.biu_conv_fwd_cat(cat[0].a(), cat[0].xf(), cat[1].a(), cat[1].xf(), _ptr(w), packed, _ptr(b), self.kd,
-                                           self.kh, self.kw, self.dil, self.y.a(), None, 0, None, _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "conv_fwd_cat")
-            else:
-                check(lib.biu_conv_fwd(self.xin.a(), self.xin.xf(), _ptr(w), packed, _ptr(b), self.kd, self.kh, self.kw,
-                                       self.dil, self.y.a(), _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "conv_fwd")
-            check(lib.biu_bn_eval_affine(self.y.c, _ptr(bn.weight.data), _ptr(bn.bias.data), _ptr(bn.running_mean),
+            check(lib.biu_bn_eval_affine(y.c, _ptr(bn.weight.data), _ptr(bn.bias.data), _ptr(bn.running_mean),
                                          _ptr(bn.running_var), bn.eps, _ptr(scale), _ptr(shift), st), "bn_eval_affine")
-            self._eval_saved(eng)
-            self.batch_stats = False
+            if eng.grad_mode:
+                # Eval-mode forward under autograd (``model.eval(); loss.backward()``: frozen-BatchNorm fine-tuning, which the reference's
+                # plain nn.BatchNorm allows, unet/unet.py:54-60): the running statistics play the part of the saved batch statistics in
+                # the backward's (sum dz, sum dz * yhat).  Two C-sized vector ops, only when a backward can follow.
+                self.save_mean.copy_(bn.running_mean)
+                torch.rsqrt(bn.running_var.float() + bn.eps, out=self.save_invstd)
+        self.batch_stats = train
 
-    def _eval_saved(self, eng):
-        """Eval-mode forward under autograd (``model.eval(); loss.backward()``: frozen-BatchNorm fine-tuning, which the reference's plain
-        nn.BatchNorm allows, unet/unet.py:54-60): the running statistics play the part of the saved batch statistics in the backward's
-        (sum dz, sum dz * yhat).  Two C-sized vector ops, only when a backward can follow."""
-        if eng.grad_mode:
-            bn = self.bn
-            self.save_mean.copy_(bn.running_mean)
-            torch.rsqrt(bn.running_var.float() + bn.eps, out=self.save_invstd)
-
-    def _foldt_version(self):
-        ct = self.foldt
-        ps = (self.conv.weight, self.conv.bias, ct.up.weight, ct.up.bias)
-        return tuple((p.data_ptr(), p._version) for p in ps if p is not None)
-
-    def _foldt_packed(self, st, eng=None):
-        ct = self.foldt
-        ver = self._foldt_version()
-        if self.foldt_ver != ver:
-            check(lib.biu_foldt_pack(_ptr(self.conv.weight.data), _ptr(self.conv.bias.data) if self.conv.bias is not None else None,
-                                     _ptr(ct.up.weight.data), _ptr(ct.up.bias.data), ct.xin.c, ct.y.c, self.xin.parts[1].c, self.y.c, self._dtype,
-                                     _ptr(self.foldt_blob), st), "foldt_pack")
-            self.foldt_ver = ver
-        elif eng is not None and eng._fold_ev is not None:
-            # the image was packed ahead on the engine's side stream (Engine._prepack_folds): order this stream behind it
-            torch.cuda.current_stream().wait_event(eng._fold_ev)
-        return _ptr(self.foldt_blob)
-
-    def _fwd_foldt(self, eng, st):
-        self._dtype = eng.dtype
-        ct, skip, bn = self.foldt, self.xin.parts[1], self.bn
-        blob = self._foldt_packed(st, eng)
-        scale, shift = self.y.vec("scale"), self.y.vec("shift")
-        if eng.bn_training(bn):
-            nblk = C.c_int(0)
-            check(lib.biu_foldt_fwd(ct.xin.a(), ct.xin.xf(), skip.a(), skip.xf(), blob, self.y.a(), _ptr(eng.partial), eng.partial.numel(), C.byref(nblk),
-                                    eng.dtype, st), "foldt_fwd")
-            mom = bn.momentum if bn.momentum is not None else 0.1
-            track = bn.track_running_stats and bn.running_mean is not None
-            check(lib.biu_bn_finalize(_ptr(eng.partial), nblk.value, self.y.c, float(self.y.nvox), _ptr(bn.weight.data),
-                                      _ptr(bn.bias.data), _ptr(bn.running_mean) if track else None,
-                                      _ptr(bn.running_var) if track else None, mom, bn.eps, _ptr(scale), _ptr(shift),
-                                      _ptr(self.save_mean), _ptr(self.save_invstd), st), "bn_finalize")
-            if track and bn.num_batches_tracked is not None:
-                eng.nbt_bump.append(bn.num_batches_tracked)
-            self.batch_stats = True
-        else:
-            check(lib.biu_foldt_fwd(ct.xin.a(), ct.xin.xf(), skip.a(), skip.xf(), blob, self.y.a(), None, 0, None, eng.dtype, st), "foldt_fwd")
-            check(lib.biu_bn_eval_affine(self.y.c, _ptr(bn.weight.data), _ptr(bn.bias.data), _ptr(bn.running_mean),
-                                         _ptr(bn.running_var), bn.eps, _ptr(scale), _ptr(shift), st), "bn_eval_affine")
-            self._eval_saved(eng)
-            self.batch_stats = False
-
-    def _bwd_foldt(self, eng, st, scale, shift, slope, A, B, Cc, dw, dy_sum=None):
-        ct, skip, y = self.foldt, self.xin.parts[1], self.y
-        lo = ct.xin
-        dwt, dbt = eng.new_grad(ct.up.weight), eng.new_grad(ct.up.bias)
-        side = eng.chain_stream()
-        if side is None:
-            check(lib.biu_foldt_bwd_weight_bn(lo.a(), lo.xf(), skip.a(), skip.xf(), y.g(), y.a(), scale, shift, slope, _ptr(A), _ptr(B), _ptr(Cc), _ptr(dy_sum),
-                                              _ptr(self.conv.weight.data), _ptr(ct.up.weight.data), _ptr(ct.up.bias.data), ct.y.c, _ptr(dw), _ptr(dwt),
-                                              _ptr(dbt), _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "foldt_bwd_weight_bn")
-            eng.add_grad(ct.up.weight, dwt)
-            eng.add_grad(ct.up.bias, dbt)
-            deferred = False
-        else:
-            # the passes over the tensors here; the chain rule on their tables (seven small launches, 0.12-0.16 ms per level at cfg4, needed by
-            # the optimizer only) on the side stream, beside the data gradient and the next layers: its gradients are handed over one node later
-            if self.fold_ws is None:
-                self.fold_ws = torch.empty(lib.biu_foldt_bwd_weight_workspace(lo.c, skip.c, y.c, eng.dtype), dtype=torch.uint8, device=eng.device)
-                self.fold_ev = (torch.cuda.Event(), torch.cuda.Event())
-            args = (lo.a(), lo.xf(), skip.a(), skip.xf(), y.g(), y.a(), scale, shift, slope, _ptr(A), _ptr(B), _ptr(Cc), _ptr(dy_sum),
-                    _ptr(self.conv.weight.data), _ptr(ct.up.weight.data), _ptr(ct.up.bias.data), ct.y.c, _ptr(dw), _ptr(dwt), _ptr(dbt),
-                    _ptr(self.fold_ws), self.fold_ws.numel(), eng.dtype)
-            check(lib.biu_foldt_bwd_weight_bn_phase(*args, 1 | 4, st), "foldt_bwd_weight_bn_phase(1 | 4)")          # skip half (da -> dy) + G
-            # (G on the side stream as well -- mask 4 | 2 there -- measured 11.38 -> 11.40 ms: two persistent MFMA kernels only share the chip)
-            cur = torch.cuda.current_stream()
-            ready, done = self.fold_ev
-            ready.record(cur)
-            side.wait_event(ready)
-            label = lib.label
-            with torch.cuda.stream(side):
-                lib.label = label + "/chain"
-                check(lib.biu_foldt_bwd_weight_bn_phase(*args, 2, _stream()), "foldt_bwd_weight_bn_phase(2)")              # border sums + chain rule
-                done.record(side)
-            lib.label = label
-            eng.defer_grads(done, [(ct.up.weight, dwt), (ct.up.bias, dbt), (self.conv.weight, dw)], keep=(A, B, Cc, dy_sum))
-            deferred = True
-        blob = self._foldt_packed(st)
-        want_lo = eng.wants_grad(lo)
-        up = _fusable_producer(lo) if want_lo else None
-        if not want_lo:
-            raise NotImplementedError("foldt: the coarse input of a decoder level always wants its gradient")
-        if up is not None:
-            need = lib.biu_foldt_bwd_data_bnred_floats(lo.a())
-            if up.red_partial is None or up.red_partial.numel() < need:
-                up.red_partial = torch.empty(need, dtype=torch.float32, device=eng.device)
-            n_up = C.c_int(0)
-            check(lib.biu_foldt_bwd_data(y.g(), blob, lo.g(), 0, skip.g(), int(skip.g_written()), lo.a(), *up.red_coeffs(), _ptr(up.red_partial),
-                                         up.red_partial.numel(), C.byref(n_up), _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "foldt_bwd_data")
-            up.red_nblk = n_up.value
-        else:
-            check(lib.biu_foldt_bwd_data(y.g(), blob, lo.g(), int(lo.g_written()), skip.g(), int(skip.g_written()), None, None, None, None, None, None,
-                                         None, 0, None, _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "foldt_bwd_data")
-        lo.mark_g()
-        skip.mark_g()
-        return deferred
+    def wgrad_route(self, eng, rank1: bool):
+        """Which weight-gradient call bwd() makes now, and the side stream it forks part of it to (or None): "foldt", "cat", "upconv",
+        "side" (the plain weight gradient on the side stream), "rank1" (``rank1``: a head in front left its data gradient to this
+        block's loader) or "fused", in this precedence."""
+        if self.form == "foldt":
+            return "foldt", eng.chain_stream()
+        if self.form == "cat":
+            return "cat", None
+        if self.fold_wg:
+            return "upconv", None
+        if self.kd == 3 and eng.tdtype == torch.bfloat16 and self.y.nvox <= _SIDE_WGRAD_VOX:
+            side = eng.chain_stream()
+            if side is not None:
+                return "side", side
+        return ("rank1" if rank1 else "fused"), None
 
     def rank1_ok(self, eng, head_cout: int) -> bool:
         """Will bwd() take the plain fused weight gradient in the form whose loader can rebuild the data gradient of a ``head_cout``-channel
         1x1 head (``biu_conv_bwd_weight_bn_rank1``: bf16, one head channel, 16 output channels, rolling window)?  Never under a trace hook,
-        which reads the stored gradient."""
+        which reads the stored gradient; not on the side stream, whose form applies the BatchNorm backward in a pass of its own."""
         if eng.trace or _NO_HEAD_RANK1 or eng.tdtype != torch.bfloat16 or not self.batch_stats:
             return False
-        if self.foldt is not None or isinstance(self.xin, CatAct) or self.fold_wg:
+        if self.wgrad_route(eng, True)[0] != "rank1":
             return False
-        if self.kd == 3 and self.y.nvox <= _SIDE_WGRAD_VOX and eng.chain_stream() is not None:
-            return False      # (the side-stream form applies the BatchNorm backward in a pass of its own)
         return bool(lib.biu_conv_bwd_weight_bn_rank1_ok(self.xin.a(), self.y.g(), self.y.a(), head_cout, self.kd, self.kh, self.kw, self.dil,
                                                         eng.dtype))
 
@@ -532,7 +476,8 @@ class ConvBlockNode(Node):
         if not self.y.g_written():
             return            # no gradient reaches this block (e.g. Siam 'control' branch)
         st = _stream()
-        y, cout = self.y, self.y.c
+        y, cout, xin, w = self.y, self.y.c, self.xin, self.conv.weight
+        k4 = (self.kd, self.kh, self.kw, self.dil)
         scale, shift, slope = _ptr(y.vec("scale")), _ptr(y.vec("shift")), _ptr(y.vec("slope"))
         nblk = C.c_int(0)
         if self.red_nblk:
@@ -544,7 +489,7 @@ class ConvBlockNode(Node):
                                         _ptr(partial), C.byref(nblk), eng.dtype, st), "bn_bwd_reduce")
         dgamma, dbeta = eng.new_grad(self.bn.weight), eng.new_grad(self.bn.bias)
         A, B, Cc = eng.coef[0][:cout], eng.coef[1][:cout], eng.coef[2][:cout]
-        dw = eng.new_grad(self.conv.weight)
+        dw = eng.new_grad(w)
         dy_sum = None
         if self.batch_stats:
             check(lib.biu_bn_bwd_finalize(_ptr(partial), nblk.value, cout, float(y.nvox), scale, _ptr(self.save_mean),
@@ -561,114 +506,111 @@ class ConvBlockNode(Node):
             check(lib.biu_bn_bwd_finalize_eval(_ptr(partial), nblk.value, cout, scale, _ptr(dgamma), _ptr(dbeta), _ptr(dy_sum), _ptr(A), _ptr(B),
                                                _ptr(Cc), st), "bn_bwd_finalize_eval")
             db = dy_sum if self.conv.bias is not None else None
-        # BatchNorm+LeakyReLU backward (da -> dy, in place) rides inside the weight-gradient kernel's tile loader
-        cat = self.xin.parts if isinstance(self.xin, CatAct) else None
-        if self.foldt is not None:
-            if not self._bwd_foldt(eng, st, scale, shift, slope, A, B, Cc, dw, dy_sum):
-                eng.add_grad(self.conv.weight, dw)
-            if db is not None:
-                eng.add_grad(self.conv.bias, db)
-            eng.add_grad(self.bn.weight, dgamma)
-            eng.add_grad(self.bn.bias, dbeta)
-            return
-        if cat:
-            check(lib.biu_conv_bwd_weight_cat(cat[0].a(), cat[0].xf(), cat[1].a(), cat[1].xf(), y.g(), y.a(), scale, shift, slope,
-                                              _ptr(A), _ptr(B), _ptr(Cc), self.kd, self.kh, self.kw, self.dil, _ptr(dw), _ptr(eng.ws),
-                                              eng.ws_bytes, eng.dtype, st), "conv_bwd_weight_cat")
-        elif self.fold_wg:
-            check(lib.biu_upconv_bwd_weight_bn(self.fold_src.a(), self.fold_src.xf(), y.g(), y.a(), scale, shift, slope, _ptr(A), _ptr(B),
-                                               _ptr(Cc), _ptr(dw), _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "upconv_bwd_weight_bn")
-        elif self.kd == 3 and eng.tdtype == torch.bfloat16 and y.nvox <= _SIDE_WGRAD_VOX and eng.chain_stream() is not None:
+        # ---- weight gradient: BatchNorm+LeakyReLU backward (da -> dy, in place) rides inside the kernel's tile loader
+        bn_args = (y.g(), y.a(), scale, shift, slope, _ptr(A), _ptr(B), _ptr(Cc))
+        ws = (_ptr(eng.ws), eng.ws_bytes, eng.dtype, st)
+        route, side = self.wgrad_route(eng, rank1 is not None)
+        if route == "foldt":
+            ct, skip = self.foldt, xin.parts[1]
+            lo, up = ct.xin, ct.up
+            dwt, dbt = eng.new_grad(up.weight), eng.new_grad(up.bias)
+            args = (lo.a(), lo.xf(), skip.a(), skip.xf(), *bn_args, _ptr(dy_sum), _ptr(w.data), _ptr(up.weight.data), _ptr(up.bias.data), ct.y.c,
+                    _ptr(dw), _ptr(dwt), _ptr(dbt))
+            if side is None:
+                check(lib.biu_foldt_bwd_weight_bn(*args, *ws), "foldt_bwd_weight_bn")
+                eng.add_grad(up.weight, dwt)
+                eng.add_grad(up.bias, dbt)
+            else:
+                # the passes over the tensors here; the chain rule on their tables (seven small launches, 0.12-0.16 ms per level at cfg4, needed by
+                # the optimizer only) on the side stream, beside the data gradient and the next layers: its gradients are handed over one node later
+                if self.fold_ws is None:
+                    self.fold_ws = torch.empty(lib.biu_foldt_bwd_weight_workspace(lo.c, skip.c, cout, eng.dtype), dtype=torch.uint8, device=eng.device)
+                    self.fold_ev = (torch.cuda.Event(), torch.cuda.Event())
+                args += (_ptr(self.fold_ws), self.fold_ws.numel(), eng.dtype)
+                check(lib.biu_foldt_bwd_weight_bn_phase(*args, 1 | 4, st), "foldt_bwd_weight_bn_phase(1 | 4)")          # skip half (da -> dy) + G
+                # (G on the side stream as well -- mask 4 | 2 there -- measured 11.38 -> 11.40 ms: two persistent MFMA kernels only share the chip)
+                with eng.fork(side, self.fold_ev, "/chain", [(up.weight, dwt), (up.bias, dbt), (w, dw)], keep=(A, B, Cc, dy_sum)):
+                    check(lib.biu_foldt_bwd_weight_bn_phase(*args, 2, _stream()), "foldt_bwd_weight_bn_phase(2)")       # border sums + chain rule
+        elif route == "cat":
+            p0, p1 = xin.parts
+            check(lib.biu_conv_bwd_weight_cat(p0.a(), p0.xf(), p1.a(), p1.xf(), *bn_args, *k4, _ptr(dw), *ws), "conv_bwd_weight_cat")
+        elif route == "upconv":
+            check(lib.biu_upconv_bwd_weight_bn(self.fold_src.a(), self.fold_src.xf(), *bn_args, _ptr(dw), *ws), "upconv_bwd_weight_bn")
+        elif route == "side":
             # small volumes (the 32^3 / 16^3 levels of a 128^3 U-Net): weight and data gradient of a block each fill a fraction of the chip.
             # da -> dy here, then the weight gradient (needed by the optimizer only) on the side stream BESIDE the data gradient; its own
             # accumulator workspace, the parameter gradient handed over a node or two later (Engine._flush_deferred)
-            side = eng.chain_stream()
-            check(lib.biu_bn_bwd_apply(y.g(), y.a(), scale, shift, slope, _ptr(A), _ptr(B), _ptr(Cc), y.g(), eng.dtype, st), "bn_bwd_apply")
+            check(lib.biu_bn_bwd_apply(*bn_args, y.g(), eng.dtype, st), "bn_bwd_apply")
             if self.wg_ws is None:
-                self.wg_ws = torch.empty(max(lib.biu_conv_bwd_weight_workspace(self.xin.c, cout, self.kd, self.kh, self.kw, eng.dtype), 16), dtype=torch.uint8,
+                self.wg_ws = torch.empty(max(lib.biu_conv_bwd_weight_workspace(xin.c, cout, self.kd, self.kh, self.kw, eng.dtype), 16), dtype=torch.uint8,
                                          device=eng.device)
                 self.wg_ev = (torch.cuda.Event(), torch.cuda.Event())
-            ready, done = self.wg_ev
-            ready.record(torch.cuda.current_stream())
-            side.wait_event(ready)
-            label = lib.label
-            with torch.cuda.stream(side):
-                lib.label = label + "/wgrad"
-                check(lib.biu_conv_bwd_weight(self.xin.a(), self.xin.xf(), y.g(), self.kd, self.kh, self.kw, self.dil, _ptr(dw), None, _ptr(self.wg_ws),
-                                              self.wg_ws.numel(), eng.dtype, _stream()), "conv_bwd_weight")
-                done.record(side)
-            lib.label = label
-            eng.defer_grads(done, [(self.conv.weight, dw)])
-            dw = None
-        elif rank1 is not None:
+            with eng.fork(side, self.wg_ev, "/wgrad", [(w, dw)]):
+                check(lib.biu_conv_bwd_weight(xin.a(), xin.xf(), y.g(), *k4, _ptr(dw), None, _ptr(self.wg_ws), self.wg_ws.numel(), eng.dtype, _stream()),
+                      "conv_bwd_weight")
+        elif route == "rank1":
             # the head in front did not store d loss / d a (rank one: d logits x head weights): the loader rebuilds it, dy is written as usual
-            check(lib.biu_conv_bwd_weight_bn_rank1(self.xin.a(), self.xin.xf(), _ptr(rank1[0]), _ptr(rank1[1]), 1, y.g(), y.a(), scale, shift,
-                                                   slope, _ptr(A), _ptr(B), _ptr(Cc), self.kd, self.kh, self.kw, self.dil, _ptr(dw),
-                                                   _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "conv_bwd_weight_bn_rank1")
+            check(lib.biu_conv_bwd_weight_bn_rank1(xin.a(), xin.xf(), _ptr(rank1[0]), _ptr(rank1[1]), 1, *bn_args, *k4, _ptr(dw), *ws),
+                  "conv_bwd_weight_bn_rank1")
         else:
-            check(lib.biu_conv_bwd_weight_bn(self.xin.a(), self.xin.xf(), y.g(), y.a(), scale, shift, slope, _ptr(A), _ptr(B),
-                                             _ptr(Cc), self.kd, self.kh, self.kw, self.dil, _ptr(dw), _ptr(eng.ws), eng.ws_bytes,
-                                             eng.dtype, st), "conv_bwd_weight_bn")
-        if dw is not None:
-            eng.add_grad(self.conv.weight, dw)
+            check(lib.biu_conv_bwd_weight_bn(xin.a(), xin.xf(), *bn_args, *k4, _ptr(dw), *ws), "conv_bwd_weight_bn")
+        if side is None:             # (else the side stream's work delivers dw: Engine.fork)
+            eng.add_grad(w, dw)
         if db is not None:
             eng.add_grad(self.conv.bias, db)
         eng.add_grad(self.bn.weight, dgamma)
         eng.add_grad(self.bn.bias, dbeta)
-        if cat:
-            packed = eng.pack(self.pk_b, 1, self.conv.weight, self.xin.c, cout, self.kd, self.kh, self.kw)
-            check(lib.biu_conv_bwd_data_cat(y.g(), _ptr(self.conv.weight.data), packed, self.kd, self.kh, self.kw, self.dil,
-                                            cat[0].g(), cat[0].g_accumulate(), cat[1].g(), cat[1].g_accumulate(), _ptr(eng.ws), eng.ws_bytes, eng.dtype, st),
+        # ---- data gradient
+        if self.form == "foldt":
+            lo, skip = self.foldt.xin, xin.parts[1]
+            if not eng.wants_grad(lo):
+                raise NotImplementedError("foldt: the coarse input of a decoder level always wants its gradient")
+            blob = self.foldt_img.ptr()
+            up = lo.completed_producer(unwritten=True)
+            if up is not None:
+                up.red_from(eng, lib.biu_foldt_bwd_data_bnred_floats(lo.a()), "foldt_bwd_data", lambda *red: lib.biu_foldt_bwd_data(
+                    y.g(), blob, lo.g(), 0, skip.g(), int(skip.g_written()), lo.a(), *up.red_coeffs(), *red, *ws))
+            else:
+                check(lib.biu_foldt_bwd_data(y.g(), blob, lo.g(), int(lo.g_written()), skip.g(), int(skip.g_written()), None, None, None, None, None, None,
+                                             None, 0, None, *ws), "foldt_bwd_data")
+            lo.mark_g()
+            skip.mark_g()
+        elif self.form == "cat":
+            p0, p1 = xin.parts
+            check(lib.biu_conv_bwd_data_cat(y.g(), _ptr(w.data), self.pk_b.ptr(), *k4, p0.g(), p0.g_accumulate(), p1.g(), p1.g_accumulate(), *ws),
                   "conv_bwd_data_cat")
-            cat[0].mark_g()
-            cat[1].mark_g()
+            p0.mark_g()
+            p1.mark_g()
         elif self.fold_dg_slot is not None and eng.wants_grad(self.fold_src):
             # folded: d loss / d (coarse input) in one launch; xin's gradient is never written, so the up-sampling node's backward returns
-            ver = (self.conv.weight.data_ptr(), self.conv.weight._version)
-            if self.fold_dg_slot["ver"] != ver:
-                check(lib.biu_upconv_pack(1, _ptr(self.conv.weight.data), self.xin.c, cout, eng.dtype, _ptr(self.fold_dg_slot["buf"]), st), "upconv_pack")
-                self.fold_dg_slot["ver"] = ver
-            check(lib.biu_upconv_bwd_data(y.g(), _ptr(self.fold_dg_slot["buf"]), self.fold_src.g(), int(self.fold_src.g_written()), eng.dtype, st),
-                  "upconv_bwd_data")
-            self.fold_src.mark_g()
-        elif eng.wants_grad(self.xin):
-            packed = eng.pack(self.pk_b, 1, self.conv.weight, self.xin.c, cout, self.kd, self.kh, self.kw)
-            up = _fusable_producer(self.xin)
+            src = self.fold_src
+            check(lib.biu_upconv_bwd_data(y.g(), self.fold_dg_slot.ptr(), src.g(), int(src.g_written()), eng.dtype, st), "upconv_bwd_data")
+            src.mark_g()
+        elif eng.wants_grad(xin):
+            packed = self.pk_b.ptr()
+            up = xin.completed_producer(unwritten=True)
             if up is not None:
-                part = up.red_buffer(eng, self.kd, 0)
-                n_up = C.c_int(0)
-                check(lib.biu_conv_bwd_data_bnred(y.g(), _ptr(self.conv.weight.data), packed, self.kd, self.kh, self.kw,
-                                                  self.dil, self.xin.g(), self.xin.a(), *up.red_coeffs(), _ptr(part),
-                                                  part.numel(), C.byref(n_up), _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "conv_bwd_data_bnred")
-                up.red_nblk = n_up.value
+                up.red_from(eng, lib.biu_bwd_data_bnred_floats(xin.a(), self.kd, 0), "conv_bwd_data_bnred", lambda *red: lib.biu_conv_bwd_data_bnred(
+                    y.g(), _ptr(w.data), packed, *k4, xin.g(), xin.a(), *up.red_coeffs(), *red, *ws))
             else:
-                check(lib.biu_conv_bwd_data(y.g(), _ptr(self.conv.weight.data), packed, self.kd, self.kh, self.kw, self.dil,
-                                            self.xin.g(), int(self.xin.g_written()), _ptr(eng.ws), eng.ws_bytes, eng.dtype, st), "conv_bwd_data")
-            self.xin.mark_g()
+                check(lib.biu_conv_bwd_data(y.g(), _ptr(w.data), packed, *k4, xin.g(), int(xin.g_written()), *ws), "conv_bwd_data")
+            xin.mark_g()
 
     # ---- receiving side of the fused BatchNorm-backward reduction -----------------------------------
-    def red_buffer(self, eng, kd, transposed) -> torch.Tensor:
-        need = lib.biu_bwd_data_bnred_floats(self.y.a(), kd, transposed)
+    def red_from(self, eng, need: int, what: str, call):
+        """Hand-over of the BatchNorm-backward sums from the kernel that completes this block's d loss / d a (Act.completed_producer):
+        ``call(partial, capacity, count)`` is that kernel's library call with room for ``need`` floats of partial sums; bwd() then finds
+        ``red_nblk`` rows of them in ``red_partial`` and skips its own reduction."""
         if self.red_partial is None or self.red_partial.numel() < need:
             self.red_partial = torch.empty(need, dtype=torch.float32, device=eng.device)
-        return self.red_partial
+        n = C.c_int(0)
+        check(call(_ptr(self.red_partial), self.red_partial.numel(), C.byref(n)), what)
+        self.red_nblk = n.value
 
     def red_coeffs(self):
         y = self.y
         return (_ptr(y.vec("scale")), _ptr(y.vec("shift")), _ptr(y.vec("slope")), _ptr(self.save_mean),
                 _ptr(self.save_invstd))
-
-
-def _fusable_producer(xin: Act):
-    """ConvBlockNode whose BatchNorm-backward sums the data-gradient kernel writing xin's gradient can also produce:
-    xin is that block's output, this node is its only reader (so the gradient is complete after this one write) and the
-    block normalised with batch statistics."""
-    if xin.g_written():
-        return None
-    up = xin.sole_conv_block_producer()
-    if up is None or not getattr(up, "batch_stats", False) or up.y.c != xin.c or up.y.c0 != xin.c0:
-        return None
-    return up
 
 
 class ConvTNode(Node):
@@ -682,15 +624,16 @@ class ConvTNode(Node):
         assert tuple(w.shape[:2]) == (xin.c, yout.c)
         self.params = [up.weight, up.bias]
         self.folded_into = None              # the ConvBlockNode that computes ConvT + concat + conv as one op (biu_foldt_*): this node then does nothing
-        self.pk_f = eng.packed_slot_convt(0, xin.c, yout.c, self.kd)
-        self.pk_b = eng.packed_slot_convt(1, xin.c, yout.c, self.kd)
-        eng.need_ws(lib.biu_convt_bwd_weight_workspace(xin.c, yout.c, self.kd, eng.dtype))
+        geom, dt = (xin.c, yout.c, self.kd), eng.dtype
+        self.pk_f, self.pk_b = (Packed(eng, lib.biu_convt_packed_bytes(kind, *geom, dt), (w,), "convt_pack",
+                                       lambda dst, st, kind=kind: lib.biu_convt_pack(kind, _ptr(w.data), *geom, dt, dst, st), job=(1, kind) + geom + (2, 2))
+                                for kind in (0, 1))
+        eng.need_ws(lib.biu_convt_bwd_weight_workspace(*geom, dt))
 
     def fwd(self, eng):
         if self.folded_into is not None:
             return
-        packed = eng.pack_convt(self.pk_f, 0, self.up.weight, self.xin.c, self.y.c, self.kd)
-        check(lib.biu_convt_fwd(self.xin.a(), self.xin.xf(), _ptr(self.up.weight.data), packed, _ptr(self.up.bias.data),
+        check(lib.biu_convt_fwd(self.xin.a(), self.xin.xf(), _ptr(self.up.weight.data), self.pk_f.ptr(), _ptr(self.up.bias.data),
                                 self.kd, self.y.a(), eng.dtype, _stream()), "convt_fwd")
 
     def bwd(self, eng):
@@ -703,15 +646,11 @@ class ConvTNode(Node):
         eng.add_grad(self.up.weight, dw)
         eng.add_grad(self.up.bias, db)
         if eng.wants_grad(self.xin):
-            packed = eng.pack_convt(self.pk_b, 1, self.up.weight, self.xin.c, self.y.c, self.kd)
-            up = _fusable_producer(self.xin)
+            packed = self.pk_b.ptr()
+            up = self.xin.completed_producer(unwritten=True)
             if up is not None:
-                part = up.red_buffer(eng, self.kd, 1)
-                n_up = C.c_int(0)
-                check(lib.biu_convt_bwd_data_bnred(self.y.g(), _ptr(self.up.weight.data), packed, self.kd, self.xin.g(),
-                                                   self.xin.a(), *up.red_coeffs(), _ptr(part), part.numel(), C.byref(n_up),
-                                                   eng.dtype, st), "convt_bwd_data_bnred")
-                up.red_nblk = n_up.value
+                up.red_from(eng, lib.biu_bwd_data_bnred_floats(self.xin.a(), self.kd, 1), "convt_bwd_data_bnred", lambda *red: lib.biu_convt_bwd_data_bnred(
+                    self.y.g(), _ptr(self.up.weight.data), packed, self.kd, self.xin.g(), self.xin.a(), *up.red_coeffs(), *red, eng.dtype, st))
             else:
                 check(lib.biu_convt_bwd_data(self.y.g(), _ptr(self.up.weight.data), packed, self.kd, self.xin.g(),
                                              int(self.xin.g_written()), eng.dtype, st), "convt_bwd_data")
@@ -741,15 +680,11 @@ class ResampleNode(Node):
             return
         acc, st = int(self.xin.g_written()), _stream()
         if self.kind == "maxpool":
-            up = self.xin.last_writer_producer() if self.xin.xf() is not None else None
+            up = self.xin.completed_producer() if self.xin.xf() is not None else None
             if up is not None:
                 # the pool is the last reader of its input: the finished gradient is reduced for the producer's BatchNorm here
-                part = up.red_buffer(eng, up.kd, 0)
-                n_up = C.c_int(0)
-                check(lib.biu_maxpool_bwd_bnred(self.xin.a(), self.xin.xf(), self.y.g(), self.xin.g(), acc, _ptr(up.save_mean),
-                                                _ptr(up.save_invstd), _ptr(part), part.numel(), C.byref(n_up), eng.dtype, st),
-                      "maxpool_bwd_bnred")
-                up.red_nblk = n_up.value
+                up.red_from(eng, lib.biu_bwd_data_bnred_floats(self.xin.a(), up.kd, 0), "maxpool_bwd_bnred", lambda *red: lib.biu_maxpool_bwd_bnred(
+                    self.xin.a(), self.xin.xf(), self.y.g(), self.xin.g(), acc, _ptr(up.save_mean), _ptr(up.save_invstd), *red, eng.dtype, st))
             else:
                 check(lib.biu_maxpool_bwd(self.xin.a(), self.xin.xf(), self.y.g(), self.xin.g(), acc, eng.dtype, st), "maxpool_bwd")
         elif self.kind == "down":
@@ -939,6 +874,7 @@ class HeadNode(Node):
         self.params = [conv.weight, conv.bias]
         eng.need_ws(lib.biu_head_bwd_workspace(xin.c))
         self.logits = self.activated = None
+        self._keep = ()              # operands of the last biu_head_dlogits, alive until the next one
 
     def out_shape(self, eng):
         x = self.xin
@@ -979,20 +915,17 @@ class HeadNode(Node):
         dw, db = eng.new_grad(self.conv.weight), eng.new_grad(self.conv.bias)
         want_dx = eng.wants_grad(self.xin)
         assert not self.xin.g_written(), "heads that share a trunk go through Engine._backward_heads"
-        up = self.xin.last_writer_producer() if (want_dx and self.xin.xf() is not None) else None
+        up = self.xin.completed_producer() if (want_dx and self.xin.xf() is not None) else None
         if up is not None:
             # the head is the only reader of its input: its dx pass also reduces the producer's BatchNorm-backward sums
-            part = up.red_buffer(eng, up.kd, 0)
-            n_up = C.c_int(0)
+            need = lib.biu_bwd_data_bnred_floats(self.xin.a(), up.kd, 0)
             # one output channel: d x = d logits (x) w is rank one -- not stored; the trunk's weight gradient rebuilds it in its loader
             rank1 = logits_only and self.cout == 1 and up.rank1_ok(eng, self.cout)
             if rank1:
                 up.rank1 = (dl, self.conv.weight.data)
-            check(lib.biu_head_bwd_bnred(self.xin.a(), self.xin.xf(), _ptr(self.conv.weight.data), self.cout, _ptr(dl),
-                                         None if rank1 else self.xin.g(), _ptr(dw), _ptr(db), _ptr(eng.ws), eng.ws_bytes, _ptr(up.save_mean),
-                                         _ptr(up.save_invstd), _ptr(part), part.numel(), C.byref(n_up), eng.dtype, st),
-                  "head_bwd_bnred")
-            up.red_nblk = n_up.value
+            up.red_from(eng, need, "head_bwd_bnred", lambda *red: lib.biu_head_bwd_bnred(
+                self.xin.a(), self.xin.xf(), _ptr(self.conv.weight.data), self.cout, _ptr(dl), None if rank1 else self.xin.g(), _ptr(dw), _ptr(db),
+                _ptr(eng.ws), eng.ws_bytes, _ptr(up.save_mean), _ptr(up.save_invstd), *red, eng.dtype, st))
         else:
             check(lib.biu_head_bwd(self.xin.a(), self.xin.xf(), _ptr(self.conv.weight.data), self.cout, _ptr(dl),
                                    self.xin.g() if want_dx else None, _ptr(dw), _ptr(db), _ptr(eng.ws), eng.ws_bytes,
@@ -1019,18 +952,20 @@ class Engine:
         self.heads: List[HeadNode] = []
         self.bufs: List[Buf] = []
         self.inputs: List[Act] = []
-        self._partial_c = 0
+        self._partial_c, self._partial_floats = 0, 0
         self.ws_bytes = 0
         self.partial = self.ws = None
         self.coef = None
+        self.params: List[nn.Parameter] = []            # (finalize) every parameter of the graph, once
+        self._pcount: Dict[nn.Parameter, int] = {}      # (finalize) contributions a parameter receives per backward (weight sharing: > 1)
+        self._pseen: Dict[nn.Parameter, int] = {}       # ... and how many of them this backward has delivered
         self.grads: Dict[nn.Parameter, torch.Tensor] = {}
         self.nbt_bump: List[torch.Tensor] = []
         self.grad_mode = False
-        self.module_training = True
         self.input_requires_grad = False
-        self._packed: Dict[int, dict] = {}
         self._zero_flat, self._zero_used = None, 0
-        self._slots: List[dict] = []
+        self._stack_w: Dict[tuple, torch.Tensor] = {}   # stacked weights of the heads that share a trunk (_backward_head_group)
+        self.images: List[Packed] = []                  # every packed image of the graph's parameters
         self._job_key, self._job_tab = None, None
         self.grad_hook = None        # callable(param, grad) fired inside backward when a parameter's gradient is final (ddp.py)
         self.grad_alloc = None       # callable(param) -> fp32 tensor to compute the gradient INTO (a bucket view), or None (ddp.py)
@@ -1047,18 +982,10 @@ class Engine:
         return self._live is not None and self._live() is not None
 
     def invalidate_packed(self):
-        """Forget the cached MFMA weight packings (needed after a raw ``param.data`` write, which does not bump
-        ``Tensor._version``)."""
-        for s in self._slots:
-            s["ver"] = None
-        # the folded decoder levels keep their composed weights outside the slot list (biu_upconv_pack / biu_foldt_pack images)
-        for nd_ in self.nodes:
-            for name in ("fold_slot", "fold_dg_slot"):
-                s = getattr(nd_, name, None)
-                if s is not None:
-                    s["ver"] = None
-            if getattr(nd_, "foldt_ver", None) is not None:
-                nd_.foldt_ver = None
+        """Forget every packed image, the composed weights of the folded decoder levels included (needed after a raw ``param.data``
+        write, which does not bump ``Tensor._version``)."""
+        for im in self.images:
+            im.ver = None
 
     # ---- build helpers -------------------------------------------------------------------------------
     def new_buf(self, n, d, h, w, c) -> Buf:
@@ -1088,7 +1015,7 @@ class Engine:
         self._partial_c = max(self._partial_c, c)
 
     def need_partial_floats(self, n):
-        self._partial_floats = max(getattr(self, "_partial_floats", 0), int(n))
+        self._partial_floats = max(self._partial_floats, int(n))
 
     def need_ws(self, nbytes):
         self.ws_bytes = max(self.ws_bytes, int(nbytes))
@@ -1096,13 +1023,10 @@ class Engine:
     def finalize(self):
         dev = self.device
         c = max(self._partial_c, 1)
-        self.partial = torch.empty(max(BN_MAX_PARTIALS * c * 2, getattr(self, "_partial_floats", 0)), dtype=torch.float32,
-                                   device=dev)
+        self.partial = torch.empty(max(BN_MAX_PARTIALS * c * 2, self._partial_floats), dtype=torch.float32, device=dev)
         self.coef = torch.empty((3, c), dtype=torch.float32, device=dev)
         self.ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=dev)
-        self.params: List[nn.Parameter] = []
         seen = set()
-        self._pcount: Dict[nn.Parameter, int] = {}      # contributions a parameter receives per backward (weight sharing: > 1)
         for nd_ in self.nodes:
             for p in nd_.params:
                 if p is not None:
@@ -1112,66 +1036,27 @@ class Engine:
                         self.params.append(p)
 
     # ---- MFMA weight packing cache ---------------------------------------------------------------------
-    def packed_slot(self, kind, cin, cout, kd, kh, kw, dil):
-        nbytes = lib.biu_conv_packed_bytes(kind, cin, cout, kd, kh, kw, dil, self.dtype)
-        if nbytes == 0:
-            return None
-        slot = {"buf": torch.empty(nbytes, dtype=torch.uint8, device=self.device), "ver": None,
-                "job": (0, kind, cin, cout, kd, kh, kw), "weight": None}
-        self._slots.append(slot)
-        return slot
-
-    def pack(self, slot, kind, weight: nn.Parameter, cin, cout, kd, kh, kw):
-        if slot is None:
-            return None
-        slot["weight"] = weight
-        ver = (weight.data_ptr(), weight._version)
-        if slot["ver"] != ver:
-            check(lib.biu_conv_pack(kind, _ptr(weight.data), cin, cout, kd, kh, kw, self.dtype, _ptr(slot["buf"]), _stream()),
-                  "conv_pack")
-            slot["ver"] = ver
-        return _ptr(slot["buf"])
-
-    def packed_slot_convt(self, kind, cin, cout, kd):
-        nbytes = lib.biu_convt_packed_bytes(kind, cin, cout, kd, self.dtype)
-        if nbytes == 0:
-            return None
-        slot = {"buf": torch.empty(nbytes, dtype=torch.uint8, device=self.device), "ver": None,
-                "job": (1, kind, cin, cout, kd, 2, 2), "weight": None}
-        self._slots.append(slot)
-        return slot
-
-    def pack_convt(self, slot, kind, weight: nn.Parameter, cin, cout, kd):
-        if slot is None:
-            return None
-        slot["weight"] = weight
-        ver = (weight.data_ptr(), weight._version)
-        if slot["ver"] != ver:
-            check(lib.biu_convt_pack(kind, _ptr(weight.data), cin, cout, kd, self.dtype, _ptr(slot["buf"]), _stream()),
-                  "convt_pack")
-            slot["ver"] = ver
-        return _ptr(slot["buf"])
-
     def pack_all(self):
         """Re-pack every stale weight tensor of the network in ONE launch (a step changes all of them; ~30 separate pack
-        launches otherwise).  Slots learn their weight on first use, so the very first pass still packs one by one."""
-        stale = [s for s in self._slots if s["weight"] is not None and s["ver"] != (s["weight"].data_ptr(), s["weight"]._version)]
+        launches otherwise): the conv / ConvT images (those with a ``job``) whose reader has asked for them before, so the very first
+        pass still packs one by one."""
+        stale = [s for s in self.images if s.job is not None and s.used and s.ver != s.version()]
         if len(stale) < 2:
             return
-        key = tuple((id(s), s["weight"].data_ptr()) for s in stale)
+        key = tuple((id(s), s.params[0].data_ptr()) for s in stale)
         if self._job_key != key:                       # (re)build the device job table only when the set or a pointer changed
             from ._lib import biu_pack_job
             arr = (biu_pack_job * len(stale))()
             for j, s in zip(arr, stale):
-                tr, kind, cin, cout, kd, kh, kw = s["job"]
-                j.w, j.packed = s["weight"].data_ptr(), s["buf"].data_ptr()
+                tr, kind, cin, cout, kd, kh, kw = s.job
+                j.w, j.packed = s.params[0].data_ptr(), s.buf.data_ptr()
                 j.transposed, j.kind, j.cin, j.cout, j.kd, j.kh, j.kw, j.reserved = tr, kind, cin, cout, kd, kh, kw, 0
             raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
             self._job_tab = raw.to(self.device)
             self._job_key = key
         check(lib.biu_pack_batch(_ptr(self._job_tab), len(stale), self.dtype, _stream()), "pack_batch")
         for s in stale:
-            s["ver"] = (s["weight"].data_ptr(), s["weight"]._version)
+            s.ver = s.version()
 
     # ---- run-time helpers --------------------------------------------------------------------------------
     def bn_training(self, bn: nn.Module) -> bool:
@@ -1232,13 +1117,13 @@ class Engine:
             check(lib.biu_from_nchw(_ptr(x), act.a(), self.dtype, st), "from_nchw")
 
     def _prepack_folds(self):
-        """The composed weights of the folded decoder levels (biu_foldt_pack: 3 x 216 small GEMMs per level, 0.07-0.13 ms at cfg4) depend on the
+        """The composed weights of the folded decoder levels (ConvBlockNode.foldt_img: 3 x 216 small GEMMs per level, 0.07-0.13 ms at cfg4) depend on the
         parameters only: packed at the START of the forward on a side stream, they run beside the encoder instead of in front of the decoder
         (the decoder's first use waits on the event).  Not under stream capture (a captured step packs in line)."""
         self._fold_ev = None
         if _NO_PREPACK or (torch.cuda.is_current_stream_capturing() and _NO_CAPTURE_FORK):
             return
-        stale = [n for n in self.nodes if isinstance(n, ConvBlockNode) and n.foldt is not None and n.foldt_ver != n._foldt_version()]
+        stale = [n for n in self.nodes if isinstance(n, ConvBlockNode) and n.form == "foldt" and n.foldt_img.ver != n.foldt_img.version()]
         if not stale:
             return
         cur = torch.cuda.current_stream()
@@ -1246,11 +1131,9 @@ class Engine:
             self._side = torch.cuda.Stream(device=self.device)
         self._side.wait_stream(cur)                      # the optimizer's update (and the last backward's reads of the old images) are on `cur`
         with torch.cuda.stream(self._side):
-            st = _stream()
             for n in stale:
-                n._dtype = self.dtype
                 lib.label = n.label + ":pack"
-                n._foldt_packed(st)
+                n.foldt_img.ptr()
             self._fold_ev = torch.cuda.Event()
             self._fold_ev.record(self._side)
 
@@ -1286,7 +1169,21 @@ class Engine:
             self._side = torch.cuda.Stream(device=self.device)
         return self._side
 
-    def defer_grads(self, done: "torch.cuda.Event", grads, keep=()):
+    @contextlib.contextmanager
+    def fork(self, side, events, suffix: str, grads, keep=()):
+        """The body runs on ``side`` (chain_stream) behind everything the current stream holds so far, its library calls labelled
+        ``<label><suffix>``.  It computes the parameter gradients ``grads`` = [(parameter, tensor), ...]: they are handed over a node or
+        two later, behind the event recorded after the body (_flush_deferred); ``keep`` stays alive until then.  ``events``: the node's
+        own (ready, done) pair."""
+        ready, done = events
+        ready.record(torch.cuda.current_stream())
+        side.wait_event(ready)
+        label = lib.label
+        with torch.cuda.stream(side):
+            lib.label = label + suffix
+            yield
+            done.record(side)
+        lib.label = label
         self._deferred.append((done, grads, keep))
 
     def _flush_deferred(self, keep_last: int):
@@ -1301,7 +1198,7 @@ class Engine:
         """head_grads[i] = None or (d loss / d logits, d loss / d activated output, activated output) of head i."""
         self.grads = {}
         self._deferred = []
-        self._pseen: Dict[nn.Parameter, int] = {}
+        self._pseen = {}
         self._zero_flat, self._zero_used = None, 0
         for b in self.bufs:
             for k in b.leaves:
@@ -1353,8 +1250,6 @@ class Engine:
         shp = live[0][0].out_shape(self)
         dl = torch.empty((shp[0], cout) + tuple(shp[2:]), dtype=torch.float32, device=self.device)
         key = tuple(id(h) for h, _ in live)
-        if not hasattr(self, "_stack_w"):
-            self._stack_w = {}
         if key not in self._stack_w:
             self._stack_w[key] = torch.empty((cout, x.c), dtype=torch.float32, device=self.device)
         w, o = self._stack_w[key], 0
@@ -1364,20 +1259,12 @@ class Engine:
             o += h.cout
         dw = torch.empty_like(w)
         db = torch.empty(cout, dtype=torch.float32, device=self.device)
-        up = None
-        if self.wants_grad(x) and x.xf() is not None and not x.g_written() and len(x.leaves) == 1:
-            k = x.leaves[0]        # the heads are the trunk output's only readers: this one write completes its gradient
-            cand = x.buf.producer.get(k)
-            if (x.buf.ncons.get(k, 0) == len(live) and cand is not None and getattr(cand, "batch_stats", False)
-                    and cand.y.c == x.c and cand.y.c0 == x.c0):
-                up = cand
+        # (the heads are the trunk output's only readers: this one write completes its gradient)
+        up = x.completed_producer(len(live), unwritten=True) if (self.wants_grad(x) and x.xf() is not None) else None
         if up is not None:
-            part = up.red_buffer(self, up.kd, 0)
-            n_up = C.c_int(0)
-            check(lib.biu_head_bwd_bnred(x.a(), x.xf(), _ptr(w), cout, _ptr(dl), x.g(), _ptr(dw), _ptr(db), _ptr(self.ws), self.ws_bytes,
-                                         _ptr(up.save_mean), _ptr(up.save_invstd), _ptr(part), part.numel(), C.byref(n_up), self.dtype,
-                                         _stream()), "head_bwd_bnred(stacked)")
-            up.red_nblk = n_up.value
+            up.red_from(self, lib.biu_bwd_data_bnred_floats(x.a(), up.kd, 0), "head_bwd_bnred(stacked)", lambda *red: lib.biu_head_bwd_bnred(
+                x.a(), x.xf(), _ptr(w), cout, _ptr(dl), x.g(), _ptr(dw), _ptr(db), _ptr(self.ws), self.ws_bytes, _ptr(up.save_mean),
+                _ptr(up.save_invstd), *red, self.dtype, _stream()))
         else:
             check(lib.biu_head_bwd(x.a(), x.xf(), _ptr(w), cout, _ptr(dl), x.g(), _ptr(dw), _ptr(db), _ptr(self.ws),
                                    self.ws_bytes, self.dtype, _stream()), "head_bwd(stacked)")

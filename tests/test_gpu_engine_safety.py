@@ -103,8 +103,8 @@ def test_data_write_needs_invalidate_and_inplace_op_does_not():
 
 @pytest.mark.parametrize("kind", ["foldt", "upconv"])
 def test_data_write_and_invalidate_reach_the_folded_decoder_levels(kind):
-    """The composed weights of the folded decoder levels (biu_foldt_pack / biu_upconv_pack images) are cached outside the engine's
-    slot list: ``invalidate_packed()`` after a raw ``.data`` write must drop them too (ddp.GradAverager calls it after its broadcast).
+    """The composed weights of the folded decoder levels (biu_foldt_pack / biu_upconv_pack images) are packed images like the MFMA
+    weight packings: ``invalidate_packed()`` after a raw ``.data`` write must drop them too (ddp.GradAverager calls it after its broadcast).
     Compared with a FRESH model holding the written parameters -- forward, and the gradients of the folded level's parameters."""
     torch.manual_seed(4)
     heads = {"seg": {"channels": 1, "activation": None}}

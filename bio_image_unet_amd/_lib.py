@@ -41,6 +41,11 @@ class biu_mo2d_term(C.Structure):
                 ("p0", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("weight", C.c_float)]
 
 
+class biu_mo3d_term(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("rows", C.c_int32), ("partial_off", C.c_longlong), ("n", C.c_longlong), ("per_sample", C.c_longlong),
+                ("pairs", C.c_longlong), ("p0", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("weight", C.c_float)]
+
+
 class biu_aug_params(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("rot_k", C.c_uint32), ("blur_k", C.c_uint32), ("index", C.c_uint32), ("m", C.c_double * 6),
                 ("alpha", C.c_float), ("beta", C.c_float), ("noise_a", C.c_float), ("noise_b", C.c_float),
@@ -120,6 +125,11 @@ SIGNATURES = {
     "biu_mo2d_loss_finish": (_I, [_P, _I, _P, _P, _P]),
     "biu_mo2d_loss_coef": (_I, [_P, _I, _P, _P, _P, _P]),
     "biu_mo2d_loss_bwd": (_I, [_I, _F, _F, _P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "biu_mo3d_loss_blocks": (_I, [C.c_longlong]),
+    "biu_mo3d_loss_fwd": (_I, [_I, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "biu_mo3d_loss_finish": (_I, [_P, _I, _P, _P, _P]),
+    "biu_mo3d_loss_coef": (_I, [_P, _I, _P, _P, _P, _P]),
+    "biu_mo3d_loss_bwd": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "biu_trilinear_up_fwd": (_I, [_A, _X, _A, _I, _P]),
     "biu_trilinear_up_bwd": (_I, [_A, _A, _I, _I, _P]),
     "biu_bilinear_up_fwd": (_I, [_A, _X, _A, _I, _P]),

@@ -1,2 +1,5 @@
 from ..models import MultiOutputUnet3D  # noqa: F401
 from ..workflow import PredictMo3d as Predict, TrainerMo3d as Trainer   # noqa: F401
+from . import losses  # noqa: F401
+from .losses import (BCEDiceLoss, BCEDiceTemporalLoss, DiceLoss, MultiHeadLoss, TemporalConsistencyLoss, TverskyLoss,  # noqa: F401
+                     logcoshTverskyLoss)

@@ -380,8 +380,9 @@ class TrainerMo3d(_MultiHeadLoop):
     """``bio_image_unet.multi_output_unet3d.Trainer`` counterpart (``multi_output_unet3d/train.py:17-292``).
 
     Per-head loss ``output_heads[name]['loss']`` applied to the model's (already activated) output, summed with the heads'
-    weights; ``clip_grad_norm_(1.0)`` before the step; validation applies the head activation once more before the loss
-    (``:224``); scheduler ``ReduceLROnPlateau(patience=5, factor=0.2)``; the model stays in train mode during validation."""
+    weights, the whole sum as one fused autograd node (``multi_output_unet3d.losses.MultiHeadLoss``); ``clip_grad_norm_(1.0)`` before
+    the step; validation applies the head activation once more before the loss (``:224``); scheduler
+    ``ReduceLROnPlateau(patience=5, factor=0.2)``; the model stays in train mode during validation."""
 
     def __init__(self, dataset, output_heads, num_epochs, network=MultiOutputUnet3D, use_interpolation=False, batch_size=4,
                  lr=1e-3, in_channels=1, n_filter=64, dilation=1, val_split=0.2, save_dir="./", save_name="model.pt",
@@ -399,6 +400,8 @@ class TrainerMo3d(_MultiHeadLoop):
         self.loss_function, self.loss_params, self.time_loss_weight = loss_function, loss_params, time_loss_weight
         self.n_filter, self.in_channels, self.use_interpolation, self.dim = n_filter, in_channels, use_interpolation, dataset.dim_out
         self._set_heads(output_heads)
+        from .multi_output_unet3d.losses import MultiHeadLoss
+        self.head_loss = MultiHeadLoss(output_heads, loss_functions=self.loss_functions)
         if loss_function == "BCEDiceTemporalLoss":
             self.criterion = BCEDiceTemporalLoss(loss_params=loss_params)
         else:
@@ -416,26 +419,16 @@ class TrainerMo3d(_MultiHeadLoop):
 
     @staticmethod
     def _get_loss_function(loss_name):
-        table = {"BCEDiceLoss": lambda: BCEDiceLoss(1, 1), "DiceLoss": lambda: BCEDiceLoss(0, 1), "TverskyLoss": TverskyLoss,
-                 "logcoshTverskyLoss": logcoshTverskyLoss, "BCEDiceTemporalLoss": BCEDiceTemporalLoss}
-        if loss_name not in table:
-            raise ValueError(f'Loss "{loss_name}" not defined!')
-        return table[loss_name]()
+        from .multi_output_unet3d.losses import get_loss_function
+        return get_loss_function(loss_name)
 
     def _total_loss(self, batch, validating):
         x = batch["volume"].to(self.device, non_blocking=True)
         y = {key: _target(batch[key].to(self.device, non_blocking=True)) for key in self.output_heads}
         if x.dim() == 4:
             x = x.unsqueeze(1)
-        pred = self.model(x)
-        total = 0
-        for name in self.output_heads:
-            target = y[name]
-            if target.dim() == 4:
-                target = target.unsqueeze(1)
-            p = self._apply_activation(pred[name], self.activations.get(name)) if validating else pred[name]
-            total = total + self.loss_weights[name] * self.loss_functions[name](p, target)
-        return total
+        # one fused node over the heads; validation activates the activated outputs once more, in the forward kernel's registers
+        return self.head_loss(self.model(x), y, pre_activations=self.activations if validating else None)
 
     _forward_loss = _total_loss
 

@@ -357,6 +357,46 @@ int biu_mo2d_loss_coef(const biu_mo2d_term* terms, int nterms, const float* g, c
 int biu_mo2d_loss_bwd(int kind, float ea, float eb, const float* const* pred, int nlev, const float* target, int n, int c, int h, int w,
                       const float* coef, float* const* dpred, biu_stream stream);
 
+/* The criteria of the 3-D multi-output trainer (multi_output_unet3d/losses.py) on the tensor the model returned for a head: x / target
+ * fp32 contiguous [n, c, d, h, w]; the criteria treat x as logits, p = sigmoid(x).  M = n c d h w, sums over one sample carry _n.
+ *   kind                    (p0, p1, p2)            value
+ *   0 BCEDiceLoss           (alpha, beta, -)        p0 mean BCEWithLogits(x, t) + p1 (1 - mean_n 2 (sum_n p t + 1) / (sum_n p + sum_n t + 1))
+ *   1 TverskyLoss           (alpha, beta, smooth)   1 - Tv,  Tv = (TP + s) / (TP + alpha FP + beta FN + s) over the whole tensor
+ *   2 logcoshTverskyLoss    (alpha, beta, smooth)   log cosh(1 - Tv)
+ *   3 BCEDiceTemporalLoss   (w0, w1, -)             p0 BCEDice(1, 1) + p1 mean |x[:, :, 1:] - x[:, :, :-1]| over pairs = n c (d - 1) h w;
+ *                                                   nan when d == 1 (l1_loss over an empty slice)
+ * biu_mo3d_loss_blocks: rows = the partial rows PER SAMPLE for a tensor of numel elements.
+ * biu_mo3d_loss_fwd:    partial[n][rows][BIU_MO3D_SLOTS] per-block sums { BCE, p, t, p t, |x[z+1] - x[z]| (kind 3), 0 x 3 }, no atomics:
+ *                       bit-reproducible.  pre_act (0 none, 1 sigmoid, 2 tanh, 3 relu) is applied to x before everything else -- the
+ *                       validation pass of the reference, forward only.
+ * biu_mo3d_loss_finish: ONE one-block launch for all heads of a step.  terms (device array, nterms <= BIU_MO3D_MAX_TERMS) name each head:
+ *                       its partial rows (offset in floats into `workspace`), kind, extents, parameters and head weight ->
+ *                       saved[BIU_MO3D_SAVED_HEADER + BIU_MO3D_SLOTS sum_terms n] = { sum_t weight_t loss_t, loss_0 .. loss_{nterms-1}, 0 ..,
+ *                       then per (term, sample) in table order the merged row }.
+ * biu_mo3d_loss_coef:   g = d / d total (device scalar) -> coef[sum_terms n][4] = { c0, c1, c2, ct } per (term, sample), table order.
+ * biu_mo3d_loss_bwd:    dx = c0 (p - t) + (c1 + c2 t) p (1 - p) + ct (sign(x[z] - x[z-1]) - sign(x[z+1] - x[z])) for one head from its coef
+ *                       rows (coef + 4 * samples of the terms before it); the missing neighbour's term is dropped at z = 0 and z = d - 1,
+ *                       sign(0) = 0.  Takes x as given: a pre-activation under autograd is the caller's.
+ * 16-byte accesses when every pointer is 16-byte aligned and c d h w % 4 == 0 (kind 3: h w % 4 == 0 too); scalar accesses otherwise.
+ * n <= 65535 (one grid row per sample).                                                                                               */
+#define BIU_MO3D_MAX_TERMS 16
+#define BIU_MO3D_SLOTS 8
+#define BIU_MO3D_SAVED_HEADER 32
+typedef struct biu_mo3d_term {
+    int kind, rows;             /* rows: partial rows per sample (biu_mo3d_loss_blocks)            */
+    long long partial_off;      /* floats, into the workspace handed to biu_mo3d_loss_finish       */
+    long long n, per_sample;    /* samples, and c d h w                                            */
+    long long pairs;            /* n c (d - 1) h w                                                 */
+    float p0, p1, p2, weight;
+} biu_mo3d_term;
+int biu_mo3d_loss_blocks(long long numel);
+int biu_mo3d_loss_fwd(int kind, int pre_act, const float* x, const float* target, int n, int c, int d, int h, int w, float* partial,
+                      biu_stream stream);
+int biu_mo3d_loss_finish(const biu_mo3d_term* terms, int nterms, const float* workspace, float* saved, biu_stream stream);
+int biu_mo3d_loss_coef(const biu_mo3d_term* terms, int nterms, const float* g, const float* saved, float* coef, biu_stream stream);
+int biu_mo3d_loss_bwd(int kind, const float* x, const float* target, int n, int c, int d, int h, int w, const float* coef, float* dx,
+                      biu_stream stream);
+
 /* Trilinear x2 up-sampling, align_corners = False (F.interpolate(scale_factor=2, mode='trilinear'),
  * unet3d/unet3d.py:82,89,96): out = interp(T(x)); depth is doubled when out->d == 2 * x->d, kept when equal.
  * bwd: dx (+)= adjoint(dout).                                                                                        */

@@ -19,7 +19,10 @@ Layout: all five Trainers sit on ``_EpochLoop`` (construction tail, batch loop, 
 a few class attributes (scheduler, gradient clip, which lines it prints), ``_forward_loss`` (``_total_loss`` on the two multi-output families,
 which share ``_MultiHeadLoop``), ``_checkpoint(epoch, val_loss)`` -- the dictionary it saves -- and ``_report`` where its text differs.  The
 Predicts share checkpoint loading (``_load_params``), percentile normalisation (``_percentile_rescale``) and result writing (``_write``,
-``_write_heads``).
+``_write_heads``).  Every Predict takes ``preprocess='host'`` (that numpy path, the default) or ``'device'``: the raw stack is uploaded once
+in its own dtype and percentiles, rescale, padding and tiling run in HBM (``preprocess.DeviceFrontEnd``) over the same tile origins
+(``_origins``); its docstring states where the two differ (float32 input of the float32-arithmetic host paths, NaN, float64 that float32
+cannot hold).
 """
 from __future__ import annotations
 
@@ -34,6 +37,7 @@ from torch.utils.data import DataLoader, random_split
 from .losses import BCEDiceLoss, BCEDiceLossSiam, BCEDiceTemporalLoss, TverskyLoss, logcoshTverskyLoss, weightedBCELoss
 from .models import AttentionUnet, MultiOutputNestedUNet, MultiOutputUnet3D, Siam_UNet, UNet3D, Unet, Unet_v0
 from .optim import Adam
+from .preprocess import DeviceFrontEnd
 from .utils import get_device, init_weights
 
 try:                                    # progress bars are cosmetic
@@ -623,28 +627,60 @@ def _quantize_u8(prob: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _check_preprocess(preprocess):
+    """``preprocess`` of the Predict classes: ``'host'`` normalises and tiles in numpy as the reference does; ``'device'`` uploads the raw
+    stack once and does both in HBM (``preprocess.DeviceFrontEnd``)."""
+    if preprocess not in ("host", "device"):
+        raise ValueError(f"preprocess '{preprocess}' not valid: 'host' or 'device'")
+
+
+def _patch_batch(patches, i, j, device):
+    """Patches ``i:j`` on the device: a slice of the host array sent up, or cut and normalised there by the device front end."""
+    if isinstance(patches, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(patches[i:j])).to(device, non_blocking=True)
+    return patches.batch(i, j)
+
+
 class Predict2D:
     """``bio_image_unet.unet.Predict`` counterpart (``unet/predict.py:14-229``) for in-memory arrays.
 
     Same preprocessing, tiling, uint8 re-quantisation ``(p*255).astype('uint8')`` and nan-mean stitching; patches are
     pushed through the network in batches (eval-mode BatchNorm makes that identical to the reference's batch of 1) so the
     device is not synchronised once per patch.  The result is kept in ``self.imgs_result`` and written to
-    ``result_name`` (TIFF via tifffile when importable -- float16 like ``save_as_tif`` -- otherwise ``.npy``)."""
+    ``result_name`` (TIFF via tifffile when importable -- float16 like ``save_as_tif`` -- otherwise ``.npy``).
+
+    ``preprocess='device'`` (default ``'host'``) normalises and tiles in HBM (``preprocess.DeviceFrontEnd``): fp64 from the values as
+    uploaded, bit-equal to the host path for integer and float64 input (float64 goes up as float32 and raises ``ValueError`` unless every
+    value is exactly representable); float32 input, which the host path normalises in numpy float32, gets the same formula in fp64
+    rounded once; NaN raises ``ValueError`` (use ``preprocess='host'``); a constant image is 0 / 0 on both paths."""
 
     def __init__(self, imgs, result_name, model_params, network="Unet", resize_dim=(512, 512), invert=False,
                  normalization_mode="single", clip_threshold=(0., 99.8), add_tile=0, normalize_result=False,
-                 show_progress=True, device: Union[torch.device, str] = "auto", progress_notifier=None, batch_size=8):
+                 show_progress=True, device: Union[torch.device, str] = "auto", progress_notifier=None, batch_size=8,
+                 preprocess="host"):
+        _check_preprocess(preprocess)
         self.device = _pick_device(device)
         if isinstance(imgs, str):
             import tifffile                      # only needed for file input; not a dependency of the hot path
             imgs = tifffile.imread(imgs)
-        imgs = np.array(imgs, dtype=np.float64 if np.asarray(imgs).dtype.kind != "f" else np.asarray(imgs).dtype)
         self.resize_dim, self.add_tile = tuple(resize_dim), add_tile
-        if imgs.ndim == 2:
-            imgs = imgs[None]
-        self.imgs_shape = imgs.shape
-        imgs = normalise_stack(imgs, normalization_mode, clip_threshold, invert)
-        patches = self._split(imgs)
+        if preprocess == "device":
+            # the raw stack goes up in its own dtype; percentiles, rescale, reflect padding and tiling happen in HBM (preprocess.py).  fp64
+            # from the values as uploaded: bit-equal to the host path for integer and float64 input; float32 input, which the host path
+            # normalises in numpy float32, comes out as the same formula evaluated in fp64
+            raw = np.asarray(imgs)
+            raw = raw[None] if raw.ndim == 2 else raw
+            self.imgs_shape = raw.shape
+            fe = DeviceFrontEnd(raw, self.device)
+            fe.normalise(normalization_mode, clip_threshold)
+            patches = fe.tiles(self._origins(), (1,) + self.resize_dim, out="uint8", invert=invert)
+        else:
+            imgs = np.array(imgs, dtype=np.float64 if np.asarray(imgs).dtype.kind != "f" else np.asarray(imgs).dtype)
+            if imgs.ndim == 2:
+                imgs = imgs[None]
+            self.imgs_shape = imgs.shape
+            imgs = normalise_stack(imgs, normalization_mode, clip_threshold, invert)
+            patches = self._split(imgs)
 
         self.model_params = _load_params(model_params, self.device)
         if network is None:
@@ -671,24 +707,28 @@ class Predict2D:
         # float16 like ``save_as_tif`` in the TIFF only; the ``.npy`` fallback keeps the array as it is
         _write(result_name, _unit_range(self.imgs_result) if normalize_result else self.imgs_result, tif_dtype="float16" if normalize_result else None)
 
-    def _split(self, imgs):
+    def _origins(self):
+        """Tile grid of ``unet/predict.py:153-181``: sets ``N_x``, ``N_y``, ``X_start``, ``Y_start`` and returns the patch order as
+        (image, 0, row, column) in the (reflect-padded) stack -- shared by the host ``_split`` and the device front end."""
         n_img, h, w = self.imgs_shape
         th, tw = self.resize_dim
         self.N_x = int(np.ceil(h / th)) + self.add_tile
         self.N_y = int(np.ceil(w / tw)) + self.add_tile
         self.N_per_img = self.N_x * self.N_y
+        self.X_start, self.Y_start = tile_starts(h, th, self.N_x), tile_starts(w, tw, self.N_y)
+        return [(i, 0, int(xs), int(ys)) for i in range(n_img) for xs in self.X_start for ys in self.Y_start]
+
+    def _split(self, imgs):
+        n_img, h, w = self.imgs_shape
+        th, tw = self.resize_dim
+        origins = self._origins()
         if th > h:
             imgs = np.pad(imgs, ((0, 0), (0, th - h), (0, 0)), "reflect")
         if tw > w:
             imgs = np.pad(imgs, ((0, 0), (0, 0), (0, tw - w)), "reflect")
-        self.X_start, self.Y_start = tile_starts(h, th, self.N_x), tile_starts(w, tw, self.N_y)
         patches = np.zeros((n_img * self.N_per_img, 1, th, tw), dtype="uint8")
-        k = 0
-        for img in imgs:
-            for xs in self.X_start:
-                for ys in self.Y_start:
-                    patches[k, 0] = img[xs:xs + th, ys:ys + tw]        # float -> uint8 truncation, as upstream
-                    k += 1
+        for k, (i, _, xs, ys) in enumerate(origins):
+            patches[k, 0] = imgs[i, xs:xs + th, ys:ys + tw]            # float -> uint8 truncation, as upstream
         return patches
 
     def _predict_and_stitch(self, patches, batch_size):
@@ -704,7 +744,7 @@ class Predict2D:
         done, cur = [], 0
         with torch.no_grad():
             for i in range(0, patches.shape[0], batch_size):
-                x = torch.from_numpy(patches[i:i + batch_size]).to(self.device, non_blocking=True)      # uint8 across PCIe
+                x = _patch_batch(patches, i, i + batch_size, self.device)      # uint8 across PCIe (host path) or cut in HBM (device path)
                 prob, _ = self.model(x)
                 q = _quantize_u8(prob)
                 for j in range(q.shape[0]):
@@ -756,11 +796,13 @@ class Predict3D:
     Whole-volume percentile clip to [0, 255]; patches of ``resize_dim`` (z, x, y) at ``linspace`` origins (reflect padding
     when the volume is smaller); one eval-mode forward per patch; uint8 re-quantisation; stitching through the
     reference's three-layer float16 buffer (patch ``n`` goes to layer ``n % 3``, later patches overwrite earlier ones of
-    the same layer, then ``nanmean`` over the layers)."""
+    the same layer, then ``nanmean`` over the layers).  ``preprocess='device'``: as for ``Predict2D``, same departures (the host path
+    computes in float64 for integer volumes and in float32 for float32 ones)."""
 
     def __init__(self, vol, result_name, model_params, network=UNet3D, resize_dim=(64, 128, 128), invert=False,
                  normalization_mode="single", clip_threshold=(0., 99.8), add_patch=0, normalize_result=False,
-                 progress_bar=True, device: Union[torch.device, str] = "auto", progress_notifier=None):
+                 progress_bar=True, device: Union[torch.device, str] = "auto", progress_notifier=None, preprocess="host"):
+        _check_preprocess(preprocess)
         self.device = _pick_device(device)
         if isinstance(vol, str):
             import tifffile
@@ -771,8 +813,13 @@ class Predict3D:
         if vol.ndim == 2:
             vol = vol[None]
             self.vol_shape = vol.shape
-        vol = normalise_stack(vol, "all", clip_threshold, invert)       # the whole volume's histogram, whatever normalization_mode says
-        patches = self._split(vol)
+        if preprocess == "device":                                      # (departures as for Predict2D)
+            fe = DeviceFrontEnd(vol, self.device, depth=vol.shape[0])
+            fe.normalise("all", clip_threshold)
+            patches = fe.tiles(self._origins(), self.resize_dim, out="uint8", invert=invert)
+        else:
+            vol = normalise_stack(vol, "all", clip_threshold, invert)   # the whole volume's histogram, whatever normalization_mode says
+            patches = self._split(vol)
         mp = self.model_params = _load_params(model_params, self.device)
         self.model = network(n_filter=mp["n_filter"], in_channels=mp["in_channels"], out_channels=mp["out_channels"],
                              use_interpolation=mp.get("use_interpolation", False)).to(self.device)
@@ -784,15 +831,17 @@ class Predict3D:
         st = _Stitcher(self.device, 1, tuple(max(vs[a], rd[a]) for a in range(3)), layers=3)
         origins = [(int(z), int(x), int(y)) for z in self.Z_start for x in self.X_start for y in self.Y_start]
         with torch.no_grad():
-            for i, p in enumerate(patches):
-                x = torch.from_numpy(p).to(self.device, non_blocking=True).view((1, 1) + self.resize_dim)      # uint8; /255 in the layout kernel
+            for i in range(self.N):
+                x = _patch_batch(patches, i, i + 1, self.device).view((1, 1) + self.resize_dim)      # uint8; /255 in the layout kernel
                 prob, _ = self.model(x)
                 st.add(_quantize_u8(prob).view((1,) + self.resize_dim), origins[i], layer=i % 3, overwrite=True)
         out = st.finish(True)[0].cpu().numpy()
         self.vol_result = np.squeeze(out[:vs[0], :vs[1], :vs[2]])
         _write(result_name, _unit_range(self.vol_result).astype("float16") if normalize_result else self.vol_result)
 
-    def _split(self, vol):
+    def _origins(self):
+        """Patch grid of ``unet3d/predict.py:118-150``: sets the counts and ``Z_start`` / ``X_start`` / ``Y_start`` and returns the patch order
+        as (0, z, x, y) in the (reflect-padded) volume -- shared by the host ``_split`` and the device front end."""
         vs, rd, ap = self.vol_shape, self.resize_dim, self.add_patch
         self.N_z = int(np.ceil(vs[0] / rd[0])) + ap
         self.N_x = int(np.ceil(vs[1] / rd[1])) + ap
@@ -801,17 +850,18 @@ class Predict3D:
         self.N_x += ap if self.N_x > 1 else 0
         self.N_y += ap if self.N_y > 1 else 0
         self.N = self.N_x * self.N_y * self.N_z
-        vol = np.pad(vol, [(0, max(0, rd[a] - vs[a])) for a in range(3)], "reflect")
         self.Z_start = tile_starts(vs[0], rd[0], self.N_z)
         self.X_start = tile_starts(vs[1], rd[1], self.N_x)
         self.Y_start = tile_starts(vs[2], rd[2], self.N_y)
+        return [(0, int(z), int(x), int(y)) for z in self.Z_start for x in self.X_start for y in self.Y_start]
+
+    def _split(self, vol):
+        vs, rd = self.vol_shape, self.resize_dim
+        origins = self._origins()
+        vol = np.pad(vol, [(0, max(0, rd[a] - vs[a])) for a in range(3)], "reflect")
         patches = np.zeros((self.N,) + rd, dtype="uint8")
-        n = 0
-        for z in self.Z_start:
-            for x in self.X_start:
-                for y in self.Y_start:
-                    patches[n] = vol[z:z + rd[0], x:x + rd[1], y:y + rd[2]]
-                    n += 1
+        for n, (_, z, x, y) in enumerate(origins):
+            patches[n] = vol[z:z + rd[0], x:x + rd[1], y:y + rd[2]]
         return patches
 
 
@@ -820,11 +870,17 @@ class PredictSiam:
 
     Frame i is predicted together with its predecessor (frame 0 with frame 1, or with itself in a one-frame movie); every
     pair is normalised on its own (``normalization_mode`` over the two-frame stack), zero-padded (``'constant'``) up to
-    ``resize_dim``, tiled, predicted and stitched by the nan-mean of overlapping uint8 tiles."""
+    ``resize_dim``, tiled, predicted and stitched by the nan-mean of overlapping uint8 tiles.
+
+    ``preprocess='device'`` uploads the movie once and selects every pair's statistics in one batch before the frame loop (a pair is one
+    unit in ``'first'`` / ``'all'``, every image its own in ``'single'``); the host path computes in float64 whatever the input, so the
+    device path equals it bit for bit for every input it accepts (integers, float32, float64 that float32 holds exactly; NaN raises
+    ``ValueError``)."""
 
     def __init__(self, movie, result_name, model_params, resize_dim=None, invert=False, normalization_mode="single",
                  clip_threshold=(0., 99.8), add_tile=0, normalize_result=False, show_progress=True,
-                 device: Union[torch.device, str] = "auto", progress_notifier=None, batch_size=8):
+                 device: Union[torch.device, str] = "auto", progress_notifier=None, batch_size=8, preprocess="host"):
+        _check_preprocess(preprocess)
         self.device = _pick_device(device)
         if isinstance(movie, str):
             import tifffile
@@ -850,15 +906,24 @@ class PredictSiam:
         h, w = self.imgs_shape[1], self.imgs_shape[2]
         stitch = _Stitcher(self.device, 1, (1, max(th, h), max(tw, w)))
         origins = [(0, int(xs), int(ys)) for xs in self.X_start for ys in self.Y_start]
+        if preprocess == "device":
+            # the movie goes up once; every pair's order statistics are selected in one batch before the frame loop (float64 arithmetic on
+            # the values as uploaded, as the host path's ``np.array([prev, cur], dtype=np.float64)``), zero padding written by the kernel
+            fe = DeviceFrontEnd(movie, self.device)
+            fe.normalise_pairs(normalization_mode, clip_threshold)
+            pairs = fe.pair_tiles(self._origins(), self.resize_dim, invert=invert)
         for i in range(self.tif_len):
-            prev = (movie[0] if self.tif_len == 1 else movie[1]) if i == 0 else cur
-            cur = movie[i]
-            pair = normalise_stack(np.array([prev, cur], dtype=np.float64), normalization_mode, clip_threshold, invert).astype("uint8")
-            patches = self._split(pair)
+            if preprocess == "device":
+                patches = pairs.frame(i, self.N)
+            else:
+                prev = (movie[0] if self.tif_len == 1 else movie[1]) if i == 0 else cur
+                cur = movie[i]
+                pair = normalise_stack(np.array([prev, cur], dtype=np.float64), normalization_mode, clip_threshold, invert).astype("uint8")
+                patches = self._split(pair)
             stitch.reset()
             with torch.no_grad():
                 for b in range(0, self.N, batch_size):
-                    both = torch.from_numpy(patches[b:b + batch_size]).to(self.device, non_blocking=True)       # uint8 (cur, prev)
+                    both = _patch_batch(patches, b, b + batch_size, self.device)       # uint8 (cur, prev)
                     q = _quantize_u8(self.model(both[:, 0:1].contiguous(), both[:, 1:2].contiguous())[0])
                     for j in range(q.shape[0]):
                         stitch.add(q[j].unsqueeze(1), origins[b + j])
@@ -866,17 +931,18 @@ class PredictSiam:
         self.imgs_result = torch.stack(frames).cpu().numpy()
         _write(result_name, self.imgs_result)
 
+    def _origins(self):
+        """Tile order of one frame pair as (0, 0, row, column) -- shared by the host ``_split`` and the device front end."""
+        return [(0, 0, int(xs), int(ys)) for xs in self.X_start for ys in self.Y_start]
+
     def _split(self, pair):
         th, tw = self.resize_dim
         h, w = self.imgs_shape[1], self.imgs_shape[2]
         pair = np.pad(pair, ((0, 0), (0, max(0, th - h)), (0, max(0, tw - w))), "constant")
         patches = np.zeros((self.N, 2, th, tw), dtype="uint8")
-        n = 0
-        for xs in self.X_start:
-            for ys in self.Y_start:
-                patches[n, 0] = pair[1][xs:xs + th, ys:ys + tw]          # current frame
-                patches[n, 1] = pair[0][xs:xs + th, ys:ys + tw]          # previous frame
-                n += 1
+        for n, (_, _, xs, ys) in enumerate(self._origins()):
+            patches[n, 0] = pair[1][xs:xs + th, ys:ys + tw]          # current frame
+            patches[n, 1] = pair[0][xs:xs + th, ys:ys + tw]          # previous frame
         return patches
 
 
@@ -886,24 +952,43 @@ class PredictMo3d:
     Float normalisation to [0, 1] (no uint8 step), patches of ``min(volume, max_patch_size)`` on a stride of
     ``patch * (1 - overlap_factor)`` plus a last patch flush with the border, batches of ``batch_size``, outputs kept as
     float32 per head, weighted blending with the reference's linear ramps over ``blend_margin`` voxels at interior patch
-    faces (built exactly as upstream assigns them: plane by plane, later axes overwriting earlier ones)."""
+    faces (built exactly as upstream assigns them: plane by plane, later axes overwriting earlier ones).
+
+    ``preprocess='device'``: normalisation and patch cutting in HBM.  The host path computes in numpy float32 (its percentiles included); the
+    device path evaluates the same formula in fp64 on the uploaded values (uint8 / uint16 / int16 as they are, anything else after the
+    host path's own cast to float32) and rounds to float32 once, so the two can differ in the last bit of a patch value.  NaN raises
+    ``ValueError`` (use ``preprocess='host'``)."""
 
     def __init__(self, imgs, model_params, result_path=None, network=MultiOutputUnet3D, max_patch_size=(64, 256, 256),
                  overlap_factor=0.1, batch_size=1, normalization_mode="single", clip_threshold=(0., 99.98), add_tile=0,
-                 compress_tif=False, show_progress=True, device: Union[torch.device, str] = "auto", progress_notifier=None):
+                 compress_tif=False, show_progress=True, device: Union[torch.device, str] = "auto", progress_notifier=None,
+                 preprocess="host"):
+        _check_preprocess(preprocess)
         self.device = _pick_device(device)
         if isinstance(imgs, str):
             import tifffile
             imgs = tifffile.imread(imgs)
         self.max_patch_size, self.overlap_factor, self.batch_size = max_patch_size, overlap_factor, batch_size
-        imgs = np.array(imgs, dtype="float32")
-        if imgs.ndim == 3:
-            imgs = imgs[None]
-        elif imgs.ndim != 4:
-            raise ValueError(f"Unsupported input shape: {imgs.shape}")
-        self.imgs_shape = imgs.shape
-        imgs = self._preprocess(imgs, normalization_mode, clip_threshold)
-        patches = self._split(imgs)
+        raw = np.asarray(imgs)
+        if preprocess == "host" or not DeviceFrontEnd.native(raw.dtype):
+            imgs = raw = np.array(imgs, dtype="float32")                 # the host path's cast; the device path keeps small integers as they are
+        if raw.ndim == 3:
+            imgs = raw = raw[None]
+        elif raw.ndim != 4:
+            raise ValueError(f"Unsupported input shape: {raw.shape}")
+        self.imgs_shape = raw.shape
+        if preprocess == "device":
+            # the host path normalises in numpy float32 (percentiles included); here the same formulas run in fp64 on the uploaded values
+            # and are rounded to float32 once
+            if normalization_mode not in ("single", "first", "all"):
+                raise ValueError(f"Invalid normalization mode: {normalization_mode}")
+            fe = DeviceFrontEnd(raw, self.device, depth=raw.shape[1])
+            fe.normalise(normalization_mode, clip_threshold, family="minmax_eps" if normalization_mode == "single" else "lohi_eps")
+            origins = self._origins(raw.shape)
+            patches = fe.tiles(origins, self.patch_size, out="float32", view=(1,) + self.patch_size)
+        else:
+            imgs = self._preprocess(imgs, normalization_mode, clip_threshold)
+            patches = self._split(imgs)
         mp = self.model_params = _load_params(model_params, self.device)
         self.model = network(in_channels=mp["in_channels"], n_filter=mp["n_filter"], output_heads=mp["output_heads"],
                              use_interpolation=mp.get("use_interpolation", True)).to(self.device)
@@ -925,8 +1010,10 @@ class PredictMo3d:
             return imgs
         raise ValueError(f"Invalid normalization mode: {mode}")
 
-    def _split(self, imgs):
-        nvol, D, H, W = imgs.shape
+    def _origins(self, shape):
+        """Patch grid of ``multi_output_unet3d/predict.py:162-201``: sets ``patch_size``, the start lists and the counts and returns the
+        patch order as (volume, z, y, x) -- shared by the host ``_split`` and the device front end."""
+        nvol, D, H, W = shape
         self.patch_size = ps = tuple(min(a, b) for a, b in zip((D, H, W), self.max_patch_size))
         stride = [max(1, int(s * (1 - self.overlap_factor))) for s in ps]
 
@@ -938,9 +1025,12 @@ class PredictMo3d:
         self.Z_start, self.Y_start, self.X_start = starts(D, ps[0], stride[0]), starts(H, ps[1], stride[1]), starts(W, ps[2], stride[2])
         self.N_z, self.N_y, self.N_x = len(self.Z_start), len(self.Y_start), len(self.X_start)
         self.N_per_vol = self.N_z * self.N_y * self.N_x
-        out = [imgs[v, z:z + ps[0], y:y + ps[1], x:x + ps[2]] for v in range(nvol) for z in self.Z_start for y in self.Y_start
-               for x in self.X_start]
-        return np.stack(out)[:, None]
+        return [(v, z, y, x) for v in range(nvol) for z in self.Z_start for y in self.Y_start for x in self.X_start]
+
+    def _split(self, imgs):
+        origins = self._origins(imgs.shape)
+        ps = self.patch_size
+        return np.stack([imgs[v, z:z + ps[0], y:y + ps[1], x:x + ps[2]] for v, z, y, x in origins])[:, None]
 
     def _weights(self, flags, shape, blend_margin):
         """Blend mask of one patch; ``flags`` = (front, back, top, bottom, left, right) interior faces.  Restates the
@@ -985,7 +1075,7 @@ class PredictMo3d:
         index = [(v, zi, yi, xi) for v in range(nvol) for zi in range(self.N_z) for yi in range(self.N_y) for xi in range(self.N_x)]
         with torch.no_grad():
             for b in range(0, len(patches), batch_size):
-                preds = self.model(torch.from_numpy(np.ascontiguousarray(patches[b:b + batch_size])).to(self.device, non_blocking=True))
+                preds = self.model(_patch_batch(patches, b, b + batch_size, self.device))
                 for j in range(min(batch_size, len(patches) - b)):
                     v, zi, yi, xi = index[b + j]
                     wt = weight_of(zi, yi, xi)
@@ -1008,25 +1098,39 @@ class PredictMo2d:
 
     As upstream, patches are cut on a stride of ``X_start[1]`` / ``Y_start[1]`` (``:180-181``) and stitched at ``X_start`` / ``Y_start``;
     the first ``N_x x N_y`` windows of that stride are taken.  ``result`` is a dict of arrays per head, or ``None`` when ``result_path``
-    is given and the heads were written to ``result_path + name + '.tif'``."""
+    is given and the heads were written to ``result_path + name + '.tif'``.
+
+    ``preprocess='device'``: as for ``PredictMo3d`` -- fp64 on the device, rounded to float32 once, against numpy float32 on the host; NaN
+    raises ``ValueError``."""
 
     safe_margin = 20
 
     def __init__(self, imgs, model_params, result_path=None, network=MultiOutputNestedUNet, max_patch_size=(1024, 1024), batch_size=1,
                  normalization_mode="single", clip_threshold=(0., 99.98), add_tile=0, compress_tif=False, show_progress=True,
-                 device: Union[torch.device, str] = "auto", progress_notifier=None):
+                 device: Union[torch.device, str] = "auto", progress_notifier=None, preprocess="host"):
+        _check_preprocess(preprocess)
         self.device = _pick_device(device)
         if isinstance(imgs, str):
             import tifffile
             imgs = tifffile.imread(imgs)
         self.max_patch_size, self.batch_size, self.add_tile = max_patch_size, batch_size, add_tile
         self.normalization_mode, self.clip_threshold, self.result_path = normalization_mode, clip_threshold, result_path
-        imgs = np.array(imgs, dtype="float32")
-        if imgs.ndim == 2:
-            imgs = imgs[None]
-        self.imgs_shape = imgs.shape
-        imgs = self._preprocess(imgs, normalization_mode, clip_threshold)
-        patches = self._split(imgs)
+        raw = np.asarray(imgs)
+        if preprocess == "host" or not DeviceFrontEnd.native(raw.dtype):
+            imgs = raw = np.array(imgs, dtype="float32")                 # the host path's cast; the device path keeps small integers as they are
+        if raw.ndim == 2:
+            imgs = raw = raw[None]
+        self.imgs_shape = raw.shape
+        if preprocess == "device":
+            # the host path normalises in numpy float32 (percentiles included); here the same formula runs in fp64 on the uploaded values and
+            # is rounded to float32 once
+            fe = DeviceFrontEnd(raw, self.device)
+            fe.normalise(normalization_mode, clip_threshold)
+            origins = self._origins()
+            patches = fe.tiles(origins, (1,) + self.patch_size, out="float32")
+        else:
+            imgs = self._preprocess(imgs, normalization_mode, clip_threshold)
+            patches = self._split(imgs)
         mp = self.model_params = _load_params(model_params, self.device)
         self.model = network(in_channels=mp["in_channels"], n_filter=mp["n_filter"], output_heads=mp["output_heads"],
                              deep_supervision=mp.get("deep_supervision", False), train_mode=False).to(self.device)
@@ -1065,16 +1169,31 @@ class PredictMo2d:
             w[:, -m:] = 0
         return w
 
-    def _split(self, imgs):
-        self.patch_size, self.N_x, self.N_y, (H, W), self.X_start, self.Y_start = self.geometry(self.imgs_shape, self.max_patch_size, self.add_tile)
-        ph, pw = self.patch_size
+    def _strides(self):
+        """``geometry`` into the attributes, and the stride the patches are cut on: ``X_start[1]`` / ``Y_start[1]`` (``predict.py:180-181``)."""
+        self.patch_size, self.N_x, self.N_y, self.padded, self.X_start, self.Y_start = self.geometry(self.imgs_shape, self.max_patch_size, self.add_tile)
         self.N_per_img = self.N_x * self.N_y
         self.N = self.N_per_img * self.imgs_shape[0]
-        imgs = np.pad(imgs, ((0, 0), (0, H - self.imgs_shape[1]), (0, W - self.imgs_shape[2])), "reflect")
         sx = int(self.X_start[1]) if self.N_x > 1 else 1
         sy = int(self.Y_start[1]) if self.N_y > 1 else 1
         if sx < 1 or sy < 1:
             raise ValueError("slice step cannot be zero (add_tile on an image no larger than one patch)")      # as upstream's view[::0]
+        return sx, sy
+
+    def _origins(self):
+        """The windows ``_split`` takes, as (image, 0, row, column) in the reflect-padded stack: the first ``N_x x N_y`` windows of the
+        stride that fit -- what the device front end cuts."""
+        sx, sy = self._strides()
+        (ph, pw), (H, W) = self.patch_size, self.padded
+        rows = list(range(0, H - ph + 1, sx))[:self.N_x]
+        cols = list(range(0, W - pw + 1, sy))[:self.N_y]
+        return [(i, 0, r, c) for i in range(self.imgs_shape[0]) for r in rows for c in cols]
+
+    def _split(self, imgs):
+        sx, sy = self._strides()
+        ph, pw = self.patch_size
+        H, W = self.padded
+        imgs = np.pad(imgs, ((0, 0), (0, H - self.imgs_shape[1]), (0, W - self.imgs_shape[2])), "reflect")
         win = np.lib.stride_tricks.sliding_window_view(imgs, self.patch_size, axis=(1, 2))[:, ::sx, ::sy][:, :self.N_x, :self.N_y]
         return np.ascontiguousarray(win).reshape(-1, ph, pw)
 
@@ -1094,7 +1213,7 @@ class PredictMo2d:
             return wcache[flags]
         with torch.no_grad():
             for b in range(0, patches.shape[0], batch_size):
-                x = torch.from_numpy(patches[b:b + batch_size]).to(self.device, non_blocking=True).view(-1, cin, ph, pw)
+                x = _patch_batch(patches, b, b + batch_size, self.device).view(-1, cin, ph, pw)
                 out = self.model(x)
                 for key in self.target_keys:
                     res = out[key]

@@ -586,6 +586,43 @@ int biu_stitch_finish(const float* acc, const float* wsum, int layers, int chann
                       biu_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The front of the Predict pipelines: percentile clip, rescale and tiling of the raw stack on the device (the numpy stage of
+ * unet/predict.py:122-181, unet3d/predict.py:97-150, siam_unet/predict.py:98-170, multi_output_unet/predict.py:129-181,
+ * multi_output_unet3d/predict.py:99-160).  Everything is enqueued on `stream`; nothing synchronises.
+ *
+ *   biu_order_stats  : exact order statistics.  x holds `segments` runs of n elements of type `elem`, run s starting at element
+ *                      s * stride (stride = n: the array cut into equal parts; stride < n: overlapping windows, as the frame pairs of
+ *                      the Siamese predictor).  out[s * nranks + r] = the value at 0-based position ranks[r] of run s in sorted order,
+ *                      as fp64 (ranks is a host array, the same for every run; nranks <= 8).  float32 sorts as np.sort does: IEEE order
+ *                      (-0.0 and +0.0 compare equal to the caller), NaN last.  *nan_count (device) = NaN elements met, summed over
+ *                      the runs; 0 for integer input.  Radix select on an order-preserving 32-bit key, 8 bits per pass, integer
+ *                      atomics only: the result is deterministic.  workspace: biu_order_stats_workspace(segments, nranks) bytes of
+ *                      device memory, 256-byte aligned.  n <= 2^31, segments <= 65535.
+ *   biu_prep_finalize: stats [units][6] = minimum, maximum, x_k, x_k+1 of the lower percentile, x_k, x_k+1 of the upper (k =
+ *                      floor(q/100 * (n - 1)), and k + 1 replaced by k where q/100 * (n - 1) >= n - 1) -> scalars [units][4] = lo, hi, sub,
+ *                      den.  lo / hi restate np.percentile(method='linear') in fp64 bit for bit; the fused kernel then computes
+ *                      (clip(v, lo, hi) - sub) / den:
+ *                        BIU_PREP_MINMAX      sub = min(clip), den = max(clip) - min(clip)           (unet, unet3d, siam_unet, multi_output_unet)
+ *                        BIU_PREP_MINMAX_EPS  the same with den + 1e-8                               (multi_output_unet3d 'single')
+ *                        BIU_PREP_LOHI_EPS    sub = lo, den = hi - lo + 1e-8                         (multi_output_unet3d 'first' / 'all')
+ *   biu_prep_tiles   : src [planes][height][width] of type `elem`; origins (device) = ntiles records (unit, z0, y0, x0); tile t is
+ *                      out[t][td][th][tw] read from planes z0.., rows y0.., columns x0.. and normalised with scalars[unit].  `depth`
+ *                      divides planes: a tile stays inside the block of `depth` planes that holds z0 (2-D stacks: depth = td = 1).
+ *                      Beyond the source, pad_zero = 0 reflects as numpy 'reflect' does (no edge repeat, period 2 (n - 1), repeatedly),
+ *                      pad_zero != 0 writes 0.  out_f32 = 0: uint8, `(a * 255)` (`255 - a * 255` with invert) truncated; out_f32 != 0:
+ *                      float32, rounded once from fp64.  Pixel arithmetic is fp64, one rounding per operation, never contracted.
+ * ---------------------------------------------------------------------------------------------- */
+enum { BIU_ELEM_U8 = 0, BIU_ELEM_U16 = 1, BIU_ELEM_I16 = 2, BIU_ELEM_F32 = 3 };
+enum { BIU_PREP_MINMAX = 0, BIU_PREP_MINMAX_EPS = 1, BIU_PREP_LOHI_EPS = 2 };
+size_t biu_order_stats_workspace(long long segments, int nranks);
+int biu_order_stats(const void* x, int elem, long long segments, long long n, long long stride, const long long* ranks, int nranks,
+                    double* out, long long* nan_count, void* workspace, size_t workspace_bytes, biu_stream stream);
+int biu_prep_finalize(const double* stats, int units, long long n, double q_lo, double q_hi, int family, double* scalars,
+                      biu_stream stream);
+int biu_prep_tiles(const void* src, int elem, int planes, int depth, int height, int width, const int* origins, int ntiles, int td, int th,
+                   int tw, const double* scalars, int units, int pad_zero, int out_f32, int invert, void* out, biu_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
  * On-the-fly training augmentation of uint8 tile batches (the albumentations pipelines of unet/data.py:217-245,
  * siam_unet/data.py:236-243, unet3d/data.py:209-239, which the reference runs offline)
  *

@@ -1,0 +1,261 @@
+"""The device front end of the Predict pipelines (``csrc/biu_prep.hip`` through the C ABI and ``bio_image_unet_amd/preprocess.py``): exact
+order statistics against ``np.sort``, the NaN count, and the fused normalise + tile kernel against the host lines of the five ``Predict``
+classes -- bit for bit (``np.array_equal``) everywhere: the selection is exact and every pixel operation is one correctly rounded fp64
+operation in the host's order, so no tolerance is involved."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from bio_image_unet_amd import preprocess as P  # noqa: E402
+from bio_image_unet_amd import workflow as Wf  # noqa: E402
+from bio_image_unet_amd._lib import lib  # noqa: E402
+
+LENGTHS = [1, 2, 255, 4099, 64 * 64 + 3]
+S = 3
+
+
+def _segments(dtype, n):
+    """S = 3 segments of n elements with disjoint value ranges (a slip across a segment boundary changes the answer)."""
+    rng = np.random.default_rng(n)
+    if dtype == "uint8":                  # n >> 256 at the larger lengths: every rank falls inside a run of ties
+        return np.stack([rng.integers(lo, hi, n) for lo, hi in ((0, 80), (85, 170), (175, 256))]).astype(np.uint8)
+    if dtype == "uint16":                 # the high byte decides between segments and inside them; segment 2 is above 32767
+        return np.stack([rng.integers(s * 21000 + 5, s * 21000 + 20000, n) for s in range(3)]).astype(np.uint16)
+    if dtype == "int16":
+        return np.stack([rng.integers(lo, hi, n) for lo, hi in ((-32768, -11000), (-10000, 10000), (11000, 32768))]).astype(np.int16)
+    # float32: segment 0 negative (a cluster that differs only in the lowest mantissa bits, large values, -1.0 exactly),
+    # segment 1 around zero (+-0.0, positive and negative denormals, tiny normals), segment 2 positive with the same kind of cluster
+    ulps = rng.integers(0, 1 << 9, n).astype(np.uint32)
+    neg = (np.float32(-1.5).view(np.uint32) + ulps).view(np.float32)
+    neg[::5] = -rng.random(len(neg[::5]), dtype=np.float32) * 1e6 - 2
+    neg[::11] = -1.0
+    den = (rng.integers(0, 1 << 20, n).astype(np.uint32)).view(np.float32)            # denormals (exponent field 0), 0 included
+    den[::2] *= -1
+    den[::7] = 0.0
+    den[3::7] = -0.0
+    den[5::9] = rng.standard_normal(len(den[5::9])).astype(np.float32) * 1e-30
+    pos = (np.float32(1.5).view(np.uint32) + ulps[::-1]).view(np.float32)
+    pos[::6] = rng.random(len(pos[::6]), dtype=np.float32) * 1e6 + 2
+    out = np.stack([neg, den, pos]).astype(np.float32)
+    assert out[0].max() <= -1 and np.abs(out[1]).max() < 1e-28 and out[2].min() >= 1
+    return out
+
+
+def _ranks(n):
+    return [0, n - 1, n // 2, n // 3, min(n - 1, n // 2 + 1), (n * 998) // 1000]
+
+
+@pytest.mark.parametrize("n", LENGTHS)
+@pytest.mark.parametrize("dtype", ["uint8", "uint16", "int16", "float32"])
+def test_selection_is_exact(dtype, n):
+    x = _segments(dtype, n)
+    ranks = _ranks(n)
+    want = np.stack([np.sort(seg)[ranks] for seg in x]).astype(np.float64)
+    got, nan = P.order_stats(torch.from_numpy(x).cuda(), ranks, segments=S, return_nan_count=True)
+    assert got.dtype == torch.float64 and tuple(got.shape) == (S, len(ranks))
+    assert np.array_equal(got.cpu().numpy(), want), (dtype, n)
+    assert int(nan) == 0
+    # the same data one element further on: the array itself, and so every segment, starts off a 16-byte boundary
+    shifted = torch.from_numpy(np.concatenate([x.reshape(-1)[:1], x.reshape(-1)])).cuda()[1:]
+    assert shifted.data_ptr() % 16 != 0 and shifted.is_contiguous()
+    assert np.array_equal(P.order_stats(shifted, ranks, segments=S).cpu().numpy(), want), (dtype, n, "shifted")
+
+
+def test_selection_over_overlapping_windows():
+    """stride < n: window s covers frames s and s + 1 (the Siamese predictor's pairs)."""
+    m = 1031
+    x = np.random.default_rng(5).integers(0, 65536, 4 * m).astype(np.uint16)
+    ranks = [0, 2 * m - 1, m, m + 1, 17]
+    got = P.order_stats(torch.from_numpy(x).cuda(), ranks, segments=3, n=2 * m, stride=m)
+    want = np.stack([np.sort(x[s * m:s * m + 2 * m])[ranks] for s in range(3)]).astype(np.float64)
+    assert np.array_equal(got.cpu().numpy(), want)
+
+
+def test_selection_is_repeatable_and_eight_ranks():
+    x = _segments("float32", 4099)
+    ranks = [0, 1, 2, 2048, 2049, 4096, 4097, 4098]
+    t = torch.from_numpy(x).cuda()
+    a, b = P.order_stats(t, ranks, segments=S), P.order_stats(t, ranks, segments=S)
+    assert torch.equal(a, b)
+    assert np.array_equal(a.cpu().numpy(), np.stack([np.sort(seg)[ranks] for seg in x]).astype(np.float64))
+
+
+def test_nan_count_and_nan_sorts_last():
+    rng = np.random.default_rng(6)
+    x = rng.standard_normal(3 * 1000).astype(np.float32)
+    planted = rng.choice(x.size, 7, replace=False)
+    x[planted[:4]] = np.nan
+    x[planted[4:]] = np.float32(np.nan) * -1                  # sign bit set
+    x[planted[6]] = np.array([0x7f800001], dtype=np.uint32).view(np.float32)[0]          # signalling pattern
+    ranks = [0, 500, 999]
+    got, nan = P.order_stats(torch.from_numpy(x).cuda(), ranks, segments=3, return_nan_count=True)
+    assert int(nan) == 7
+    want = np.stack([np.sort(x[s * 1000:(s + 1) * 1000])[ranks] for s in range(3)]).astype(np.float64)
+    assert np.array_equal(got.cpu().numpy(), want, equal_nan=True)
+
+
+def test_c_abi_refuses_bad_arguments():
+    x = torch.zeros(100, dtype=torch.uint8, device="cuda")
+    out = torch.empty(2, dtype=torch.float64, device="cuda")
+    nan = torch.empty(1, dtype=torch.int64, device="cuda")
+    n_ws = lib.biu_order_stats_workspace(1, 2)
+    ws = torch.empty(n_ws, dtype=torch.uint8, device="cuda")
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def call(elem, ranks, ws_bytes):
+        return lib.biu_order_stats(C.c_void_p(x.data_ptr()), elem, 1, 100, 100, (C.c_longlong * 2)(*ranks), 2, C.c_void_p(out.data_ptr()),
+                                   C.c_void_p(nan.data_ptr()), C.c_void_p(ws.data_ptr()), ws_bytes, st)
+    assert call(P.ELEM_U8, [0, 100], n_ws) == -1 and b"rank" in lib.biu_last_error()          # BIU_ERR_SHAPE
+    assert call(P.ELEM_U8, [0, 99], n_ws - 1) == -4                                               # BIU_ERR_WORKSPACE
+    assert call(7, [0, 99], n_ws) == -2                                                           # BIU_ERR_UNSUPPORTED
+    assert call(P.ELEM_U8, [0, 99], n_ws) == 0
+    assert out.cpu().tolist() == [0.0, 0.0]
+    with pytest.raises(ValueError):
+        P.order_stats(x, [0], segments=3)                      # 100 elements do not divide into 3
+    with pytest.raises(TypeError):
+        P.order_stats(x.double(), [0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# fused normalise + tile gather against the host lines
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _bare(cls, **attrs):
+    obj = cls.__new__(cls)
+    for k, v in attrs.items():
+        setattr(obj, k, v)
+    return obj
+
+
+def _all(tiles):
+    return tiles.batch(0, len(tiles)).cpu().numpy()
+
+
+STACK_U16 = np.random.default_rng(10).integers(100, 60000, (3, 37, 53)).astype(np.uint16)
+
+
+@pytest.mark.parametrize("clip", [(0., 99.8), (0.2, 99.8)])
+@pytest.mark.parametrize("invert", [False, True])
+@pytest.mark.parametrize("mode", ["single", "first", "all"])
+@pytest.mark.parametrize("tile", [(16, 24), (48, 64)])
+def test_uint8_form_equals_host_normalise_and_split(tile, mode, invert, clip):
+    """``normalise_stack(float64) + Predict2D._split``; 48 x 64 is larger than the 37 x 53 image: reflect on both axes."""
+    x = STACK_U16
+    p = _bare(Wf.Predict2D, imgs_shape=x.shape, resize_dim=tile, add_tile=0)
+    want = p._split(Wf.normalise_stack(x.astype(np.float64), mode, clip, invert))
+    fe = P.DeviceFrontEnd(x, "cuda")
+    fe.normalise(mode, clip)
+    tiles = fe.tiles(p._origins(), (1,) + tile, out="uint8", invert=invert)
+    got = _all(tiles)
+    assert got.dtype == np.uint8 and got.shape == want.shape
+    assert np.array_equal(got, want), (np.abs(got.astype(int) - want.astype(int)).max(), int((got != want).sum()))
+    if len(tiles) > 3:
+        assert np.array_equal(tiles.batch(1, 3).cpu().numpy(), want[1:3])
+
+
+@pytest.mark.parametrize("dtype", ["uint8", "int16", "float32"])
+def test_uint8_form_other_source_types(dtype):
+    """Integer-valued data in the other three element types (float32 holding integers is exact in float64 too); odd tile width: no 16-byte
+    rows, the element-store path."""
+    rng = np.random.default_rng(11)
+    x = {"uint8": lambda: rng.integers(3, 250, (2, 37, 53)), "int16": lambda: rng.integers(-30000, 30000, (2, 37, 53)),
+         "float32": lambda: rng.integers(-5000, 90000, (2, 37, 53))}[dtype]().astype(dtype)
+    for tile in [(16, 24), (20, 21)]:
+        p = _bare(Wf.Predict2D, imgs_shape=x.shape, resize_dim=tile, add_tile=1)
+        want = p._split(Wf.normalise_stack(x.astype(np.float64), "single", (0.2, 99.8), True))
+        fe = P.DeviceFrontEnd(x, "cuda")
+        fe.normalise("single", (0.2, 99.8))
+        assert np.array_equal(_all(fe.tiles(p._origins(), (1,) + tile, out="uint8", invert=True)), want), (dtype, tile)
+
+
+@pytest.mark.parametrize("mode", ["single", "first", "all"])
+@pytest.mark.parametrize("tile", [(16, 24), (48, 64)])
+@pytest.mark.parametrize("frames", [4, 1])
+def test_siam_layout_and_constant_pad(frames, tile, mode):
+    """``PredictSiam``'s host lines per frame: the pair normalised as one float64 stack, cast to uint8, zero-padded, cut into
+    [N, 2, th, tw] with channel 0 the current frame."""
+    movie = np.random.default_rng(12).integers(50, 4000, (frames, 37, 53)).astype(np.uint16)
+    p = _bare(Wf.PredictSiam, imgs_shape=[frames, 37, 53], resize_dim=tile)
+    p.N_x, p.N_y = int(np.ceil(37 / tile[0])), int(np.ceil(53 / tile[1]))
+    p.N = p.N_x * p.N_y
+    p.X_start, p.Y_start = Wf.tile_starts(37, tile[0], p.N_x), Wf.tile_starts(53, tile[1], p.N_y)
+    fe = P.DeviceFrontEnd(movie, "cuda")
+    fe.normalise_pairs(mode, (0.2, 99.8))
+    pairs = fe.pair_tiles(p._origins(), tile, invert=True)
+    for i in range(frames):
+        prev = (movie[0] if frames == 1 else movie[1]) if i == 0 else movie[i - 1]
+        pair = Wf.normalise_stack(np.array([prev, movie[i]], dtype=np.float64), mode, (0.2, 99.8), True).astype("uint8")
+        want = p._split(pair)
+        got = _all(pairs.frame(i, p.N))
+        assert got.shape == want.shape == (p.N, 2) + tile
+        assert np.array_equal(got, want), (i, int((got != want).sum()))
+
+
+@pytest.mark.parametrize("resize_dim", [(8, 16, 16), (24, 16, 16)])
+def test_volume_tiles(resize_dim):
+    """``Predict3D``: whole-volume statistics, 3-D tiles; (24, 16, 16) is deeper than the 20-plane volume: reflect along z."""
+    vol = np.random.default_rng(13).integers(0, 50000, (20, 40, 36)).astype(np.uint16)
+    p = _bare(Wf.Predict3D, vol_shape=vol.shape, resize_dim=resize_dim, add_patch=0)
+    want = p._split(Wf.normalise_stack(vol, "all", (0.2, 99.8), False))
+    fe = P.DeviceFrontEnd(vol, "cuda", depth=20)
+    fe.normalise("all", (0.2, 99.8))
+    got = _all(fe.tiles(p._origins(), resize_dim, out="uint8"))
+    assert got.shape == want.shape and np.array_equal(got, want), int((got != want).sum())
+
+
+@pytest.mark.parametrize("mode", ["single", "first", "all"])
+@pytest.mark.parametrize("max_patch", [(48, 48), (64, 96)])
+def test_float_form_mo2d(mode, max_patch, capsys):
+    """float32 input, float32 patches: bit-equal to the host formula evaluated in float64 and rounded once.  (64, 96) pads the 50 x 80 image
+    by reflection.  The distance to the actual float32 host path is printed (``-s``), not asserted."""
+    x = (np.random.default_rng(14).random((2, 50, 80)) * 900 + 17).astype(np.float32)
+    clip = (0.2, 99.98)
+    p = _bare(Wf.PredictMo2d, imgs_shape=x.shape, max_patch_size=max_patch, add_tile=0)
+    want = p._split(Wf.PredictMo2d._preprocess(x.astype(np.float64), mode, clip)).astype(np.float32)
+    fe = P.DeviceFrontEnd(x, "cuda")
+    fe.normalise(mode, clip)
+    got = _all(fe.tiles(p._origins(), (1,) + p.patch_size, out="float32"))[:, 0]
+    assert got.dtype == np.float32 and np.array_equal(got, want), float(np.abs(got - want).max())
+    host32 = p._split(Wf.PredictMo2d._preprocess(x.copy(), mode, clip))
+    with capsys.disabled():
+        print(f"\n[mo2d {mode} {max_patch}] largest |device - float32 host path| = {np.abs(got - host32).max():.3e}")
+
+
+@pytest.mark.parametrize("mode", ["single", "first", "all"])
+def test_float_form_mo3d(mode, capsys):
+    x = (np.random.default_rng(15).random((2, 10, 20, 18)) * 3000 - 40).astype(np.float32)
+    clip = (0.2, 99.98)
+    p = _bare(Wf.PredictMo3d, max_patch_size=(4, 8, 8), overlap_factor=0.25)
+    want = p._split(Wf.PredictMo3d._preprocess(x.astype(np.float64), mode, clip)).astype(np.float32)
+    fe = P.DeviceFrontEnd(x, "cuda")
+    fe.normalise(mode, clip, family="minmax_eps" if mode == "single" else "lohi_eps")
+    got = _all(fe.tiles(p._origins(x.shape), p.patch_size, out="float32", view=(1,) + p.patch_size))
+    assert got.shape == want.shape and np.array_equal(got, want), float(np.abs(got - want).max())
+    host32 = p._split(Wf.PredictMo3d._preprocess(x.copy(), mode, clip))
+    with capsys.disabled():
+        print(f"\n[mo3d {mode}] largest |device - float32 host path| = {np.abs(got - host32).max():.3e}")
+
+
+def test_front_end_refusals():
+    x = np.random.default_rng(16).random((2, 20, 24)).astype(np.float32)
+    bad = x.copy()
+    bad[1, 3, 4] = np.nan
+    fe = P.DeviceFrontEnd(bad, "cuda")
+    for mode in ("single", "first", "all"):
+        with pytest.raises(ValueError, match='preprocess="host"'):
+            fe.normalise(mode, (0., 99.8))
+    with pytest.raises(ValueError, match='preprocess="host"'):
+        fe.normalise_pairs("all", (0., 99.8))
+    with pytest.raises(ValueError, match='preprocess="host"'):
+        P.DeviceFrontEnd(x.astype(np.float64) + 1e-12, "cuda")           # float64 that float32 cannot hold
+    fe = P.DeviceFrontEnd(x.astype(np.float64), "cuda")                  # float64 that it can
+    with pytest.raises(ValueError, match="not valid"):
+        fe.normalise("every", (0., 99.8))
+    fe.normalise("all", (0., 99.8))
+    with pytest.raises(ValueError, match="outside"):
+        fe.tiles([(0, 0, 30, 0)], (1, 8, 8))
+    with pytest.raises(RuntimeError):
+        P.DeviceFrontEnd(x, "cpu")

@@ -181,6 +181,8 @@ SIGNATURES = {
     "biu_to_nchw": (_I, [_A, _X, _P, _I, _P]),
     "biu_augment_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "biu_augment_f32": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
+    "biu_spline_prefilter_f32": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "biu_augment_f32_cubic": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "biu_augment_vol_f32": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "biu_augment_vol_chunk": (_I, [_I] * 8),
     "biu_philox_u32": (_I, [_P, C.c_longlong, C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, C.c_uint, _P]),

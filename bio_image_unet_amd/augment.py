@@ -286,7 +286,8 @@ class Augmenter(_AugmenterCore):
 # kind       what the kernel does
 # =========  ================================================================================================================
 # "image"    nearest gather, then blur -> shot noise -> Gauss noise -> brightness/contrast (fp32, clipped to [0, 1])
-# "mask"     any scalar target (mask, probability, distance map): bilinear under an arbitrary angle, nearest otherwise
+# "mask"     any scalar target (mask, probability, distance map): bilinear under an arbitrary angle, nearest otherwise;
+#            ``target_interp="cubic"``: the reference's periodic cubic B-spline and its clip instead of the bilinear gather
 # "vector"   plane pairs ``(cos phi, sin phi)``: nearest gather, the pair is rotated by the record's rotation (phi - t)
 # =========  ================================================================================================================
 #
@@ -305,6 +306,7 @@ _F1 = struct.Struct("<f")
 _REC_F32 = struct.Struct("<4I6d10f")
 assert _REC_F32.size == PARAMS_F32_DTYPE.itemsize
 _QUARTER = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))                # (cos, sin) of k quarter turns, exact
+TARGET_INTERP = ("linear", "cubic")                                          # AugmenterF32(target_interp=...)
 
 
 def _f32(v: float) -> float:
@@ -356,7 +358,12 @@ def _pair(v, what):
 
 class AugmenterF32(_AugmenterCore):
     """Draws ``biu_augf_params`` records on the host and runs ``biu_augment_f32`` on device batches of float32 or uint8 fields (the output is
-    always float32, so ``DeviceFeeder``'s augmented buffers are float32 whatever the store holds): the 2-D multi-output family's recipe ``"mo2d"``."""
+    always float32, so ``DeviceFeeder``'s augmented buffers are float32 whatever the store holds): the 2-D multi-output family's recipe ``"mo2d"``.
+
+    ``target_interp``: how "mask" fields are resampled under an arbitrary-angle rotation.  ``"linear"`` (the default) gathers bilinearly;
+    ``"cubic"`` is the reference's ``scipy.ndimage.rotate(order=3, mode='grid-wrap')`` with its clip into the target's own range
+    (``biu_spline_prefilter_f32`` + ``biu_augment_f32_cubic``, three launches for such a field instead of one).  The mode draws no uniform:
+    the records of both are the same, and batches without an arbitrary-angle sample take the one ``biu_augment_f32`` launch either way."""
 
     recipe = "mo2d"
     params_dtype, _rec, n_uniform, blur_flag = PARAMS_F32_DTYPE, _REC_F32, 16, BLUR_F
@@ -366,7 +373,7 @@ class AugmenterF32(_AugmenterCore):
 
     def __init__(self, *, gauss_noise_lims=(0.01, 0.1), shot_noise_lims=(0.001, 0.01), brightness_contrast=(0.1, 0.1), blur_limit=(3, 5),
                  random_rotate: bool = True, scale_limit=(0, 0), seed: int = 0, kinds: Optional[Dict[str, str]] = None,
-                 shape: Optional[Sequence[int]] = None):
+                 shape: Optional[Sequence[int]] = None, target_interp: str = "linear"):
         self.gauss_noise_lims = tuple(float(v) for v in _pair(gauss_noise_lims, "gauss_noise_lims"))
         self.shot_noise_lims = tuple(float(v) for v in _pair(shot_noise_lims, "shot_noise_lims"))
         self.brightness_contrast = tuple(float(v) for v in _pair(brightness_contrast, "brightness_contrast"))
@@ -374,6 +381,10 @@ class AugmenterF32(_AugmenterCore):
         sl = _pair(scale_limit, "scale_limit")
         self.scale_limit = tuple(float(v) for v in ((-sl[0], sl[0]) if np.isscalar(scale_limit) else sl))
         self.random_rotate = bool(random_rotate)
+        if target_interp not in TARGET_INTERP:
+            raise ValueError(f'target_interp "{target_interp}": one of {list(TARGET_INTERP)}')
+        self.target_interp = target_interp
+        self._spline_scratch = {}                # (field name, shape, device) -> (coef, range), see _launch
         if self.blur_limit[1] > MAX_BLUR:
             raise ValueError(f"blur_limit {self.blur_limit}: box kernels above {MAX_BLUR} are not supported")
         self.blur_sizes = [k for k in range(max(3, self.blur_limit[0]), self.blur_limit[1] + 1) if k % 2]
@@ -397,10 +408,15 @@ class AugmenterF32(_AugmenterCore):
     def describe(self) -> dict:
         return {"recipe": self.recipe, "seed": self.seed, "gauss_noise_lims": self.gauss_noise_lims, "shot_noise_lims": self.shot_noise_lims,
                 "brightness_contrast": self.brightness_contrast, "blur_limit": self.blur_limit, "random_rotate": self.random_rotate,
-                "scale_limit": self.scale_limit, "stage_p": dict(STAGE_P_MO2D), "kinds": dict(self.kinds)}
+                "scale_limit": self.scale_limit, "stage_p": dict(STAGE_P_MO2D), "kinds": dict(self.kinds), "target_interp": self.target_interp}
 
     def kind(self, name: str) -> str:
         return self.kinds.get(name, "image" if name == "image" else "vector" if name == "orientation" else "mask")
+
+    def __call__(self, batch, params, epoch, out=None, params_dev=None):
+        # the host knows from the records, as it knows max_blur, whether any sample of the batch takes the cubic path
+        self._any_rot = self.target_interp == "cubic" and bool((np.asarray(params["flags"]) & ROT_F).any())
+        return super().__call__(batch, params, epoch, out, params_dev)
 
     def _packer(self, h, w):
         """``draw``'s record from sixteen uniforms."""
@@ -431,6 +447,20 @@ class AugmenterF32(_AugmenterCore):
         kind = KINDS_F32[self.kind(name)]
         if kind == KIND_VECTOR and planes % 2:
             raise ValueError(f'field "{name}": a vector field holds (cos, sin) plane pairs, got {planes} plane(s)')
+        if kind == KIND_MASK and self._any_rot:
+            # coefficients (the field in fp32) and value range, allocated once per (field, shape, device) and reused: every augmentation
+            # launch of a feeder runs on one stream, so the next batch's prefilter cannot overtake this batch's gather.  One augmenter
+            # serves one feeder (or one caller) at a time.
+            key = (name, tuple(t.shape), t.device)
+            if key not in self._spline_scratch:
+                self._spline_scratch[key] = (torch.empty(t.shape, dtype=torch.float32, device=t.device),
+                                             torch.empty((t.shape[0], 2), dtype=torch.float32, device=t.device))
+            coef, rng = self._spline_scratch[key]
+            args = (t.shape[0], planes, t.shape[-2], t.shape[-1], C.c_void_p(params_dev.data_ptr()), stream)
+            status = lib.biu_spline_prefilter_f32(C.c_void_p(t.data_ptr()), int(t.dtype == torch.uint8), C.c_void_p(coef.data_ptr()),
+                                                  C.c_void_p(rng.data_ptr()), *args)
+            return status or lib.biu_augment_f32_cubic(C.c_void_p(t.data_ptr()), int(t.dtype == torch.uint8), C.c_void_p(coef.data_ptr()),
+                                                       C.c_void_p(rng.data_ptr()), C.c_void_p(dst.data_ptr()), *args)
         return lib.biu_augment_f32(C.c_void_p(t.data_ptr()), int(t.dtype == torch.uint8), C.c_void_p(dst.data_ptr()), t.shape[0], planes,
                                    t.shape[-2], t.shape[-1], kind, C.c_void_p(params_dev.data_ptr()), max_blur if kind == KIND_IMAGE else 0,
                                    self.seed, epoch, field_id(name), stream)

@@ -22,6 +22,7 @@ The 2-D multi-output family's items are float32 (``multi_output_unet/data.py:318
 ``orientation`` target that reaches the network as ``(cos, sin)`` in [-1, 1].  A store field therefore has a dtype, ``"u8"`` (the default) or
 ``"f32"`` (file ``<path>.<field>.f32``, written and read back bit for bit, never scaled); the feeder carries float fields as float32 and
 ``augment.AugmenterF32`` (2-D) or ``augment.AugmenterVol`` (volumes) augments them.  A mixed store (``image`` as u8, targets as f32) keeps the image's PCIe traffic at a quarter.
+``AugmenterF32(target_interp="cubic")`` keeps its spline scratch per field: every augmentation launch of a feeder runs on one stream, so one augmenter serves one feeder.
 """
 from __future__ import annotations
 

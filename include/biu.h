@@ -721,6 +721,34 @@ int biu_augment_f32(const void* src, int src_is_u8, float* dst, int n, int plane
                     int max_blur_k, unsigned long long seed, unsigned epoch, unsigned field_id, biu_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Cubic-spline resampling of MASK fields under an arbitrary-angle rotation: what the reference computes with
+ * scipy.ndimage.rotate(order=3, mode='grid-wrap') followed by its clip (multi_output_unet/data.py:213-242).  Opt-in; two calls replace
+ * the one biu_augment_f32(kind = BIU_AUGF_MASK) call of a field.  src, n, planes, h, w, params: as for biu_augment_f32.
+ *
+ * biu_spline_prefilter_f32, for every sample whose record has BIU_AUGF_ROT (the others' coef and range are left unspecified):
+ *   coef [n, planes, h, w] : coefficients of the periodic cubic B-spline through the loaded values s, per plane, separable, x then y:
+ *                              c[k] = sum over |j| <= BIU_SPLINE_R of sqrt(3) z^|j| s[(k - j) mod len],   z = sqrt(3) - 2
+ *                            the exact prefilter of 'grid-wrap' is the same sum over all integers j; the dropped tail is at most
+ *                            2 sqrt(3) |z|^(R + 1) / (1 - |z|) = 9.0e-10 of max |s| per axis at R = 16, below 2^-26.  fp32 taps (the fp64
+ *                            values rounded once) and fp32 sums: s[k - j] + s[k + j] is formed first, terms are added from |j| = R inwards.
+ *   range [n, 2]           : lo = min, hi = max of the sample's loaded values over all planes (NaN aside), exact
+ * biu_augment_f32_cubic writes dst [n, planes, h, w], never src, coef or range:
+ *   records with BIU_AUGF_ROT : at the fp64 source coordinate (sx, sy) of m, x0 = floor(sx), t = sx - x0, the taps x0 - 1 .. x0 + 2 carry
+ *                            the weights (1 - t)^3 / 6, (3 t^3 - 6 t^2 + 4) / 6, (-3 t^3 + 3 t^2 + 3 t + 1) / 6, t^3 / 6, evaluated in fp64 and
+ *                            rounded once to fp32; likewise in y; v = sum of 4 x 4 coefficients (every index wraps) in fp32, rows first.
+ *                            Then the reference's clip: v = min(max(v, lo), hi) if lo >= 0 and hi <= 1, no clip otherwise.
+ *   other records          : biu_augment_f32's MASK output (nearest gather from src), bit for bit; coef and range are not read.
+ * Three launches (range, prefilter, gather) on `stream`; no atomics, nothing cleared beforehand.  Null pointers, buffers that overlap
+ * (src, coef, range among each other; dst with any of them), unaligned float pointers, non-positive extents and 2^31 elements or more
+ * return a status and launch nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define BIU_SPLINE_R 16      /* the prefilter's taps reach |j| <= 16 per axis */
+int biu_spline_prefilter_f32(const void* src, int src_is_u8, float* coef, float* range, int n, int planes, int h, int w,
+                             const biu_augf_params* params, biu_stream stream);
+int biu_augment_f32_cubic(const void* src, int src_is_u8, const float* coef, const float* range, float* dst, int n, int planes, int h, int w,
+                          const biu_augf_params* params, biu_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
  * On-the-fly training augmentation of float volumes: the 3-D multi-output family (multi_output_unet3d/data.py:152-178, which the
  * reference runs offline through albumentations).  One launch per field per batch; the records are biu_augf_params unchanged.
  *

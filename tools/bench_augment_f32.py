@@ -3,6 +3,7 @@
     python tools/bench_augment_f32.py kernels [--iters 200]
     python tools/bench_augment_f32.py torch   [--iters 50]
     python tools/bench_augment_f32.py steps   [--rounds 6]
+    python tools/bench_augment_f32.py cubic   [--iters 200] [--rounds 6]
 
 kernels : one launch per field per batch, timed with device events around --iters back-to-back launches (launch gaps included), per kind
           (IMAGE with every intensity stage on, with and without the blur; MASK nearest and bilinear; VECTOR), float32 and uint8 sources, at
@@ -11,7 +12,13 @@ torch   : the same pipeline written as the eager torch composition a user would 
           on a wrap-padded tile, torch.poisson / randn_like, clamp), event-timed per batch.
 steps   : what the user pays.  Median synchronised step time of TrainerMo2d (MultiOutputNestedUNet(n_filter=32), batch 4, 256^2, a mask, a
           distance and an orientation head) fed from a mixed u8 / f32 TileStore, A / A / B interleaved in one process: two feeders without
-          augmenter (the spread between two runs of the same thing) and one with.  One model and optimizer serve all three.
+          augmenter (the spread between two runs of the same thing), one with the default augmenter and one with
+          AugmenterF32(target_interp="cubic").  One model and optimizer serve all four.
+cubic   : what the cubic-spline resampling of rotated targets costs over the bilinear gather.  The MASK launch of biu_augment_f32 against
+          biu_spline_prefilter_f32 + biu_augment_f32_cubic (three launches), alternating in one process, --rounds rounds of --iters back-to-back
+          calls each, at 4 x 1 x 256^2 and 4 x 2 x 256^2 with all four samples under an arbitrary angle and with one of four; median and
+          (min .. max) over the rounds.  Then a DeviceFeeder epoch (no training, consumer synchronises per batch) with either augmenter,
+          alternating, ms per batch of 4.
 """
 import argparse
 import ctypes as C
@@ -133,6 +140,56 @@ def torch_compose(a):
             print(f"{name:28s} {f'{n} x {hw}^2':>10s} {us:22.1f}")
 
 
+def _launch_cubic(src, coef, rng, dst, par):
+    n, p, h, w = src.shape
+    st, u8 = C.c_void_p(torch.cuda.current_stream().cuda_stream), int(src.dtype == torch.uint8)
+    check(lib.biu_spline_prefilter_f32(C.c_void_p(src.data_ptr()), u8, C.c_void_p(coef.data_ptr()), C.c_void_p(rng.data_ptr()), n, p, h, w,
+                                       C.c_void_p(par.data_ptr()), st), "spline_prefilter_f32")
+    check(lib.biu_augment_f32_cubic(C.c_void_p(src.data_ptr()), u8, C.c_void_p(coef.data_ptr()), C.c_void_p(rng.data_ptr()), C.c_void_p(dst.data_ptr()),
+                                    n, p, h, w, C.c_void_p(par.data_ptr()), st), "augment_f32_cubic")
+
+
+def _spread(v):
+    return f"{statistics.median(v):9.2f} ({min(v):.2f} .. {max(v):.2f})"
+
+
+def cubic(a):
+    n, hw, geo = 4, 256, dict(scale=1.07, shift=(5, -3))
+    print(f"MASK field, f32 source, us per field per batch: median (min .. max) over {a.rounds} rounds of {a.iters} back-to-back calls, alternating")
+    print(f"{'batch':>16s} {'rotating':>9s} {'bilinear, 1 launch':>30s} {'cubic, 3 launches':>30s} {'ratio':>6s}")
+    for p in (1, 2):
+        for rotating in (4, 1):
+            recs = np.stack([A.record_f32(i, hw, hw, angle=17.3 + 40 * i if i < rotating else None, **geo) for i in range(n)])
+            par = torch.from_numpy(recs.view(np.uint8).copy()).cuda()
+            src = _source(n, p, hw, False)
+            dst, coef = torch.empty_like(src), torch.empty_like(src)
+            rng = torch.empty((n, 2), dtype=torch.float32, device="cuda")
+            lin, cub = [], []
+            for _ in range(a.rounds):
+                lin.append(_timed(lambda i: _launch(src, dst, par, recs, A.KIND_MASK, i), a.iters))
+                cub.append(_timed(lambda i: _launch_cubic(src, coef, rng, dst, par), a.iters))
+            print(f"{f'{n} x {p} x {hw}^2':>16s} {f'{rotating} of {n}':>9s} {_spread(lin):>30s} {_spread(cub):>30s} {statistics.median(cub) / statistics.median(lin):6.2f}")
+    with tempfile.TemporaryDirectory() as tmp:
+        st = _make_store(tmp, 80, (256, 256))
+        idx = list(range(80))
+        feeders = {"linear": DeviceFeeder(st, idx, 4, "cuda", augmenter=A.AugmenterF32.from_store(st, seed=1)),
+                   "cubic": DeviceFeeder(st, idx, 4, "cuda", augmenter=A.AugmenterF32.from_store(st, seed=1, target_interp="cubic"))}
+        times = {k: [] for k in feeders}
+        for rnd in range(a.rounds + 1):                          # round 0 warms up and is dropped
+            for k, fd in feeders.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                batches = 0
+                for _ in fd:
+                    torch.cuda.synchronize()
+                    batches += 1
+                if rnd:
+                    times[k].append((time.perf_counter() - t0) * 1e3 / batches)
+        print(f"DeviceFeeder epoch, 80 tiles of 256^2 (image u8; mask, distance, orientation f32), batch 4, no training: ms per batch, median (min .. max) over {a.rounds} epochs")
+        for k, v in times.items():
+            print(f"  {k:8s} {_spread(v)}")
+
+
 def _make_store(tmp, n, hw):
     fields = {"image": hw, "mask": (1,) + hw, "distance": hw, "orientation": (2,) + hw}
     st = TileStore.create(os.path.join(tmp, "mo2d"), n, fields, {"dim_out": list(hw), "scale_limit": [-0.1, 0.1]},
@@ -158,7 +215,8 @@ def steps(a):
                          save_dir=os.path.join(tmp, "out"), device="cuda")
         idx = tr.train_loader.indices
         feeders = {"A1 (no augmenter)": DeviceFeeder(st, idx, 4, "cuda"), "A2 (no augmenter)": DeviceFeeder(st, idx, 4, "cuda"),
-                   "B  (augmenter)": DeviceFeeder(st, idx, 4, "cuda", augmenter=A.AugmenterF32.from_store(st, seed=1))}
+                   "B  (augmenter)": DeviceFeeder(st, idx, 4, "cuda", augmenter=A.AugmenterF32.from_store(st, seed=1)),
+                   "C  (cubic targets)": DeviceFeeder(st, idx, 4, "cuda", augmenter=A.AugmenterF32.from_store(st, seed=1, target_interp="cubic"))}
         times = {k: [] for k in feeders}
         for rnd in range(a.rounds + 1):                          # round 0 warms every shape up and is dropped
             for k, fd in feeders.items():
@@ -183,13 +241,13 @@ def steps(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["kernels", "steps", "torch"])
+    ap.add_argument("mode", choices=["kernels", "steps", "torch", "cubic"])
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=6)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
     print("python tools/bench_augment_f32.py " + " ".join(sys.argv[1:]))
-    {"kernels": kernels, "steps": steps, "torch": torch_compose}[a.mode](a)
+    {"kernels": kernels, "steps": steps, "torch": torch_compose, "cubic": cubic}[a.mode](a)
 
 
 if __name__ == "__main__":

@@ -178,6 +178,10 @@ SIGNATURES = {
     "biu_order_stats": (_I, [_P, _I, C.c_longlong, C.c_longlong, C.c_longlong, C.POINTER(C.c_longlong), _I, _P, _P, _P, _Z, _P]),
     "biu_prep_finalize": (_I, [_P, _I, C.c_longlong, _D, _D, _I, _P, _P]),
     "biu_prep_tiles": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "biu_lut_u8": (_I, [_P, _P, _P, C.c_longlong, _P]),
+    "biu_morph_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "biu_thin_step_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "biu_tile_gather_u8": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     "biu_to_nchw": (_I, [_A, _X, _P, _I, _P]),
     "biu_augment_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "biu_augment_f32": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),

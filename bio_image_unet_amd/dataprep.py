@@ -1,0 +1,364 @@
+"""From raw images and label masks to a training ``TileStore`` on the device (``csrc/biu_dataprep.hip``, ``csrc/biu_prep.hip``).
+
+What is left of the reference's ``DataProcess`` for the three uint8 families once augmentation runs on the fly (``Trainer(..., augment=True)``):
+percentile normalisation of the images to bytes, the mask edit (skeletonise, erosion or dilation with a disk or square footprint, invert)
+and the tile split.  ``prepare_unet`` / ``prepare_unet3d`` / ``prepare_siam`` take in-memory arrays, run every pixel operation in HBM and
+return an open ``feed.TileStore`` of un-augmented uint8 tiles whose ``attrs`` carry ``dim_out``, ``clip_threshold`` and the augmentation
+limits -- ``Trainer(store, ..., augment=True)`` needs nothing else.
+
+Contract (what the tests hold it to; every comparison is an equality)
+
+* Images: ``DeviceFrontEnd(...).normalise('single', clip_threshold)`` and ``tiles(..., out='uint8')`` as they stand, one item -- all its
+  channels or planes, or both frames of a Siamese pair -- as one unit.  That is fp64 arithmetic from the uploaded values; the reference
+  computes in float32, so the truncation can differ by one grey level on isolated pixels (DESIGN).
+* ``morph``: grey erosion / dilation with ``disk(r)`` = ``{dy^2 + dx^2 <= r^2}`` (1 <= r <= 7) or ``square(w)`` (1 <= w <= 15), border and
+  even-footprint convention of ``scipy.ndimage.grey_erosion`` / ``grey_dilation(footprint=..., mode='reflect')``.
+* ``thin``: Zhang-Suen thinning as ``thin_table`` states it, pixels outside the plane 0, both sub-iterations judged on the state before
+  them, iterated to the fixed point.  It is defined by these rules, not pinned to ``skimage.morphology.skeletonize``.
+* ``gather``: tiles with ``np.pad(..., 'reflect')`` beyond the far end (``preprocess.reflect_index``), optional ``255 - v``.
+* The split (``split_starts``, ``origins_2d``, ``origins_3d``) is the reference's, ``add_patch`` quirk of ``unet3d/data.py:188-190`` included.
+* Masks are uint8; a bool mask is taken as 0 / 255.  The reference's ``int8`` round trip of masks is the identity on bytes.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from ._lib import check, lib
+from .feed import TileStore
+from .preprocess import DeviceFrontEnd
+from .utils import get_device
+
+ERODE, DILATE = 0, 1
+FOOTPRINTS = {"disk": 0, "square": 1}
+THIN_BLOCK = 8                  # full iterations enqueued between two reads of the cleared-pixel counter
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+# ---- host: the thinning table and the split geometry -------------------------------------------------------------------------------------
+def thin_table() -> np.ndarray:
+    """The 256-entry table ``biu_thin_step_u8`` reads, built from the Zhang-Suen rules.  Entry ``n`` describes the neighbourhood with
+    P2 (north) in bit 0 of ``n`` and then clockwise P3 (NE), P4 (E), P5 (SE), P6 (S), P7 (SW), P8 (W), P9 (NW) in bits 1..7.  With
+    B = set neighbours and A = 0 -> 1 steps in the cycle P2, P3, ..., P9, P2, a set pixel is cleared if 2 <= B <= 6, A == 1 and
+
+        first sub-iteration  (bit 0 of the entry):  P2 P4 P6 == 0 and P4 P6 P8 == 0
+        second sub-iteration (bit 1 of the entry):  P2 P4 P8 == 0 and P2 P6 P8 == 0"""
+    tab = np.zeros(256, dtype=np.uint8)
+    for n in range(256):
+        p = [(n >> k) & 1 for k in range(8)]                 # p[0] = P2 ... p[7] = P9
+        b = sum(p)
+        a = sum(1 for k in range(8) if p[k] == 0 and p[(k + 1) % 8] == 1)
+        if not (2 <= b <= 6 and a == 1):
+            continue
+        p2, p4, p6, p8 = p[0], p[2], p[4], p[6]
+        first = p2 * p4 * p6 == 0 and p4 * p6 * p8 == 0
+        second = p2 * p4 * p8 == 0 and p2 * p6 * p8 == 0
+        tab[n] = int(first) | (int(second) << 1)
+    return tab
+
+
+def split_starts(extent: int, dim: int, add: int = 0) -> np.ndarray:
+    """Tile origins along one axis as the reference's ``__split`` computes them: the axis is reflect-padded to ``dim`` where it is shorter,
+    ``N = ceil(extent / dim)``, ``N += add`` if ``N > 1``, origins ``np.linspace(0, extent - dim, N).astype('int16')``."""
+    extent = max(int(extent), int(dim))
+    n = int(np.ceil(extent / dim))
+    n += add if n > 1 else 0
+    return np.linspace(0, extent - dim, n).astype("int16")
+
+
+def origins_2d(shape, dim_out, add_tile: int = 0):
+    """(row, column) of every tile of an ``[H, W]`` image in the reference's loop order (rows outer)."""
+    ys, xs = split_starts(shape[0], dim_out[0], add_tile), split_starts(shape[1], dim_out[1], add_tile)
+    return [(int(y), int(x)) for y in ys for x in xs]
+
+
+def origins_3d(shape, dim_out, add_patch: int = 0):
+    """(z, row, column) of every patch of a ``[D, H, W]`` volume, ``unet3d/data.py:185-200`` as written: ``N_x`` grows by ``add_patch`` when
+    ``N_z > 1`` and again when the grown ``N_x > 1``; ``N_y`` grows when ``N_y > 1``; ``N_z`` never grows."""
+    ext = [max(int(e), int(d)) for e, d in zip(shape, dim_out)]
+    n_z, n_x, n_y = (int(np.ceil(e / d)) for e, d in zip(ext, dim_out))
+    n_x += add_patch if n_z > 1 else 0
+    n_x += add_patch if n_x > 1 else 0
+    n_y += add_patch if n_y > 1 else 0
+    zs, xs, ys = (np.linspace(0, e - d, n).astype("int16") for e, d, n in zip(ext, dim_out, (n_z, n_x, n_y)))
+    return [(int(z), int(x), int(y)) for z in zs for x in xs for y in ys]
+
+
+# ---- device: the four kernels --------------------------------------------------------------------------------------------------------------
+def _planes(x: torch.Tensor, what: str) -> torch.Tensor:
+    if not (isinstance(x, torch.Tensor) and x.is_cuda):
+        raise RuntimeError(f"{what} needs a tensor on the GPU; there is no CPU path")
+    if x.dtype != torch.uint8 or x.dim() != 3 or x.numel() == 0:
+        raise ValueError(f"{what}: need a non-empty uint8 tensor [planes, H, W], got {x.dtype} {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def lut(x: torch.Tensor, table, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``table[x]`` for a uint8 device tensor (``biu_lut_u8``); ``table``: 256 values in 0..255.  ``out`` may be ``x`` itself."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()):
+        raise ValueError("lut: need a contiguous uint8 tensor on the GPU")
+    tab = np.asarray(table)
+    if tab.shape != (256,) or tab.min() < 0 or tab.max() > 255:
+        raise ValueError("lut: the table holds 256 values in 0..255")
+    out = torch.empty_like(x) if out is None else out
+    if x.numel() == 0:
+        return out
+    with torch.cuda.device(x.device):
+        t = torch.from_numpy(tab.astype(np.uint8)).to(x.device)
+        check(lib.biu_lut_u8(_ptr(x), _ptr(t), _ptr(out), x.numel(), _stream()), "lut_u8")
+    return out
+
+
+def morph(x: torch.Tensor, op: str, kernel: str, size: int) -> torch.Tensor:
+    """Grey ``'erosion'`` or ``'dilation'`` of every plane of ``x`` ``[planes, H, W]`` (uint8, on the GPU) with ``disk(size)`` or
+    ``square(size)`` (``biu_morph_u8``); enqueued on the current stream."""
+    if op not in ("erosion", "dilation"):
+        raise ValueError(f"morph: operation {op} unknown!")
+    if kernel not in FOOTPRINTS:
+        raise ValueError(f"Dilate kernel {kernel} unknown!")
+    x = _planes(x, "morph")
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        check(lib.biu_morph_u8(_ptr(x), _ptr(out), x.shape[0], x.shape[1], x.shape[2], ERODE if op == "erosion" else DILATE, FOOTPRINTS[kernel],
+                               int(size), _stream()), "morph_u8")
+    return out
+
+
+def thin(x: torch.Tensor, block: int = THIN_BLOCK) -> torch.Tensor:
+    """Zhang-Suen thinning of every plane of ``x`` ``[planes, H, W]`` (uint8 on the GPU, nonzero = set) to its fixed point; returns 0 / 1 bytes.
+
+    Launch plan: one launch per sub-iteration, ping-pong between two buffers (the kernel boundary is the only synchronisation between
+    workgroups).  ``block`` full iterations are enqueued, then the counter the launches added their cleared pixels to is read once; the
+    loop stops when a block cleared nothing.  A converged image is a fixed point of both sub-iterations, so the result does not depend on
+    ``block``.  Every iteration before convergence clears at least one pixel, so (foreground + 1) iterations always suffice: a block that
+    would start beyond them (beyond ``foreground + block - 1`` in whole blocks) raises ``RuntimeError`` instead."""
+    x = _planes(x, "thin")
+    block = int(block)
+    if block < 1:
+        raise ValueError("thin: block >= 1")
+    with torch.cuda.device(x.device):
+        table = torch.from_numpy(thin_table()).to(x.device)
+        a, b = torch.empty_like(x), torch.empty_like(x)
+        counter = torch.zeros((1,), dtype=torch.int64, device=x.device)
+        foreground = int(torch.count_nonzero(x).item())
+        args = (x.shape[0], x.shape[1], x.shape[2])
+        src, done = x, 0
+        while True:
+            if done > foreground + block - 1:
+                raise RuntimeError(f"thin: no fixed point after {done} iterations of an image with {foreground} foreground pixels")
+            counter.zero_()
+            for _ in range(block):
+                check(lib.biu_thin_step_u8(_ptr(src), _ptr(a), *args, 0, _ptr(table), _ptr(counter), _stream()), "thin_step_u8")
+                check(lib.biu_thin_step_u8(_ptr(a), _ptr(b), *args, 1, _ptr(table), _ptr(counter), _stream()), "thin_step_u8")
+                src = b
+            done += block
+            if int(counter.item()) == 0:
+                return b
+
+
+def gather(x: torch.Tensor, depth: int, origins, tile, invert: bool = False) -> torch.Tensor:
+    """Tiles ``[len(origins), td, th, tw]`` of the uint8 stack ``x`` ``[planes, H, W]`` (``biu_tile_gather_u8``): ``origins`` are (plane, row,
+    column) with the plane counted over the whole stack; a tile stays inside the block of ``depth`` planes that holds its first plane and
+    reflects beyond the far ends as ``np.pad(..., 'reflect')`` does.  ``invert`` writes ``255 - v``."""
+    x = _planes(x, "gather")
+    td, th, tw = (int(t) for t in tile)
+    rec = np.asarray([(0, z, y, c) for z, y, c in origins], dtype=np.int64).reshape(-1, 4)
+    if depth < 1 or x.shape[0] % depth or min(td, th, tw) < 1:
+        raise ValueError(f"gather: depth {depth} does not divide {x.shape[0]} planes, or an empty tile {tile}")
+    if rec.size == 0 or rec.min() < 0 or rec.max() >= 2 ** 30 or (rec[:, 1] >= x.shape[0]).any():
+        raise ValueError("tile origins outside the stack")
+    out = torch.empty((rec.shape[0], td, th, tw), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        dev = torch.from_numpy(np.ascontiguousarray(rec.astype(np.int32))).to(x.device)
+        check(lib.biu_tile_gather_u8(_ptr(x), x.shape[0], int(depth), x.shape[1], x.shape[2], _ptr(dev), rec.shape[0], td, th, tw,
+                                     int(bool(invert)), _ptr(out), _stream()), "tile_gather_u8")
+    return out
+
+
+# ---- the mask edit -------------------------------------------------------------------------------------------------------------------------
+_V = np.arange(256)
+_TIMES_255 = np.where(_V != 0, 255, 0)
+
+
+def edit_mask(m: torch.Tensor, skeletonize: bool, dilate_mask: int, dilate_kernel: str) -> torch.Tensor:
+    """``unet`` / ``unet3d`` (``unet/data.py:148-161``), every plane by itself: binarise ``> 1``, thin, ``x 255`` if ``skeletonize``;
+    ``dilate_mask > 0`` ERODES with ``kernel(dilate_mask)``, ``< 0`` dilates with ``kernel(-dilate_mask)`` (the reference's sign).  The
+    final ``255 - v`` of ``invert`` commutes with the tile gather and rides in it."""
+    if skeletonize:
+        m = lut(thin(lut(m, _V > 1)), _TIMES_255)
+    if dilate_mask > 0:
+        m = morph(m, "erosion", dilate_kernel, dilate_mask)
+    elif dilate_mask < 0:
+        m = morph(m, "dilation", dilate_kernel, -dilate_mask)
+    return m
+
+
+def edit_mask_siam(m: torch.Tensor, invert_masks: bool, threshold_masks, skeletonize: bool, dilate_mask: int, dilate_kernel: str) -> torch.Tensor:
+    """``siam_unet/data.py:162-179``: invert, threshold (``>= t`` -> 255, else 0), skeletonise (``> 1`` -> 1, thin what is not 0, ``x 255``),
+    then ``dilate_mask > 0`` DILATES and ``< 0`` erodes -- the opposite sign of the other two families.  The pointwise steps are one table."""
+    v = _V.copy()
+    if invert_masks:
+        v = 255 - v
+    if threshold_masks is not None:
+        v = np.where(v >= threshold_masks, 255, 0)
+    if skeletonize:
+        v = np.where(v > 1, 1, v) != 0
+    if invert_masks or threshold_masks is not None or skeletonize:
+        m = lut(m, v)
+    if skeletonize:
+        m = lut(thin(m), _TIMES_255)
+    if dilate_mask > 0:
+        m = morph(m, "dilation", dilate_kernel, dilate_mask)
+    elif dilate_mask < 0:
+        m = morph(m, "erosion", dilate_kernel, -dilate_mask)
+    return m
+
+
+# ---- the three entry points ----------------------------------------------------------------------------------------------------------------
+def _load(item) -> np.ndarray:
+    if isinstance(item, (str, os.PathLike)):
+        import tifffile                                       # optional, as for Predict2D: arrays need nothing
+        return tifffile.imread(os.fspath(item))
+    return np.asarray(item)
+
+
+def _mask_u8(m: np.ndarray) -> np.ndarray:
+    if m.dtype == np.bool_:
+        return m.astype(np.uint8) * 255
+    if m.dtype != np.uint8:
+        raise TypeError(f"masks are uint8 or bool arrays, got {m.dtype}")
+    return m
+
+
+def _check_common(images, masks, dilate_kernel):
+    if len(masks) != len(images):
+        raise ValueError("Number of ground truth does not match number of image stacks")
+    if dilate_kernel not in FOOTPRINTS:
+        raise ValueError(f"Dilate kernel {dilate_kernel} unknown!")
+    if len(images) == 0:
+        raise ValueError("no images")
+
+
+def _device(device) -> torch.device:
+    device = get_device() if device == "auto" else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"data preparation runs on the GPU (biu_morph_u8, biu_thin_step_u8, biu_tile_gather_u8); got device '{device}'")
+    return device
+
+
+def _attrs(dim_out, clip_threshold, **limits):
+    plain = lambda v: [plain(e) for e in v] if isinstance(v, (tuple, list)) else v
+    return {"dim_out": [int(d) for d in dim_out], "clip_threshold": plain(clip_threshold), **{k: plain(v) for k, v in limits.items()}}
+
+
+def _image_tiles(unit: np.ndarray, device, clip_threshold, origins, tile, view) -> np.ndarray:
+    """``unit`` ``[planes, H, W]`` normalised as one image; ``origins``: (plane, row, column) per tile."""
+    fe = DeviceFrontEnd(unit, device, depth=unit.shape[0])
+    fe.normalise("single", clip_threshold)
+    t = fe.tiles([(0, z, y, x) for z, y, x in origins], tile, out="uint8", view=view)
+    return t.batch(0, len(t)).cpu().numpy()
+
+
+def prepare_unet(images: Sequence, masks: Sequence, path: str, dim_out=(256, 256), in_channels: int = 1, out_channels: int = 1, dilate_mask: int = 0,
+                 dilate_kernel: str = "disk", add_tile: int = 0, invert: bool = False, skeletonize: bool = False, clip_threshold=(0.2, 99.8),
+                 shiftscalerotate=(0, 0, 0), noise_lims=(0.5, 1.2), brightness_contrast=(0.25, 0.25), blur_limit=(3, 7), device="auto") -> TileStore:
+    """``bio_image_unet.unet.DataProcess`` up to its split (``unet/data.py:124-215``) from arrays: ``images`` ``[H, W]`` or ``[C, H, W]`` of any
+    dtype the device front end uploads, ``masks`` ``[H, W]`` or ``[C, H, W]`` uint8 or bool, sizes free per item.  Returns the open store at
+    ``path`` with fields ``image`` / ``mask`` (a channel axis only where ``in_channels`` / ``out_channels`` exceeds 1)."""
+    _check_common(images, masks, dilate_kernel)
+    items = []
+    for img, msk in zip(images, masks):
+        img, msk = _load(img), _mask_u8(_load(msk))
+        img, msk = (img[None] if img.ndim == 2 else img), (msk[None] if msk.ndim == 2 else msk)
+        if img.ndim != 3 or msk.ndim != 3 or img.shape[0] != in_channels or msk.shape[0] != out_channels or img.shape[1:] != msk.shape[1:]:
+            raise ValueError(f"image {img.shape} and mask {msk.shape} do not make an item of {in_channels} input and {out_channels} output channels")
+        items.append((img, msk, origins_2d(img.shape[1:], dim_out, add_tile)))
+    device = _device(device)
+    th, tw = (int(d) for d in dim_out)
+    shp = lambda c: (th, tw) if c == 1 else (c, th, tw)
+    store = TileStore.create(path, sum(len(o) for _, _, o in items), {"image": shp(in_channels), "mask": shp(out_channels)},
+                             _attrs(dim_out, clip_threshold, shiftscalerotate=shiftscalerotate, noise_lims=noise_lims,
+                                    brightness_contrast=brightness_contrast, blur_limit=blur_limit))
+    n = 0
+    for img, msk, org in items:
+        zyx = [(0, y, x) for y, x in org]
+        store.maps["image"][n:n + len(org)] = _image_tiles(img, device, clip_threshold, zyx, (in_channels, th, tw), shp(in_channels))
+        m = edit_mask(torch.from_numpy(np.ascontiguousarray(msk)).to(device), skeletonize, dilate_mask, dilate_kernel)
+        store.maps["mask"][n:n + len(org)] = gather(m, out_channels, zyx, (out_channels, th, tw), invert).view((len(org),) + shp(out_channels)).cpu().numpy()
+        n += len(org)
+    store.flush()
+    return store
+
+
+def prepare_unet3d(volumes: Sequence, masks: Sequence, path: str, dim_out=(128, 128, 128), dilate_mask: int = 0, dilate_kernel: str = "disk",
+                   add_patch: int = 0, invert: bool = False, skeletonize: bool = False, clip_threshold=(0.2, 99.8), shiftscalerotate=(0, 0, 0),
+                   noise_amp=10, brightness_contrast=(0.25, 0.25), device="auto") -> TileStore:
+    """``bio_image_unet.unet3d.DataProcess`` up to its split (``unet3d/data.py:116-207``) from ``[D, H, W]`` arrays; the mask edit runs slice by
+    slice in 2-D, as there.  Fields ``volume`` / ``mask``, both ``dim_out``."""
+    _check_common(volumes, masks, dilate_kernel)
+    items = []
+    for vol, msk in zip(volumes, masks):
+        vol, msk = _load(vol), _mask_u8(_load(msk))
+        if vol.ndim != 3 or vol.shape != msk.shape:
+            raise ValueError(f"volume {vol.shape} and mask {msk.shape} do not make a [D, H, W] item")
+        items.append((vol, msk, origins_3d(vol.shape, dim_out, add_patch)))
+    device = _device(device)
+    dim = tuple(int(d) for d in dim_out)
+    store = TileStore.create(path, sum(len(o) for _, _, o in items), {"volume": dim, "mask": dim},
+                             _attrs(dim_out, clip_threshold, shiftscalerotate=shiftscalerotate, noise_amp=noise_amp, brightness_contrast=brightness_contrast))
+    n = 0
+    for vol, msk, org in items:
+        store.maps["volume"][n:n + len(org)] = _image_tiles(vol, device, clip_threshold, org, dim, dim)
+        m = edit_mask(torch.from_numpy(np.ascontiguousarray(msk)).to(device), skeletonize, dilate_mask, dilate_kernel)
+        store.maps["mask"][n:n + len(org)] = gather(m, vol.shape[0], org, dim, invert).cpu().numpy()
+        n += len(org)
+    store.flush()
+    return store
+
+
+def prepare_siam(pairs: Sequence, masks: Sequence, path: str, dim_out=(256, 256), dilate_mask: int = 0, dilate_kernel: str = "disk",
+                 invert_masks: bool = False, threshold_masks=None, skeletonize: bool = False, clip_threshold=(0.2, 99.8), shiftscalerotate=(0, 0, 0),
+                 noise_amp=10, brightness_contrast=(0.25, 0.25), rescale=None, device="auto") -> TileStore:
+    """``bio_image_unet.siam_unet.DataProcess`` up to its split (``siam_unet/data.py:126-233``) from arrays: a pair is ``[2, H, W]`` (previous,
+    current) or ``[H, 2 W]`` (previous on the left) and is normalised as one unit; ``masks`` are ``[H, W]``.  Fields ``image`` / ``prev_image`` /
+    ``mask``.  ``rescale`` other than ``None`` is refused: it is ``skimage.transform.rescale``."""
+    if rescale is not None:
+        raise NotImplementedError("rescale needs skimage.transform and is not supported: rescale the arrays before they are prepared")
+    _check_common(pairs, masks, dilate_kernel)
+    items = []
+    for pair, msk in zip(pairs, masks):
+        pair, msk = _load(pair), _mask_u8(_load(msk))
+        if pair.ndim == 2:
+            if pair.shape[1] % 2:
+                raise ValueError(f"a side-by-side pair needs an even width, got {pair.shape}")
+            half = pair.shape[1] // 2
+            pair = np.stack([pair[:, :half], pair[:, half:]])
+        elif pair.ndim != 3 or pair.shape[0] != 2:
+            raise ValueError("Unknown data structure of input images.")
+        if msk.ndim != 2 or msk.shape != pair.shape[1:]:
+            raise ValueError(f"pair {pair.shape} and mask {msk.shape} do not make an item")
+        items.append((pair, msk, origins_2d(msk.shape, dim_out)))
+    device = _device(device)
+    th, tw = (int(d) for d in dim_out)
+    store = TileStore.create(path, sum(len(o) for _, _, o in items), {"image": (th, tw), "prev_image": (th, tw), "mask": (th, tw)},
+                             _attrs(dim_out, clip_threshold, shiftscalerotate=shiftscalerotate, noise_amp=noise_amp, brightness_contrast=brightness_contrast))
+    n = 0
+    for pair, msk, org in items:
+        both = _image_tiles(pair, device, clip_threshold, [(z, y, x) for z in (0, 1) for y, x in org], (1, th, tw), (th, tw))
+        store.maps["prev_image"][n:n + len(org)], store.maps["image"][n:n + len(org)] = both[:len(org)], both[len(org):]
+        m = edit_mask_siam(torch.from_numpy(np.ascontiguousarray(msk[None])).to(device), invert_masks, threshold_masks, skeletonize, dilate_mask, dilate_kernel)
+        store.maps["mask"][n:n + len(org)] = gather(m, 1, [(0, y, x) for y, x in org], (1, th, tw)).view(len(org), th, tw).cpu().numpy()
+        n += len(org)
+    store.flush()
+    return store

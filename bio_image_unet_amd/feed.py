@@ -14,8 +14,8 @@ flat uint8 file per field, mapped into memory:
   PCIe) while the current step computes, and the batch reaches the network as uint8 -- the division by 255 rides in the input-layout
   kernel (``biu_from_nchw_u8``), targets are widened by ``biu_u8_to_f32``.
 
-TIFF decoding and tiling stay out of scope (``DataProcess``): they run once, offline, and their output is what this store holds.
-Augmentation does not have to: ``DeviceFeeder(..., augmenter=augment.Augmenter(...))`` augments every training batch on the device, fresh
+Normalisation, the mask edit and tiling run once and their output is what this store holds: ``dataprep.prepare_unet`` / ``prepare_unet3d`` /
+``prepare_siam`` do them on the device for the three uint8 families (TIFF decoding stays with the caller).  Augmentation does not run once: ``DeviceFeeder(..., augmenter=augment.Augmenter(...))`` augments every training batch on the device, fresh
 every epoch, from a store of un-augmented tiles (``augment.py``).
 
 The 2-D multi-output family's items are float32 (``multi_output_unet/data.py:318-349``): distance and probability maps, and an

@@ -5,3 +5,4 @@ from ..losses import BCEDiceLossSiam as BCEDiceLoss, BCELoss2dProb as BCELoss2d 
 from ..models import Siam_UNet  # noqa: F401
 from ..workflow import TrainerSiam as Trainer   # noqa: F401
 from ..workflow import PredictSiam as Predict   # noqa: F401
+from ..dataprep import prepare_siam as prepare   # noqa: F401  (raw arrays -> feed.TileStore, on the device)

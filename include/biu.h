@@ -623,6 +623,36 @@ int biu_prep_tiles(const void* src, int elem, int planes, int depth, int height,
                    int tw, const double* scalars, int units, int pad_zero, int out_f32, int invert, void* out, biu_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Training data preparation: the mask edit and the mask half of the tile split of the reference's DataProcess (unet/data.py:124-215,
+ * unet3d/data.py:116-207, siam_unet/data.py:126-233) on uint8 planes [planes][height][width], contiguous.  Everything is integer-exact,
+ * enqueued on `stream`, and the caller owns all memory.  src and dst must not overlap (biu_lut_u8 excepted: it may run in place).
+ *
+ *   biu_lut_u8         : dst[i] = lut[src[i]] -- every pointwise step of the mask edit (binarise, threshold, invert, x 255) or a chain of
+ *                        them as one 256-entry table (device memory).
+ *   biu_morph_u8       : grey erosion (op = BIU_MORPH_ERODE, minimum) or dilation (BIU_MORPH_DILATE, maximum) per plane.  Footprints:
+ *                        BIU_FOOT_DISK, size = r in 1..7: {(dy, dx): dy^2 + dx^2 <= r^2}; BIU_FOOT_SQUARE, size = w in 1..15: per axis the
+ *                        offsets [-(w/2), w/2] for odd w, and for even w scipy.ndimage's convention: erosion [-w/2, w/2 - 1], dilation
+ *                        [-(w/2 - 1), w/2].  Border: scipy's mode='reflect' (the edge pixel repeated: -1 -> 0, -2 -> 1, n -> n - 1),
+ *                        applied literally.  Larger footprints are refused (BIU_ERR_UNSUPPORTED).
+ *   biu_thin_step_u8   : one sub-iteration (sub = 0 | 1) of Zhang-Suen thinning: src holds 0 / 1 bytes (nonzero counts as set), pixels
+ *                        outside a plane are 0, every pixel is judged on src, dst is written in full (0 / 1).  table (device, 256 bytes):
+ *                        entry n = neighbourhood code with bit 0 = P2 (north), then clockwise P3 (NE) .. P9 (NW) in bits 1..7; bit `sub`
+ *                        of the entry set = a set pixel with this neighbourhood is cleared in that sub-iteration.  *cleared (device) is
+ *                        incremented by the number of pixels the launch cleared (integer atomic; the caller zeroes it).
+ *   biu_tile_gather_u8 : the mask twin of biu_prep_tiles: origins (device) = ntiles records (ignored, z0, y0, x0); tile t is
+ *                        out[t][td][th][tw] read from planes z0.., rows y0.., columns x0.. inside the block of `depth` planes that holds
+ *                        z0, reflecting beyond the source as numpy 'reflect' does; invert != 0 writes 255 - v.
+ * ---------------------------------------------------------------------------------------------- */
+enum { BIU_MORPH_ERODE = 0, BIU_MORPH_DILATE = 1 };
+enum { BIU_FOOT_DISK = 0, BIU_FOOT_SQUARE = 1 };
+int biu_lut_u8(const uint8_t* src, const uint8_t* lut, uint8_t* dst, long long n, biu_stream stream);
+int biu_morph_u8(const uint8_t* src, uint8_t* dst, int planes, int height, int width, int op, int footprint, int size, biu_stream stream);
+int biu_thin_step_u8(const uint8_t* src, uint8_t* dst, int planes, int height, int width, int sub, const uint8_t* table,
+                     unsigned long long* cleared, biu_stream stream);
+int biu_tile_gather_u8(const uint8_t* src, int planes, int depth, int height, int width, const int* origins, int ntiles, int td, int th,
+                       int tw, int invert, uint8_t* out, biu_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
  * On-the-fly training augmentation of uint8 tile batches (the albumentations pipelines of unet/data.py:217-245,
  * siam_unet/data.py:236-243, unet3d/data.py:209-239, which the reference runs offline)
  *

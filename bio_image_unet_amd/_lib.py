@@ -251,6 +251,16 @@ class _Lib:
 lib = _Lib(_load())
 
 
+def ptr(t):
+    """Device address of a tensor as the C ABI takes it; ``None`` stays ``None`` (a null pointer)."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def stream():
+    """torch's current stream, the one every kernel of the library is launched on."""
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
 def check(status: int, what: str = ""):
     if status != 0:
         msg = lib.biu_last_error()

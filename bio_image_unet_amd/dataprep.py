@@ -21,14 +21,13 @@ Contract (what the tests hold it to; every comparison is an equality)
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import check, lib, ptr as _ptr, stream as _stream
 from .feed import TileStore
 from .preprocess import DeviceFrontEnd
 from .utils import get_device
@@ -36,14 +35,6 @@ from .utils import get_device
 ERODE, DILATE = 0, 1
 FOOTPRINTS = {"disk": 0, "square": 1}
 THIN_BLOCK = 8                  # full iterations enqueued between two reads of the cleared-pixel counter
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
 
 
 # ---- host: the thinning table and the split geometry -------------------------------------------------------------------------------------

@@ -25,16 +25,9 @@ from torch import nn
 
 from . import _lib
 from ._lib import BIU_BF16, BIU_F32, BN_MAX_PARTIALS, biu_act, biu_xform, check, lib
+from ._lib import ptr as _ptr, stream as _stream
 
 LRELU_SLOPE = 0.1      # nn.LeakyReLU(negative_slope=0.1), reference unet/unet.py:58
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _disabled(token: str, env: Optional[str] = None) -> bool:

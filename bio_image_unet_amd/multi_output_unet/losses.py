@@ -18,6 +18,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .._lib import stream as _stream
+
 K_BCEDICE, K_TVERSKY, K_LCTVERSKY, K_MSE, K_MAE, K_HUBER, K_DGRAD, K_WDGRAD, K_WVF = range(9)
 MAX_LEVELS, MAX_TERMS, SLOTS = 4, 32, 8
 
@@ -35,10 +37,6 @@ def _call(name, *args):
     from .._lib import check, lib
     launches += 1
     check(getattr(lib, name)(*args), name[4:])
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _ptrs(tensors):

@@ -18,6 +18,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .._lib import stream as _stream
+
 K_BCEDICE, K_TVERSKY, K_LCTVERSKY, K_TEMPORAL = range(4)
 MAX_TERMS, SLOTS, SAVED_HEADER = 16, 8, 32
 ACT_CODE = {"sigmoid": 1, "tanh": 2, "relu": 3}      # engine._ACT_CODE; anything else is no activation, softmax goes through torch
@@ -36,10 +38,6 @@ def _call(name, *args):
     from .._lib import check, lib
     launches += 1
     check(getattr(lib, name)(*args), name[4:])
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _p(t, floats=0):

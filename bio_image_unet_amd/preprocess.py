@@ -26,17 +26,13 @@ import math
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import check, lib, stream as _stream
 
 ELEM_U8, ELEM_U16, ELEM_I16, ELEM_F32 = 0, 1, 2, 3
 _ELEM_NP = {np.dtype("uint8"): ELEM_U8, np.dtype("uint16"): ELEM_U16, np.dtype("int16"): ELEM_I16, np.dtype("float32"): ELEM_F32}
 _ELEM_TORCH = {torch.uint8: ELEM_U8, torch.uint16: ELEM_U16, torch.int16: ELEM_I16, torch.float32: ELEM_F32}
 FAMILIES = {"minmax": 0, "minmax_eps": 1, "lohi_eps": 2}
 MAX_RANKS = 8
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def percentile_ranks(q: float, n: int):

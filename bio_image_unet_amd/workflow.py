@@ -17,12 +17,16 @@ take ``augment=True`` to augment the training batches of a ``feed.TileStore`` on
 
 Layout: all five Trainers sit on ``_EpochLoop`` (construction tail, batch loop, validation loop, epoch driver); a family is its constructor,
 a few class attributes (scheduler, gradient clip, which lines it prints), ``_forward_loss`` (``_total_loss`` on the two multi-output families,
-which share ``_MultiHeadLoop``), ``_checkpoint(epoch, val_loss)`` -- the dictionary it saves -- and ``_report`` where its text differs.  The
-Predicts share checkpoint loading (``_load_params``), percentile normalisation (``_percentile_rescale``) and result writing (``_write``,
-``_write_heads``).  Every Predict takes ``preprocess='host'`` (that numpy path, the default) or ``'device'``: the raw stack is uploaded once
-in its own dtype and percentiles, rescale, padding and tiling run in HBM (``preprocess.DeviceFrontEnd``) over the same tile origins
-(``_origins``); its docstring states where the two differ (float32 input of the float32-arithmetic host paths, NaN, float64 that float32
-cannot hold).
+which share ``_MultiHeadLoop``), ``_checkpoint(epoch, val_loss)`` -- the dictionary it saves -- and ``_report`` where its text differs.
+
+All five Predicts sit on ``_PredictBase`` (opening the input, loading checkpoint and network, the ``no_grad`` batch iterator, where a patch
+is stitched) and run in one order: input, geometry and patches, model, batch loop into ``_Stitcher``s in HBM, crop and write.  A family is
+its constructor signature, ``_origins`` -- its tile grid, the one list that both cuts the patches and places them in the stitch --, its host
+normalisation and ``_split`` (one line over ``_cut``), ``_build(model_params, network)`` and what it does with one predicted patch; the two
+multi-output families share ``_HeadStitch`` (a stitcher per head and image, the weight arrays by neighbour flags).  Every Predict takes
+``preprocess='host'`` (numpy, the default) or ``'device'``: the raw stack is uploaded once in its own dtype and percentiles, rescale,
+padding and tiling run in HBM (``preprocess.DeviceFrontEnd``) over the same ``_origins``; its docstring states where the two differ
+(float32 input of the float32-arithmetic host paths, NaN, float64 that float32 cannot hold).
 """
 from __future__ import annotations
 
@@ -34,6 +38,7 @@ import torch
 from torch import nn, optim
 from torch.utils.data import DataLoader, random_split
 
+from ._lib import check, lib, ptr, stream
 from .losses import BCEDiceLoss, BCEDiceLossSiam, BCEDiceTemporalLoss, TverskyLoss, logcoshTverskyLoss, weightedBCELoss
 from .models import AttentionUnet, MultiOutputNestedUNet, MultiOutputUnet3D, Siam_UNet, UNet3D, Unet, Unet_v0
 from .optim import Adam
@@ -539,7 +544,7 @@ class TrainerMo2d(_MultiHeadLoop, metaclass=_OwnKeywords):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# 2-D prediction: normalise -> tile -> forward (eval) -> uint8 -> stitch (mean of overlaps)
+# Prediction: open -> normalise -> tile -> forward (eval) -> stitch in HBM -> write
 # ----------------------------------------------------------------------------------------------------------------------
 def _percentile_rescale(imgs, mode, clip, top=None, invert=False):
     """Percentile clip, shift to 0 and divide by the maximum -- then times ``top`` and, with ``invert``, ``top - a``: per image ('single'), by
@@ -593,37 +598,49 @@ class _Stitcher:
 
     def add(self, patch: torch.Tensor, origin, weight: torch.Tensor = None, layer: int = 0, overwrite: bool = False):
         """patch: device tensor [channels, pd, ph, pw] (uint8 or float32); origin (z0, y0, x0); weight [pd, ph, pw] float32 or None."""
-        import ctypes as C
-        from ._lib import check, lib
         patch = patch.contiguous()
         assert patch.dim() == 4 and patch.shape[0] == self.channels and patch.dtype in (torch.uint8, torch.float32)
         c, pd, ph, pw = patch.shape
         d, h, w = self.shape
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        check(lib.biu_stitch_add(C.c_void_p(patch.data_ptr()), int(patch.dtype == torch.uint8),
-                                 C.c_void_p(weight.data_ptr()) if weight is not None else None, c, pd, ph, pw,
-                                 C.c_void_p(self.acc[layer].data_ptr()), C.c_void_p(self.wsum[layer].data_ptr()), d, h, w,
+        st = stream()
+        check(lib.biu_stitch_add(ptr(patch), int(patch.dtype == torch.uint8), ptr(weight), c, pd, ph, pw,
+                                 ptr(self.acc[layer]), ptr(self.wsum[layer]), d, h, w,
                                  int(origin[0]), int(origin[1]), int(origin[2]), int(overwrite), st), "stitch_add")
 
     def finish(self, as_uint8: bool) -> torch.Tensor:
-        import ctypes as C
-        from ._lib import check, lib
         d, h, w = self.shape
         out = torch.empty((self.channels, d, h, w), dtype=torch.uint8 if as_uint8 else torch.float32, device=self.device)
-        check(lib.biu_stitch_finish(C.c_void_p(self.acc.data_ptr()), C.c_void_p(self.wsum.data_ptr()), self.layers, self.channels,
-                                    d * h * w, C.c_void_p(out.data_ptr()), int(as_uint8),
-                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), "stitch_finish")
+        check(lib.biu_stitch_finish(ptr(self.acc), ptr(self.wsum), self.layers, self.channels, d * h * w, ptr(out), int(as_uint8), stream()),
+              "stitch_finish")
         return out
+
+
+class _HeadStitch:
+    """The stitchers of the two multi-output Predicts, ``self[head]`` one ``_Stitcher`` per image or volume, and the weight arrays on the
+    device, one per combination of neighbour flags.  ``make_weight(index, flags)`` is the family's: the weight array of the tile at grid
+    position ``index`` of ``grid``, ``flags`` saying per axis whether it has a neighbour before and after."""
+
+    def __init__(self, device, heads, count, shape3, grid, make_weight):
+        self.device, self.grid, self.make_weight, self.weights = device, tuple(grid), make_weight, {}
+        self.stitchers = {k: [_Stitcher(device, cfg["channels"], shape3) for _ in range(count)] for k, cfg in heads.items()}
+
+    def __getitem__(self, head):
+        return self.stitchers[head]
+
+    def add(self, patches, image, origin, index):
+        """patches: {head: [channels, pd, ph, pw] float32}, one patch's predictions; into image ``image`` at ``origin``."""
+        flags = tuple(f for i, n in zip(index, self.grid) for f in (i > 0, i < n - 1))
+        if flags not in self.weights:
+            self.weights[flags] = torch.from_numpy(self.make_weight(index, flags)).to(self.device).contiguous()
+        for k, patch in patches.items():
+            self.stitchers[k][image].add(patch, origin, weight=self.weights[flags])
 
 
 def _quantize_u8(prob: torch.Tensor) -> torch.Tensor:
     """``(res * 255).astype('uint8')`` (unet/predict.py:200) on the device."""
-    import ctypes as C
-    from ._lib import check, lib
     prob = prob.contiguous().float()
     out = torch.empty(prob.shape, dtype=torch.uint8, device=prob.device)
-    check(lib.biu_quantize_u8(C.c_void_p(prob.data_ptr()), 255.0, C.c_void_p(out.data_ptr()), prob.numel(),
-                              C.c_void_p(torch.cuda.current_stream().cuda_stream)), "quantize_u8")
+    check(lib.biu_quantize_u8(ptr(prob), 255.0, ptr(out), prob.numel(), stream()), "quantize_u8")
     return out
 
 
@@ -641,126 +658,16 @@ def _patch_batch(patches, i, j, device):
     return patches.batch(i, j)
 
 
-class Predict2D:
-    """``bio_image_unet.unet.Predict`` counterpart (``unet/predict.py:14-229``) for in-memory arrays.
-
-    Same preprocessing, tiling, uint8 re-quantisation ``(p*255).astype('uint8')`` and nan-mean stitching; patches are
-    pushed through the network in batches (eval-mode BatchNorm makes that identical to the reference's batch of 1) so the
-    device is not synchronised once per patch.  The result is kept in ``self.imgs_result`` and written to
-    ``result_name`` (TIFF via tifffile when importable -- float16 like ``save_as_tif`` -- otherwise ``.npy``).
-
-    ``preprocess='device'`` (default ``'host'``) normalises and tiles in HBM (``preprocess.DeviceFrontEnd``): fp64 from the values as
-    uploaded, bit-equal to the host path for integer and float64 input (float64 goes up as float32 and raises ``ValueError`` unless every
-    value is exactly representable); float32 input, which the host path normalises in numpy float32, gets the same formula in fp64
-    rounded once; NaN raises ``ValueError`` (use ``preprocess='host'``); a constant image is 0 / 0 on both paths."""
-
-    def __init__(self, imgs, result_name, model_params, network="Unet", resize_dim=(512, 512), invert=False,
-                 normalization_mode="single", clip_threshold=(0., 99.8), add_tile=0, normalize_result=False,
-                 show_progress=True, device: Union[torch.device, str] = "auto", progress_notifier=None, batch_size=8,
-                 preprocess="host"):
-        _check_preprocess(preprocess)
-        self.device = _pick_device(device)
-        if isinstance(imgs, str):
-            import tifffile                      # only needed for file input; not a dependency of the hot path
-            imgs = tifffile.imread(imgs)
-        self.resize_dim, self.add_tile = tuple(resize_dim), add_tile
-        if preprocess == "device":
-            # the raw stack goes up in its own dtype; percentiles, rescale, reflect padding and tiling happen in HBM (preprocess.py).  fp64
-            # from the values as uploaded: bit-equal to the host path for integer and float64 input; float32 input, which the host path
-            # normalises in numpy float32, comes out as the same formula evaluated in fp64
-            raw = np.asarray(imgs)
-            raw = raw[None] if raw.ndim == 2 else raw
-            self.imgs_shape = raw.shape
-            fe = DeviceFrontEnd(raw, self.device)
-            fe.normalise(normalization_mode, clip_threshold)
-            patches = fe.tiles(self._origins(), (1,) + self.resize_dim, out="uint8", invert=invert)
-        else:
-            imgs = np.array(imgs, dtype=np.float64 if np.asarray(imgs).dtype.kind != "f" else np.asarray(imgs).dtype)
-            if imgs.ndim == 2:
-                imgs = imgs[None]
-            self.imgs_shape = imgs.shape
-            imgs = normalise_stack(imgs, normalization_mode, clip_threshold, invert)
-            patches = self._split(imgs)
-
-        self.model_params = _load_params(model_params, self.device)
-        if network is None:
-            network = self.model_params.get("network")
-            if network is None:
-                raise ValueError("network is not defined")
-        if network == "Unet":
-            network = Unet
-        elif network == "AttentionUnet":
-            network = AttentionUnet
-        elif network == "Unet_v0":                       # legacy checkpoints carry no channel counts (unet/predict.py:93-97)
-            network = Unet_v0
-            if "in_channels" not in self.model_params:
-                self.model_params["in_channels"] = 1
-                self.model_params["out_channels"] = 1
-        elif isinstance(network, str):
-            raise ValueError(f"network '{network}' is not one of 'Unet', 'AttentionUnet', 'Unet_v0' (or pass a class)")
-        mp = self.model_params
-        # (the reference ignores the checkpoint's 'dilation' here, unet/predict.py:98-99 -- so does this)
-        self.model = network(n_filter=mp["n_filter"], in_channels=mp["in_channels"], out_channels=mp["out_channels"]).to(self.device)
-        self.model.load_state_dict(mp["state_dict"])
-        self.model.eval()
-        self.imgs_result = self._predict_and_stitch(patches, batch_size)
-        # float16 like ``save_as_tif`` in the TIFF only; the ``.npy`` fallback keeps the array as it is
-        _write(result_name, _unit_range(self.imgs_result) if normalize_result else self.imgs_result, tif_dtype="float16" if normalize_result else None)
-
-    def _origins(self):
-        """Tile grid of ``unet/predict.py:153-181``: sets ``N_x``, ``N_y``, ``X_start``, ``Y_start`` and returns the patch order as
-        (image, 0, row, column) in the (reflect-padded) stack -- shared by the host ``_split`` and the device front end."""
-        n_img, h, w = self.imgs_shape
-        th, tw = self.resize_dim
-        self.N_x = int(np.ceil(h / th)) + self.add_tile
-        self.N_y = int(np.ceil(w / tw)) + self.add_tile
-        self.N_per_img = self.N_x * self.N_y
-        self.X_start, self.Y_start = tile_starts(h, th, self.N_x), tile_starts(w, tw, self.N_y)
-        return [(i, 0, int(xs), int(ys)) for i in range(n_img) for xs in self.X_start for ys in self.Y_start]
-
-    def _split(self, imgs):
-        n_img, h, w = self.imgs_shape
-        th, tw = self.resize_dim
-        origins = self._origins()
-        if th > h:
-            imgs = np.pad(imgs, ((0, 0), (0, th - h), (0, 0)), "reflect")
-        if tw > w:
-            imgs = np.pad(imgs, ((0, 0), (0, 0), (0, tw - w)), "reflect")
-        patches = np.zeros((n_img * self.N_per_img, 1, th, tw), dtype="uint8")
-        for k, (i, _, xs, ys) in enumerate(origins):
-            patches[k, 0] = imgs[i, xs:xs + th, ys:ys + tw]            # float -> uint8 truncation, as upstream
-        return patches
-
-    def _predict_and_stitch(self, patches, batch_size):
-        """uint8 patches up (divided by 255 in the input-layout kernel), eval-mode forward in batches, ``(p * 255)`` truncated to
-        uint8 and added into the stitched image on the device; nan-mean of the overlapping uint8 tiles followed by the uint8
-        cast == floor(sum / count) (``unet/predict.py:184-229``).  One download per stack."""
-        n_img, h, w = self.imgs_shape
-        th, tw = self.resize_dim
-        oc = self.model_params["out_channels"]
-        H, W = max(th, h), max(tw, w)
-        origins = [(0, int(xs), int(ys)) for xs in self.X_start for ys in self.Y_start]
-        st = _Stitcher(self.device, oc, (1, H, W))
-        done, cur = [], 0
-        with torch.no_grad():
-            for i in range(0, patches.shape[0], batch_size):
-                x = _patch_batch(patches, i, i + batch_size, self.device)      # uint8 across PCIe (host path) or cut in HBM (device path)
-                prob, _ = self.model(x)
-                q = _quantize_u8(prob)
-                for j in range(q.shape[0]):
-                    k = i + j
-                    if k // self.N_per_img != cur:
-                        done.append(st.finish(True))
-                        st.reset()
-                        cur = k // self.N_per_img
-                    st.add(q[j].unsqueeze(1), origins[k % self.N_per_img])
-            done.append(st.finish(True))
-        res = torch.stack(done).cpu().numpy()[:, :, 0]                       # (n_img, oc, H, W)
-        return np.squeeze(res[:, :, :h, :w])
-
-
-def _load_params(model_params, device):
-    return torch.load(model_params, map_location=device) if isinstance(model_params, str) else model_params
+def _cut(stack, origins, tile, dtype=None, mode="reflect"):
+    """The host cut: ``stack`` [images, D, H, W], padded at the far ends where a tile is larger (``mode``), and the ``tile`` at every origin
+    (image, z, y, x) -- the numpy counterpart of ``DeviceFrontEnd.tiles``.  Assignment casts to ``dtype`` (float -> uint8 truncates)."""
+    pad = [(0, 0)] + [(0, max(0, t - n)) for t, n in zip(tile, stack.shape[1:])]
+    if any(p for _, p in pad):
+        stack = np.pad(stack, pad, mode)
+    patches = np.empty((len(origins),) + tuple(tile), dtype=dtype or stack.dtype)
+    for n, (i, z, y, x) in enumerate(origins):
+        patches[n] = stack[i, z:z + tile[0], y:y + tile[1], x:x + tile[2]]
+    return patches
 
 
 def _unit_range(img):
@@ -790,7 +697,140 @@ def _write_heads(result_path, result):
     return None
 
 
-class Predict3D:
+class _PredictBase:
+    """The one pipeline under the five Predicts.  A constructor runs it in this order: ``_open`` the input; geometry and patches -- the host
+    path normalises and ``_split``s in numpy, the device path hands ``_origins()`` to a ``DeviceFrontEnd``; ``_load_model``; the loop over
+    ``_batches`` that runs ``_forward`` and stitches every predicted patch at ``_place(k)``; crop and write.  A family provides ``_origins()``
+    (its tile grid, kept as ``self.origins``: the only statement of tile order, for cutting and for stitching), ``_split``, its
+    normalisation, ``_build(model_params, network)`` and what it does with one predicted patch."""
+    rank = 3            # of the stack; input one rank lower is a single image / volume and gets the leading axis
+
+    def _open(self, data, device, preprocess):
+        """The input as an array of ``rank`` axes (a path is read through ``tifffile``); sets ``self.device``."""
+        _check_preprocess(preprocess)
+        self.device = _pick_device(device)
+        if isinstance(data, str):
+            import tifffile                      # only needed for file input; not a dependency of the hot path
+            data = tifffile.imread(data)
+        data = np.asarray(data)
+        return data[None] if data.ndim == self.rank - 1 else data
+
+    def _load_model(self, model_params, network=None):
+        """The checkpoint (a path or the dictionary itself) into ``model_params`` and the family's network, loaded and in eval mode."""
+        mp = self.model_params = torch.load(model_params, map_location=self.device) if isinstance(model_params, str) else model_params
+        self.model = self._build(mp, network).to(self.device)
+        self.model.load_state_dict(mp["state_dict"])
+        self.model.eval()
+        return mp
+
+    def _batches(self, patches, batch_size):
+        """(index of its first patch, the batch on the device) over ``patches`` -- a host array that goes up slice by slice, or the device
+        front end's tiles, cut in HBM."""
+        for i in range(0, len(patches), batch_size):
+            yield i, _patch_batch(patches, i, i + batch_size, self.device)
+
+    @torch.no_grad()
+    def _forward(self, *batch):
+        """The network on one batch, outside autograd.  (``no_grad`` sits here and not around the ``yield`` of ``_batches``: held open across a
+        ``yield`` it would stay in force after an exception in the loop body, until the suspended generator is collected.)"""
+        return self.model(*batch)
+
+    def _grid_2d(self, n_img):
+        """Tile grid of the two 2-D uint8 families (``unet/predict.py:153-181``) over ``n_img`` images of ``imgs_shape[1:]``: ``add_tile`` extra
+        tiles per axis, ``linspace`` origins; the order is image, row, column."""
+        (h, w), (th, tw) = self.imgs_shape[1:], self.resize_dim
+        self.N_x = int(np.ceil(h / th)) + self.add_tile
+        self.N_y = int(np.ceil(w / tw)) + self.add_tile
+        self.N_per_img = self.N_x * self.N_y
+        self.X_start, self.Y_start = tile_starts(h, th, self.N_x), tile_starts(w, tw, self.N_y)
+        self.origins = [(i, 0, int(xs), int(ys)) for i in range(n_img) for xs in self.X_start for ys in self.Y_start]
+        return self.origins
+
+    def _place(self, k):
+        """Where patch ``k`` is stitched: (image or volume, origin in it) -- the two parts of the origin it was cut at."""
+        o = self.origins[k]
+        return o[0], o[1:]
+
+
+class Predict2D(_PredictBase):
+    """``bio_image_unet.unet.Predict`` counterpart (``unet/predict.py:14-229``) for in-memory arrays.
+
+    Same preprocessing, tiling, uint8 re-quantisation ``(p*255).astype('uint8')`` and nan-mean stitching; patches are
+    pushed through the network in batches (eval-mode BatchNorm makes that identical to the reference's batch of 1) so the
+    device is not synchronised once per patch.  The result is kept in ``self.imgs_result`` and written to
+    ``result_name`` (TIFF via tifffile when importable -- float16 like ``save_as_tif`` -- otherwise ``.npy``).
+
+    ``preprocess='device'`` (default ``'host'``) normalises and tiles in HBM (``preprocess.DeviceFrontEnd``): fp64 from the values as
+    uploaded, bit-equal to the host path for integer and float64 input (float64 goes up as float32 and raises ``ValueError`` unless every
+    value is exactly representable); float32 input, which the host path normalises in numpy float32, gets the same formula in fp64
+    rounded once; NaN raises ``ValueError`` (use ``preprocess='host'``); a constant image is 0 / 0 on both paths."""
+
+    def __init__(self, imgs, result_name, model_params, network="Unet", resize_dim=(512, 512), invert=False,
+                 normalization_mode="single", clip_threshold=(0., 99.8), add_tile=0, normalize_result=False,
+                 show_progress=True, device: Union[torch.device, str] = "auto", progress_notifier=None, batch_size=8,
+                 preprocess="host"):
+        raw = self._open(imgs, device, preprocess)
+        self.resize_dim, self.add_tile, self.imgs_shape = tuple(resize_dim), add_tile, raw.shape
+        if preprocess == "device":
+            # the raw stack goes up in its own dtype; percentiles, rescale, reflect padding and tiling happen in HBM (preprocess.py).  fp64
+            # from the values as uploaded: bit-equal to the host path for integer and float64 input; float32 input, which the host path
+            # normalises in numpy float32, comes out as the same formula evaluated in fp64
+            fe = DeviceFrontEnd(raw, self.device)
+            fe.normalise(normalization_mode, clip_threshold)
+            patches = fe.tiles(self._origins(), (1,) + self.resize_dim, out="uint8", invert=invert)
+        else:
+            imgs = np.array(raw, dtype=np.float64 if raw.dtype.kind != "f" else raw.dtype)
+            patches = self._split(normalise_stack(imgs, normalization_mode, clip_threshold, invert))
+        self._load_model(model_params, network)
+        self.imgs_result = self._predict_and_stitch(patches, batch_size)
+        # float16 like ``save_as_tif`` in the TIFF only; the ``.npy`` fallback keeps the array as it is
+        _write(result_name, _unit_range(self.imgs_result) if normalize_result else self.imgs_result, tif_dtype="float16" if normalize_result else None)
+
+    def _build(self, mp, network):
+        if network is None:
+            network = mp.get("network")
+            if network is None:
+                raise ValueError("network is not defined")
+        if network == "Unet_v0" and "in_channels" not in mp:        # legacy checkpoints carry no channel counts (unet/predict.py:93-97)
+            mp["in_channels"] = mp["out_channels"] = 1
+        if isinstance(network, str):
+            table = {"Unet": Unet, "AttentionUnet": AttentionUnet, "Unet_v0": Unet_v0}
+            if network not in table:
+                raise ValueError(f"network '{network}' is not one of 'Unet', 'AttentionUnet', 'Unet_v0' (or pass a class)")
+            network = table[network]
+        # (the reference ignores the checkpoint's 'dilation' here, unet/predict.py:98-99 -- so does this)
+        return network(n_filter=mp["n_filter"], in_channels=mp["in_channels"], out_channels=mp["out_channels"])
+
+    def _origins(self):
+        """Tile grid of ``unet/predict.py:153-181``: sets ``N_x``, ``N_y``, ``X_start``, ``Y_start`` and returns the patch order as
+        (image, 0, row, column) in the (reflect-padded) stack -- shared by the host ``_split``, the device front end and the stitch."""
+        return self._grid_2d(self.imgs_shape[0])
+
+    def _split(self, imgs):
+        return _cut(imgs[:, None], self._origins(), (1,) + self.resize_dim, "uint8")          # float -> uint8 truncation, as upstream
+
+    def _predict_and_stitch(self, patches, batch_size):
+        """uint8 patches up (divided by 255 in the input-layout kernel), eval-mode forward in batches that run across image borders,
+        ``(p * 255)`` truncated to uint8 and added into the stitched image on the device; nan-mean of the overlapping uint8 tiles followed
+        by the uint8 cast == floor(sum / count) (``unet/predict.py:184-229``).  One download per stack."""
+        n_img, h, w = self.imgs_shape
+        th, tw = self.resize_dim
+        st = _Stitcher(self.device, self.model_params["out_channels"], (1, max(th, h), max(tw, w)))
+        done = []
+        for i, x in self._batches(patches, batch_size):             # uint8 across PCIe (host path) or cut in HBM (device path)
+            q = _quantize_u8(self._forward(x)[0])
+            for j in range(q.shape[0]):
+                img, origin = self._place(i + j)
+                if img != len(done):                                # the first patch of the next image: the one before is complete
+                    done.append(st.finish(True))
+                    st.reset()
+                st.add(q[j].unsqueeze(1), origin)
+        done.append(st.finish(True))
+        res = torch.stack(done).cpu().numpy()[:, :, 0]              # (n_img, oc, H, W)
+        return np.squeeze(res[:, :, :h, :w])
+
+
+class Predict3D(_PredictBase):
     """``bio_image_unet.unet3d.Predict`` counterpart (``unet3d/predict.py:12-195``) for in-memory volumes.
 
     Whole-volume percentile clip to [0, 255]; patches of ``resize_dim`` (z, x, y) at ``linspace`` origins (reflect padding
@@ -802,46 +842,33 @@ class Predict3D:
     def __init__(self, vol, result_name, model_params, network=UNet3D, resize_dim=(64, 128, 128), invert=False,
                  normalization_mode="single", clip_threshold=(0., 99.8), add_patch=0, normalize_result=False,
                  progress_bar=True, device: Union[torch.device, str] = "auto", progress_notifier=None, preprocess="host"):
-        _check_preprocess(preprocess)
-        self.device = _pick_device(device)
-        if isinstance(vol, str):
-            import tifffile
-            vol = tifffile.imread(vol)
-        vol = np.asarray(vol)
-        self.resize_dim, self.add_patch = tuple(resize_dim), add_patch
-        self.vol_shape = vol.shape
-        if vol.ndim == 2:
-            vol = vol[None]
-            self.vol_shape = vol.shape
+        vol = self._open(vol, device, preprocess)
+        self.resize_dim, self.add_patch, self.vol_shape = tuple(resize_dim), add_patch, vol.shape
+        rd, vs = self.resize_dim, self.vol_shape
         if preprocess == "device":                                      # (departures as for Predict2D)
             fe = DeviceFrontEnd(vol, self.device, depth=vol.shape[0])
             fe.normalise("all", clip_threshold)
-            patches = fe.tiles(self._origins(), self.resize_dim, out="uint8", invert=invert)
-        else:
-            vol = normalise_stack(vol, "all", clip_threshold, invert)   # the whole volume's histogram, whatever normalization_mode says
-            patches = self._split(vol)
-        mp = self.model_params = _load_params(model_params, self.device)
-        self.model = network(n_filter=mp["n_filter"], in_channels=mp["in_channels"], out_channels=mp["out_channels"],
-                             use_interpolation=mp.get("use_interpolation", False)).to(self.device)
-        self.model.load_state_dict(mp["state_dict"])
-        self.model.eval()
+            patches = fe.tiles(self._origins(), rd, out="uint8", invert=invert)
+        else:                                                           # the whole volume's histogram, whatever normalization_mode says
+            patches = self._split(normalise_stack(vol, "all", clip_threshold, invert))
+        self._load_model(model_params, network)
         # one eval-mode forward per patch as upstream (unet3d/predict.py:155-171); quantisation and the three-layer stitch buffer
         # (patch n overwrites layer n % 3, then the nan-mean over the layers, :173-195) stay on the device
-        vs, rd = self.vol_shape, self.resize_dim
         st = _Stitcher(self.device, 1, tuple(max(vs[a], rd[a]) for a in range(3)), layers=3)
-        origins = [(int(z), int(x), int(y)) for z in self.Z_start for x in self.X_start for y in self.Y_start]
-        with torch.no_grad():
-            for i in range(self.N):
-                x = _patch_batch(patches, i, i + 1, self.device).view((1, 1) + self.resize_dim)      # uint8; /255 in the layout kernel
-                prob, _ = self.model(x)
-                st.add(_quantize_u8(prob).view((1,) + self.resize_dim), origins[i], layer=i % 3, overwrite=True)
+        for i, x in self._batches(patches, 1):
+            prob, _ = self._forward(x.view((1, 1) + rd))                   # uint8; /255 in the layout kernel
+            st.add(_quantize_u8(prob).view((1,) + rd), self._place(i)[1], layer=i % 3, overwrite=True)
         out = st.finish(True)[0].cpu().numpy()
         self.vol_result = np.squeeze(out[:vs[0], :vs[1], :vs[2]])
         _write(result_name, _unit_range(self.vol_result).astype("float16") if normalize_result else self.vol_result)
 
+    def _build(self, mp, network):
+        return network(n_filter=mp["n_filter"], in_channels=mp["in_channels"], out_channels=mp["out_channels"],
+                       use_interpolation=mp.get("use_interpolation", False))
+
     def _origins(self):
         """Patch grid of ``unet3d/predict.py:118-150``: sets the counts and ``Z_start`` / ``X_start`` / ``Y_start`` and returns the patch order
-        as (0, z, x, y) in the (reflect-padded) volume -- shared by the host ``_split`` and the device front end."""
+        as (0, z, x, y) in the (reflect-padded) volume -- shared by the host ``_split``, the device front end and the stitch."""
         vs, rd, ap = self.vol_shape, self.resize_dim, self.add_patch
         self.N_z = int(np.ceil(vs[0] / rd[0])) + ap
         self.N_x = int(np.ceil(vs[1] / rd[1])) + ap
@@ -853,19 +880,14 @@ class Predict3D:
         self.Z_start = tile_starts(vs[0], rd[0], self.N_z)
         self.X_start = tile_starts(vs[1], rd[1], self.N_x)
         self.Y_start = tile_starts(vs[2], rd[2], self.N_y)
-        return [(0, int(z), int(x), int(y)) for z in self.Z_start for x in self.X_start for y in self.Y_start]
+        self.origins = [(0, int(z), int(x), int(y)) for z in self.Z_start for x in self.X_start for y in self.Y_start]
+        return self.origins
 
     def _split(self, vol):
-        vs, rd = self.vol_shape, self.resize_dim
-        origins = self._origins()
-        vol = np.pad(vol, [(0, max(0, rd[a] - vs[a])) for a in range(3)], "reflect")
-        patches = np.zeros((self.N,) + rd, dtype="uint8")
-        for n, (_, z, x, y) in enumerate(origins):
-            patches[n] = vol[z:z + rd[0], x:x + rd[1], y:y + rd[2]]
-        return patches
+        return _cut(vol[None], self._origins(), self.resize_dim, "uint8")
 
 
-class PredictSiam:
+class PredictSiam(_PredictBase):
     """``bio_image_unet.siam_unet.Predict`` counterpart (``siam_unet/predict.py:16-250``) for an in-memory movie (T, H, W).
 
     Frame i is predicted together with its predecessor (frame 0 with frame 1, or with itself in a one-frame movie); every
@@ -880,73 +902,52 @@ class PredictSiam:
     def __init__(self, movie, result_name, model_params, resize_dim=None, invert=False, normalization_mode="single",
                  clip_threshold=(0., 99.8), add_tile=0, normalize_result=False, show_progress=True,
                  device: Union[torch.device, str] = "auto", progress_notifier=None, batch_size=8, preprocess="host"):
-        _check_preprocess(preprocess)
-        self.device = _pick_device(device)
-        if isinstance(movie, str):
-            import tifffile
-            movie = tifffile.imread(movie)
-        movie = np.asarray(movie)
-        if movie.ndim == 2:
-            movie = movie[None]
-        mp = self.model_params = _load_params(model_params, self.device)
-        self.model = Siam_UNet(n_filter=mp["n_filter"], mode=mp["mode"]).to(self.device)
-        self.model.load_state_dict(mp["state_dict"])
-        self.model.eval()
-        self.tif_len = movie.shape[0]
-        self.imgs_shape = [self.tif_len, movie.shape[1], movie.shape[2]]
-        self.resize_dim = tuple(resize_dim) if resize_dim is not None else (movie.shape[1], movie.shape[2])
+        movie = self._open(movie, device, preprocess)
+        self.tif_len, h, w = self.imgs_shape = list(movie.shape)
+        self.resize_dim, self.add_tile = tuple(resize_dim) if resize_dim is not None else (h, w), add_tile
         th, tw = self.resize_dim
-        self.N_x = int(np.ceil(self.imgs_shape[1] / th)) + add_tile
-        self.N_y = int(np.ceil(self.imgs_shape[2] / tw)) + add_tile
-        self.N_per_img = self.N = self.N_x * self.N_y
-        self.X_start = tile_starts(self.imgs_shape[1], th, self.N_x)
-        self.Y_start = tile_starts(self.imgs_shape[2], tw, self.N_y)
-        frames = []
-        cur = None
-        h, w = self.imgs_shape[1], self.imgs_shape[2]
-        stitch = _Stitcher(self.device, 1, (1, max(th, h), max(tw, w)))
-        origins = [(0, int(xs), int(ys)) for xs in self.X_start for ys in self.Y_start]
         if preprocess == "device":
             # the movie goes up once; every pair's order statistics are selected in one batch before the frame loop (float64 arithmetic on
             # the values as uploaded, as the host path's ``np.array([prev, cur], dtype=np.float64)``), zero padding written by the kernel
             fe = DeviceFrontEnd(movie, self.device)
             fe.normalise_pairs(normalization_mode, clip_threshold)
             pairs = fe.pair_tiles(self._origins(), self.resize_dim, invert=invert)
+        self._load_model(model_params)
+        stitch = _Stitcher(self.device, 1, (1, max(th, h), max(tw, w)))
+        frames, cur = [], None
         for i in range(self.tif_len):
             if preprocess == "device":
                 patches = pairs.frame(i, self.N)
-            else:
+            else:                               # the host path normalises and cuts a pair when its turn comes, never the whole movie
                 prev = (movie[0] if self.tif_len == 1 else movie[1]) if i == 0 else cur
                 cur = movie[i]
                 pair = normalise_stack(np.array([prev, cur], dtype=np.float64), normalization_mode, clip_threshold, invert).astype("uint8")
                 patches = self._split(pair)
             stitch.reset()
-            with torch.no_grad():
-                for b in range(0, self.N, batch_size):
-                    both = _patch_batch(patches, b, b + batch_size, self.device)       # uint8 (cur, prev)
-                    q = _quantize_u8(self.model(both[:, 0:1].contiguous(), both[:, 1:2].contiguous())[0])
-                    for j in range(q.shape[0]):
-                        stitch.add(q[j].unsqueeze(1), origins[b + j])
+            for b, both in self._batches(patches, batch_size):                  # uint8 (cur, prev)
+                q = _quantize_u8(self._forward(both[:, 0:1].contiguous(), both[:, 1:2].contiguous())[0])
+                for j in range(q.shape[0]):
+                    stitch.add(q[j].unsqueeze(1), self._place(b + j)[1])
             frames.append(stitch.finish(True)[0, 0, :h, :w])                 # nan-mean of uint8 tiles, truncated like astype
         self.imgs_result = torch.stack(frames).cpu().numpy()
         _write(result_name, self.imgs_result)
 
+    def _build(self, mp, network):
+        return Siam_UNet(n_filter=mp["n_filter"], mode=mp["mode"])               # the model class is fixed
+
     def _origins(self):
-        """Tile order of one frame pair as (0, 0, row, column) -- shared by the host ``_split`` and the device front end."""
-        return [(0, 0, int(xs), int(ys)) for xs in self.X_start for ys in self.Y_start]
+        """Tile grid of one frame pair (``siam_unet/predict.py``, as ``Predict2D``'s): sets ``N_x``, ``N_y``, ``N``, ``X_start``, ``Y_start`` and
+        returns the tile order as (0, 0, row, column) -- shared by the host ``_split``, the device front end and the stitch."""
+        origins = self._grid_2d(1)
+        self.N = self.N_per_img
+        return origins
 
     def _split(self, pair):
-        th, tw = self.resize_dim
-        h, w = self.imgs_shape[1], self.imgs_shape[2]
-        pair = np.pad(pair, ((0, 0), (0, max(0, th - h)), (0, max(0, tw - w))), "constant")
-        patches = np.zeros((self.N, 2, th, tw), dtype="uint8")
-        for n, (_, _, xs, ys) in enumerate(self._origins()):
-            patches[n, 0] = pair[1][xs:xs + th, ys:ys + tw]          # current frame
-            patches[n, 1] = pair[0][xs:xs + th, ys:ys + tw]          # previous frame
-        return patches
+        """(previous, current) -> patches [N, 2, th, tw] with the current frame in channel 0."""
+        return _cut(pair[::-1][None], self._origins(), (2,) + self.resize_dim, "uint8", mode="constant")
 
 
-class PredictMo3d:
+class PredictMo3d(_PredictBase):
     """``bio_image_unet.multi_output_unet3d.Predict`` counterpart (``multi_output_unet3d/predict.py:13-307``).
 
     Float normalisation to [0, 1] (no uint8 step), patches of ``min(volume, max_patch_size)`` on a stride of
@@ -958,23 +959,17 @@ class PredictMo3d:
     device path evaluates the same formula in fp64 on the uploaded values (uint8 / uint16 / int16 as they are, anything else after the
     host path's own cast to float32) and rounds to float32 once, so the two can differ in the last bit of a patch value.  NaN raises
     ``ValueError`` (use ``preprocess='host'``)."""
+    rank = 4
 
     def __init__(self, imgs, model_params, result_path=None, network=MultiOutputUnet3D, max_patch_size=(64, 256, 256),
                  overlap_factor=0.1, batch_size=1, normalization_mode="single", clip_threshold=(0., 99.98), add_tile=0,
                  compress_tif=False, show_progress=True, device: Union[torch.device, str] = "auto", progress_notifier=None,
                  preprocess="host"):
-        _check_preprocess(preprocess)
-        self.device = _pick_device(device)
-        if isinstance(imgs, str):
-            import tifffile
-            imgs = tifffile.imread(imgs)
+        raw = self._open(imgs, device, preprocess)
         self.max_patch_size, self.overlap_factor, self.batch_size = max_patch_size, overlap_factor, batch_size
-        raw = np.asarray(imgs)
         if preprocess == "host" or not DeviceFrontEnd.native(raw.dtype):
-            imgs = raw = np.array(imgs, dtype="float32")                 # the host path's cast; the device path keeps small integers as they are
-        if raw.ndim == 3:
-            imgs = raw = raw[None]
-        elif raw.ndim != 4:
+            raw = np.array(raw, dtype="float32")                         # the host path's cast; the device path keeps small integers as they are
+        if raw.ndim != 4:
             raise ValueError(f"Unsupported input shape: {raw.shape}")
         self.imgs_shape = raw.shape
         if preprocess == "device":
@@ -987,15 +982,14 @@ class PredictMo3d:
             origins = self._origins(raw.shape)
             patches = fe.tiles(origins, self.patch_size, out="float32", view=(1,) + self.patch_size)
         else:
-            imgs = self._preprocess(imgs, normalization_mode, clip_threshold)
-            patches = self._split(imgs)
-        mp = self.model_params = _load_params(model_params, self.device)
-        self.model = network(in_channels=mp["in_channels"], n_filter=mp["n_filter"], output_heads=mp["output_heads"],
-                             use_interpolation=mp.get("use_interpolation", True)).to(self.device)
-        self.model.load_state_dict(mp["state_dict"])
-        self.model.eval()
+            patches = self._split(self._preprocess(raw, normalization_mode, clip_threshold))
+        mp = self._load_model(model_params, network)
         self.target_keys = list(mp["output_heads"].keys())
         self.result = _write_heads(result_path, self._predict_and_blend(patches, batch_size))
+
+    def _build(self, mp, network):
+        return network(in_channels=mp["in_channels"], n_filter=mp["n_filter"], output_heads=mp["output_heads"],
+                       use_interpolation=mp.get("use_interpolation", True))
 
     @staticmethod
     def _preprocess(imgs, mode, clip):
@@ -1012,7 +1006,7 @@ class PredictMo3d:
 
     def _origins(self, shape):
         """Patch grid of ``multi_output_unet3d/predict.py:162-201``: sets ``patch_size``, the start lists and the counts and returns the
-        patch order as (volume, z, y, x) -- shared by the host ``_split`` and the device front end."""
+        patch order as (volume, z, y, x) -- shared by the host ``_split``, the device front end and the blend."""
         nvol, D, H, W = shape
         self.patch_size = ps = tuple(min(a, b) for a, b in zip((D, H, W), self.max_patch_size))
         stride = [max(1, int(s * (1 - self.overlap_factor))) for s in ps]
@@ -1025,12 +1019,11 @@ class PredictMo3d:
         self.Z_start, self.Y_start, self.X_start = starts(D, ps[0], stride[0]), starts(H, ps[1], stride[1]), starts(W, ps[2], stride[2])
         self.N_z, self.N_y, self.N_x = len(self.Z_start), len(self.Y_start), len(self.X_start)
         self.N_per_vol = self.N_z * self.N_y * self.N_x
-        return [(v, z, y, x) for v in range(nvol) for z in self.Z_start for y in self.Y_start for x in self.X_start]
+        self.origins = [(v, z, y, x) for v in range(nvol) for z in self.Z_start for y in self.Y_start for x in self.X_start]
+        return self.origins
 
     def _split(self, imgs):
-        origins = self._origins(imgs.shape)
-        ps = self.patch_size
-        return np.stack([imgs[v, z:z + ps[0], y:y + ps[1], x:x + ps[2]] for v, z, y, x in origins])[:, None]
+        return _cut(imgs, self._origins(imgs.shape), self.patch_size)[:, None]
 
     def _weights(self, flags, shape, blend_margin):
         """Blend mask of one patch; ``flags`` = (front, back, top, bottom, left, right) interior faces.  Restates the
@@ -1062,29 +1055,19 @@ class PredictMo3d:
         """Batches of patches through the network; every head's float32 patch is multiplied by its blend mask and added into
         the head's volume on the device, then ``vol / wsum`` where ``wsum > 0`` (``multi_output_unet3d/predict.py:203-307``)."""
         nvol, D, H, W = self.imgs_shape
-        ps = self.patch_size
+        grid = (self.N_z, self.N_y, self.N_x)
         heads = self.model_params["output_heads"]
-        stitch = {k: [_Stitcher(self.device, heads[k]["channels"], (D, H, W)) for _ in range(nvol)] for k in self.target_keys}
-        wcache = {}
-
-        def weight_of(zi, yi, xi):
-            flags = (zi > 0, zi < self.N_z - 1, yi > 0, yi < self.N_y - 1, xi > 0, xi < self.N_x - 1)
-            if flags not in wcache:
-                wcache[flags] = torch.from_numpy(self._weights(flags, (1,) + ps, blend_margin)[0]).to(self.device).contiguous()
-            return wcache[flags]
-        index = [(v, zi, yi, xi) for v in range(nvol) for zi in range(self.N_z) for yi in range(self.N_y) for xi in range(self.N_x)]
-        with torch.no_grad():
-            for b in range(0, len(patches), batch_size):
-                preds = self.model(_patch_batch(patches, b, b + batch_size, self.device))
-                for j in range(min(batch_size, len(patches) - b)):
-                    v, zi, yi, xi = index[b + j]
-                    wt = weight_of(zi, yi, xi)
-                    for k in self.target_keys:
-                        stitch[k][v].add(preds[k][j].float(), (self.Z_start[zi], self.Y_start[yi], self.X_start[xi]), weight=wt)
-        return {k: np.squeeze(torch.stack([s_.finish(False) for s_ in stitch[k]]).cpu().numpy()) for k in self.target_keys}
+        stitch = _HeadStitch(self.device, heads, nvol, (D, H, W), grid,
+                             lambda index, flags: self._weights(flags, (1,) + self.patch_size, blend_margin)[0])
+        for b, x in self._batches(patches, batch_size):
+            preds = self._forward(x)
+            for j in range(x.shape[0]):
+                vol, origin = self._place(b + j)
+                stitch.add({k: preds[k][j].float() for k in heads}, vol, origin, np.unravel_index((b + j) % self.N_per_vol, grid))
+        return {k: np.squeeze(torch.stack([s_.finish(False) for s_ in stitch[k]]).cpu().numpy()) for k in heads}
 
 
-class PredictMo2d:
+class PredictMo2d(_PredictBase):
     """``bio_image_unet.multi_output_unet.Predict`` counterpart (``multi_output_unet/predict.py:13-285``) for in-memory arrays (a path
     goes through ``tifffile`` when importable).
 
@@ -1108,18 +1091,11 @@ class PredictMo2d:
     def __init__(self, imgs, model_params, result_path=None, network=MultiOutputNestedUNet, max_patch_size=(1024, 1024), batch_size=1,
                  normalization_mode="single", clip_threshold=(0., 99.98), add_tile=0, compress_tif=False, show_progress=True,
                  device: Union[torch.device, str] = "auto", progress_notifier=None, preprocess="host"):
-        _check_preprocess(preprocess)
-        self.device = _pick_device(device)
-        if isinstance(imgs, str):
-            import tifffile
-            imgs = tifffile.imread(imgs)
+        raw = self._open(imgs, device, preprocess)
         self.max_patch_size, self.batch_size, self.add_tile = max_patch_size, batch_size, add_tile
         self.normalization_mode, self.clip_threshold, self.result_path = normalization_mode, clip_threshold, result_path
-        raw = np.asarray(imgs)
         if preprocess == "host" or not DeviceFrontEnd.native(raw.dtype):
-            imgs = raw = np.array(imgs, dtype="float32")                 # the host path's cast; the device path keeps small integers as they are
-        if raw.ndim == 2:
-            imgs = raw = raw[None]
+            raw = np.array(raw, dtype="float32")                         # the host path's cast; the device path keeps small integers as they are
         self.imgs_shape = raw.shape
         if preprocess == "device":
             # the host path normalises in numpy float32 (percentiles included); here the same formula runs in fp64 on the uploaded values and
@@ -1129,15 +1105,14 @@ class PredictMo2d:
             origins = self._origins()
             patches = fe.tiles(origins, (1,) + self.patch_size, out="float32")
         else:
-            imgs = self._preprocess(imgs, normalization_mode, clip_threshold)
-            patches = self._split(imgs)
-        mp = self.model_params = _load_params(model_params, self.device)
-        self.model = network(in_channels=mp["in_channels"], n_filter=mp["n_filter"], output_heads=mp["output_heads"],
-                             deep_supervision=mp.get("deep_supervision", False), train_mode=False).to(self.device)
-        self.model.load_state_dict(mp["state_dict"])
-        self.model.eval()
+            patches = self._split(self._preprocess(raw, normalization_mode, clip_threshold))
+        mp = self._load_model(model_params, network)
         self.target_keys = list(mp["output_heads"].keys())
         self.result = _write_heads(result_path, self._predict_and_stitch(patches, batch_size))
+
+    def _build(self, mp, network):
+        return network(in_channels=mp["in_channels"], n_filter=mp["n_filter"], output_heads=mp["output_heads"],
+                       deep_supervision=mp.get("deep_supervision", False), train_mode=False)
 
     @staticmethod
     def _preprocess(imgs, mode, clip):
@@ -1187,52 +1162,43 @@ class PredictMo2d:
         (ph, pw), (H, W) = self.patch_size, self.padded
         rows = list(range(0, H - ph + 1, sx))[:self.N_x]
         cols = list(range(0, W - pw + 1, sy))[:self.N_y]
-        return [(i, 0, r, c) for i in range(self.imgs_shape[0]) for r in rows for c in cols]
+        self.origins = [(i, 0, r, c) for i in range(self.imgs_shape[0]) for r in rows for c in cols]
+        return self.origins
+
+    def _place(self, k):
+        """Window ``k`` of the cut list goes to its image at ``(X_start[j], Y_start[c])``, (j, c) being its place in the image's grid: the
+        origin it was cut at wherever the stride ``X_start[1]`` reproduces ``X_start`` (always with up to two tiles per axis), and upstream's
+        choice (``predict.py:252-253``) where truncation makes the two drift apart."""
+        j, c = divmod(k % self.N_per_img, self.N_y)
+        return self.origins[k][0], (0, int(self.X_start[j]), int(self.Y_start[c]))
 
     def _split(self, imgs):
-        sx, sy = self._strides()
-        ph, pw = self.patch_size
-        H, W = self.padded
-        imgs = np.pad(imgs, ((0, 0), (0, H - self.imgs_shape[1]), (0, W - self.imgs_shape[2])), "reflect")
-        win = np.lib.stride_tricks.sliding_window_view(imgs, self.patch_size, axis=(1, 2))[:, ::sx, ::sy][:, :self.N_x, :self.N_y]
-        return np.ascontiguousarray(win).reshape(-1, ph, pw)
+        return _cut(imgs[:, None], self._origins(), (1,) + self.patch_size)[:, 0]
 
     def _predict_and_stitch(self, patches, batch_size):
         n_img, h, w = self.imgs_shape
         ph, pw = self.patch_size
-        heads, cin = self.model_params["output_heads"], self.model_params["in_channels"]
-        H, W = max(ph, h), max(pw, w)
-        stitch = {k: [_Stitcher(self.device, heads[k]["channels"], (1, H, W)) for _ in range(n_img)] for k in self.target_keys}
-        sums = {k: torch.zeros((), dtype=torch.float64, device=self.device) for k in self.target_keys}
-        wcache = {}
-
-        def weight_of(j, k):
-            flags = (j > 0, j < self.N_x - 1, k > 0, k < self.N_y - 1)
-            if flags not in wcache:
-                wcache[flags] = torch.from_numpy(self.weight_plane(j, k, self.N_x, self.N_y, self.patch_size)[None]).to(self.device).contiguous()
-            return wcache[flags]
-        with torch.no_grad():
-            for b in range(0, patches.shape[0], batch_size):
-                x = _patch_batch(patches, b, b + batch_size, self.device).view(-1, cin, ph, pw)
-                out = self.model(x)
-                for key in self.target_keys:
-                    res = out[key]
-                    want = (x.shape[0], heads[key]["channels"], ph, pw)
-                    if tuple(res.shape) != want:
-                        raise RuntimeError(f"Shape mismatch for target key '{key}': predicted {tuple(res.shape)}, expected {want}")
-                    p16 = res.to(torch.float16).float()                 # the reference keeps patches as float16
-                    sums[key] += p16.double().sum()
-                    for i in range(p16.shape[0]):
-                        img, tile = divmod(b + i, self.N_per_img)
-                        j, k = divmod(tile, self.N_y)
-                        stitch[key][img].add(p16[i].unsqueeze(1), (0, int(self.X_start[j]), int(self.Y_start[k])), weight=weight_of(j, k))
+        cin, grid = self.model_params["in_channels"], (self.N_x, self.N_y)
+        heads = self.model_params["output_heads"]
+        stitch = _HeadStitch(self.device, heads, n_img, (1, max(ph, h), max(pw, w)), grid,
+                             lambda index, flags: self.weight_plane(*index, *grid, self.patch_size)[None])
+        sums = {k: torch.zeros((), dtype=torch.float64, device=self.device) for k in heads}
+        for b, x in self._batches(patches, batch_size):
+            x = x.view(-1, cin, ph, pw)
+            out, p16 = self._forward(x), {}
+            for key, cfg in heads.items():
+                want = (x.shape[0], cfg["channels"], ph, pw)
+                if tuple(out[key].shape) != want:
+                    raise RuntimeError(f"Shape mismatch for target key '{key}': predicted {tuple(out[key].shape)}, expected {want}")
+                p16[key] = out[key].to(torch.float16).float()       # the reference keeps patches as float16
+                sums[key] += p16[key].double().sum()
+            for i in range(x.shape[0]):
+                img, origin = self._place(b + i)
+                stitch.add({key: p[i].unsqueeze(1) for key, p in p16.items()}, img, origin, divmod((b + i) % self.N_per_img, self.N_y))
         result = {}
-        for key in self.target_keys:
-            c = heads[key]["channels"]
-            fill = float(np.float16(float(sums[key]) / (patches.shape[0] * c * ph * pw)))      # np.mean of a float16 array is float16
-            done = []
-            for s_ in stitch[key]:
-                done.append(torch.where(s_.wsum[0].unsqueeze(0) > 0, s_.finish(False), torch.full((), fill, device=self.device)))
+        for key, cfg in heads.items():
+            fill = float(np.float16(float(sums[key]) / (len(patches) * cfg["channels"] * ph * pw)))      # np.mean of a float16 array is float16
+            done = [torch.where(s_.wsum[0].unsqueeze(0) > 0, s_.finish(False), torch.full((), fill, device=self.device)) for s_ in stitch[key]]
             res = torch.stack(done).cpu().numpy()[:, :, 0]               # (n_img, channels, H, W)
             result[key] = np.squeeze(res[:, :, :h, :w])
         return result

@@ -178,10 +178,7 @@ def test_siam_layout_and_constant_pad(frames, tile, mode):
     """``PredictSiam``'s host lines per frame: the pair normalised as one float64 stack, cast to uint8, zero-padded, cut into
     [N, 2, th, tw] with channel 0 the current frame."""
     movie = np.random.default_rng(12).integers(50, 4000, (frames, 37, 53)).astype(np.uint16)
-    p = _bare(Wf.PredictSiam, imgs_shape=[frames, 37, 53], resize_dim=tile)
-    p.N_x, p.N_y = int(np.ceil(37 / tile[0])), int(np.ceil(53 / tile[1]))
-    p.N = p.N_x * p.N_y
-    p.X_start, p.Y_start = Wf.tile_starts(37, tile[0], p.N_x), Wf.tile_starts(53, tile[1], p.N_y)
+    p = _bare(Wf.PredictSiam, imgs_shape=[frames, 37, 53], resize_dim=tile, add_tile=0)
     fe = P.DeviceFrontEnd(movie, "cuda")
     fe.normalise_pairs(mode, (0.2, 99.8))
     pairs = fe.pair_tiles(p._origins(), tile, invert=True)

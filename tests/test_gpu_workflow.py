@@ -470,6 +470,73 @@ def test_predict_mo3d_blend_stub():
     np.testing.assert_allclose(p.result["b"][1], 0.2 + 0.5 * c, rtol=1e-5, atol=1e-6)
 
 
+def test_predict_mo3d_batches_cross_volumes_stub():
+    """Two volumes of 12 patches each in batches of 5 (5, 5, 5, 5, 4: the third straddles the volumes, the last is ragged) against batches
+    of 1.  The stub is point-wise and every stitcher gets its patches in the same order with the same weights whatever the batching, so the
+    results are equal bit for bit; the closed form is the one of ``test_predict_mo3d_blend_stub``, per volume."""
+    import numpy as np
+    from bio_image_unet_amd.workflow import PredictMo3d
+    heads = {"a": {"channels": 1, "activation": "sigmoid", "loss": "BCEDiceLoss"}, "b": {"channels": 2, "activation": None, "loss": "DiceLoss"}}
+    vols = np.random.RandomState(4).rand(2, 12, 40, 24).astype("float32") * 50
+    ck = {"in_channels": 1, "n_filter": 4, "output_heads": heads, "use_interpolation": True, "state_dict": _StubHeads(output_heads=heads).state_dict()}
+    p5, p1 = (PredictMo3d(vols.copy(), ck, network=_StubHeads, max_patch_size=(8, 16, 16), overlap_factor=0.25, batch_size=bs, show_progress=False,
+                          device="cuda") for bs in (5, 1))
+    assert p5.N_per_vol == 12 and len(p5.origins) == 24 and p5.Z_start == [0, 4] and p5.Y_start == [0, 12, 24] and p5.X_start == [0, 8]
+    for k in heads:
+        assert p5.result[k].shape == p1.result[k].shape and np.array_equal(p5.result[k], p1.result[k]), k
+    assert p5.result["a"].shape == (2, 12, 40, 24) and p5.result["b"].shape == (2, 2, 12, 40, 24)
+    for v in range(2):
+        c = np.clip(vols[v], np.percentile(vols[v], 0.), np.percentile(vols[v], 99.98))
+        c = (c - c.min()) / (np.ptp(c) + 1e-8)
+        np.testing.assert_allclose(p5.result["a"][v], 0.1 + 0.5 * c, rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose(p5.result["b"][v, 1], 0.2 + 0.5 * c, rtol=1e-5, atol=1e-6)
+
+
+class _StubHeads2D(_StubHeads):
+    """``_StubHeads`` for [B, 1, H, W] batches, with the constructor keywords ``PredictMo2d`` passes."""
+
+    def __init__(self, deep_supervision=False, train_mode=False, **kw):
+        super().__init__(**kw)
+
+    def forward(self, x):
+        return {k: (0.1 * (i + 1) + 0.5 * x).repeat(1, v["channels"], 1, 1) for i, (k, v) in enumerate(self.heads.items())}
+
+
+@pytest.mark.parametrize("preprocess", ["host", "device"])
+def test_predict_mo2d_batches_cross_images_stub(preprocess):
+    """Two images of 2 x 2 tiles in batches of 3 (3, 3, 2: the second straddles the images, the last is ragged) against batches of 1.  Exact
+    by construction: the stub is point-wise, every stitcher gets its patches in the same order, and the fill of the unweighted pixels is a
+    float64 sum of 8 x channels x 48 x 48 float16 values below 1 (multiples of 2^-14 or coarser, at most 29 bits), exact in any grouping.
+
+    Closed form where some tile has weight: every tile predicts the same value there, weights are 0 or 1, and (v + v) / 2 == v, so the
+    result is float16(0.1 + 0.5 * x) of the normalised pixel.  Bound, derived: the device may contract the stub's multiply-add and the
+    device front end rounds x once from fp64 where numpy rounds in float32 -- a few float32 ulps, which can move the float16 rounding to
+    the neighbouring value and no further: one float16 ulp below 1, 2^-11."""
+    import numpy as np
+    from bio_image_unet_amd.workflow import PredictMo2d
+    heads = {"a": {"channels": 1, "activation": "sigmoid", "loss": "BCEDiceLoss"}, "b": {"channels": 2, "activation": None, "loss": "DiceLoss"}}
+    imgs = (np.random.RandomState(5).rand(2, 50, 80) * 900 + 17).astype("float32")
+    ck = {"in_channels": 1, "n_filter": 4, "output_heads": heads, "deep_supervision": False, "state_dict": _StubHeads2D(output_heads=heads).state_dict()}
+    p3, p1 = (PredictMo2d(imgs.copy(), ck, network=_StubHeads2D, max_patch_size=(48, 48), batch_size=bs, show_progress=False, device="cuda",
+                          preprocess=preprocess) for bs in (3, 1))
+    assert p3.patch_size == (48, 48) and (p3.N_x, p3.N_y) == (2, 2) and p3.N == 8
+    for k in heads:
+        assert p3.result[k].shape == p1.result[k].shape and np.array_equal(p3.result[k], p1.result[k]), k
+    assert p3.result["a"].shape == (2, 50, 80) and p3.result["b"].shape == (2, 2, 50, 80)
+    wsum = np.zeros((50, 80))
+    for j, xs in enumerate(p3.X_start):
+        for k, ys in enumerate(p3.Y_start):
+            wsum[xs:xs + 48, ys:ys + 48] += PredictMo2d.weight_plane(j, k, 2, 2, (48, 48))
+    weighted = wsum > 0
+    assert weighted.any() and not weighted.all()            # (the columns between the two tiles' safe margins get the fill)
+    norm = PredictMo2d._preprocess(imgs.copy(), "single", (0., 99.98))
+    want = (np.float32(0.1) + np.float32(0.5) * norm).astype("float16").astype("float32")
+    dev = np.abs(p3.result["a"] - want)[:, weighted].max()
+    print(f"mo2d stub head a ({preprocess}): worst deviation from the closed form {dev:.3e} (bound {2.0 ** -11:.3e})")
+    assert dev <= 2.0 ** -11
+    assert np.unique(p3.result["a"][:, ~weighted]).size == 1       # one fill value, the float16 mean of the head's patches
+
+
 
 
 @pytest.mark.timeout(180)

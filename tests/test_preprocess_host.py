@@ -97,10 +97,7 @@ def test_origins_reproduce_split_3d(resize_dim):
 @pytest.mark.parametrize("resize_dim", [(8, 12), (24, 32)])
 def test_origins_reproduce_split_siam(resize_dim):
     pair = np.random.default_rng(2).integers(0, 256, (2, 19, 27)).astype("uint8")
-    p = _bare(Wf.PredictSiam, imgs_shape=[5, 19, 27], resize_dim=resize_dim)
-    p.N_x, p.N_y = int(np.ceil(19 / resize_dim[0])), int(np.ceil(27 / resize_dim[1]))
-    p.N = p.N_x * p.N_y
-    p.X_start, p.Y_start = Wf.tile_starts(19, resize_dim[0], p.N_x), Wf.tile_starts(27, resize_dim[1], p.N_y)
+    p = _bare(Wf.PredictSiam, imgs_shape=[5, 19, 27], resize_dim=resize_dim, add_tile=0)
     want = p._split(pair.copy())
     o = p._origins()
     cur = _gather(pair[1][None, None], o, (1,) + resize_dim, "zero")
@@ -123,3 +120,39 @@ def test_origins_reproduce_split_mo2d(shape, max_patch, add_tile):
     want = p._split(imgs)
     got = _gather(imgs[:, None], p._origins(), (1,) + p.patch_size, "reflect")
     assert want.shape == got[:, 0].shape and np.array_equal(want, got[:, 0])
+
+
+def _with_origins(cls, shape=None, **attrs):
+    p = _bare(cls, **attrs)
+    return p, (p._origins() if shape is None else p._origins(shape))
+
+
+STITCH_CASES = {
+    "2d": lambda: _with_origins(Wf.Predict2D, imgs_shape=(3, 19, 27), resize_dim=(8, 12), add_tile=1),
+    "3d": lambda: _with_origins(Wf.Predict3D, vol_shape=(10, 20, 18), resize_dim=(4, 8, 8), add_patch=1),
+    "siam": lambda: _with_origins(Wf.PredictSiam, imgs_shape=[5, 19, 27], resize_dim=(8, 12), add_tile=0),
+    "mo3d": lambda: _with_origins(Wf.PredictMo3d, shape=(2, 10, 20, 18), max_patch_size=(4, 8, 8), overlap_factor=0.25),
+    "mo2d": lambda: _with_origins(Wf.PredictMo2d, imgs_shape=(2, 50, 80), max_patch_size=(48, 48), add_tile=0),
+    "mo2d_add_tile": lambda: _with_origins(Wf.PredictMo2d, imgs_shape=(1, 50, 80), max_patch_size=(32, 32), add_tile=1),
+}
+
+
+@pytest.mark.parametrize("case", list(STITCH_CASES))
+def test_stitch_origins_are_the_cut_origins(case):
+    """Patch k is stitched into the image its cut origin names, at that origin without the leading index: one list states the tile order for
+    the cut (``_split``, the device front end) and for the stitch (``_place``)."""
+    p, origins = STITCH_CASES[case]()
+    assert len(origins) > 4 and origins is p.origins
+    assert [p._place(k) for k in range(len(origins))] == [(o[0], tuple(o[1:])) for o in origins]
+    assert len({o[0] for o in origins}) == {"2d": 3, "3d": 1, "siam": 1, "mo3d": 2, "mo2d": 2, "mo2d_add_tile": 1}[case]
+
+
+def test_mo2d_stitches_on_the_start_grid_where_the_stride_drifts():
+    """``PredictMo2d`` keeps upstream's pair of rules: windows are cut on the stride ``X_start[1]`` and stitched at ``X_start``.  With up to
+    two tiles per axis, or a stride that divides the extent (the cases above), the two are one grid; 100 rows in four tiles of 32 are not
+    (``linspace(0, 68, 4)`` truncates to 0, 22, 45, 68 against 0, 22, 44, 66), and there the stitch follows ``X_start``."""
+    p, origins = _with_origins(Wf.PredictMo2d, imgs_shape=(1, 100, 80), max_patch_size=(32, 32), add_tile=0)
+    assert list(p.X_start) == [0, 22, 45, 68] and sorted({o[2] for o in origins}) == [0, 22, 44, 66]
+    placed = [p._place(k) for k in range(len(origins))]
+    assert placed == [(0, (0, int(xs), int(ys))) for xs in p.X_start for ys in p.Y_start]
+    assert [at[2] for _, at in placed] == [o[3] for o in origins]           # the columns (0, 24, 48) agree

@@ -92,10 +92,7 @@ def main():
         return first
 
     # ---- PredictSiam -----------------------------------------------------------------------------------------------
-    ps = _bare(Wf.PredictSiam, imgs_shape=list(raw.shape), resize_dim=tile)
-    ps.N_x, ps.N_y = int(np.ceil(a.size / a.tile)), int(np.ceil(a.size / a.tile))
-    ps.N = ps.N_x * ps.N_y
-    ps.X_start, ps.Y_start = Wf.tile_starts(a.size, a.tile, ps.N_x), Wf.tile_starts(a.size, a.tile, ps.N_y)
+    ps = _bare(Wf.PredictSiam, imgs_shape=list(raw.shape), resize_dim=tile, add_tile=0)
 
     def host_siam(frames):
         first = None

@@ -58,6 +58,10 @@ class biu_augf_params(C.Structure):
                 ("gauss_sigma", C.c_float), ("angle", C.c_float), ("scale", C.c_float), ("dx", C.c_float), ("dy", C.c_float)]
 
 
+class biu_augf_source(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("h", C.c_int32), ("w", C.c_int32)]
+
+
 _P = C.c_void_p
 _A = C.POINTER(biu_act)
 _X = C.POINTER(biu_xform)
@@ -187,6 +191,7 @@ SIGNATURES = {
     "biu_augment_f32": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "biu_spline_prefilter_f32": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "biu_augment_f32_cubic": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "biu_augment_f32_crop": (_I, [_P, _I, C.c_ulonglong, _P, _I, _I, _I, _I, _I, _P, _P, _F, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "biu_augment_vol_f32": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "biu_augment_vol_chunk": (_I, [_I] * 8),
     "biu_philox_u32": (_I, [_P, C.c_longlong, C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, C.c_uint, _P]),

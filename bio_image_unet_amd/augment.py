@@ -32,6 +32,8 @@ This is distribution-level equivalence to the reference pipeline, not bit parity
 The 2-D multi-output family's float fields have a pipeline of their own, ``AugmenterF32`` / ``biu_augment_f32`` in the second half of this file;
 the 3-D multi-output family's volumes a third, ``AugmenterVol`` / ``biu_augment_vol_f32`` at the end.  The three classes share the record
 stream and the launch loop (``_AugmenterCore``) and keep their own limits and kernels (the two float classes share the record).
+``AugmenterF32`` also draws crops out of WHOLE items (``draw_crops`` / ``crop_matrix`` / ``biu_augment_f32_crop``, for ``feed.ImageStore``):
+the same record and stream, the map going from a tile pixel into the item, NaN targets replaced by ``nan_to_val`` on the way.
 """
 from __future__ import annotations
 
@@ -159,10 +161,14 @@ class _AugmenterCore:
         shape = tuple(shape) if shape is not None else self.shape
         if shape is None or len(shape) < 2:
             raise ValueError(f"{type(self).__name__}.draw needs the tile shape (constructor's or this call's `shape`)")
+        pack = self._packer(int(shape[-2]), int(shape[-1]))
+        return self._records(epoch, indices, lambda i: pack)
+
+    def _records(self, epoch: int, indices, pack_of) -> np.ndarray:
+        """The record stream under ``draw``: sample ``i`` is packed by ``pack_of(i)`` from its own uniforms."""
         idx = np.atleast_1d(np.asarray(indices, dtype=np.int64)).tolist()
         size, n = self._rec.size, self.n_uniform
         buf = bytearray(len(idx) * size)
-        pack = self._packer(int(shape[-2]), int(shape[-1]))
         key = (self.seed, int(epoch) & 0xFFFFFFFFFFFFFFFF)
         with self._lock:
             for j, i in enumerate(idx):
@@ -173,7 +179,7 @@ class _AugmenterCore:
                 st["state"]["counter"][:] = (0, i & 0xFFFFFFFFFFFFFFFF, 0, 0)
                 st["buffer_pos"], st["has_uint32"] = 4, 0
                 self._bitgen.state = st
-                pack(buf, j * size, i & 0xFFFFFFFF, self._gen.random(n).tolist())
+                pack_of(i)(buf, j * size, i & 0xFFFFFFFF, self._gen.random(n).tolist())
         return np.frombuffer(buf, dtype=self.params_dtype)
 
     # ---- device ------------------------------------------------------------------------------------------------------------------
@@ -349,6 +355,86 @@ def record_f32(index: int, h: int, w: int, *, rot_k: int = 0, angle: Optional[fl
     return np.frombuffer(buf, dtype=PARAMS_F32_DTYPE)[0]
 
 
+# ---- whole items (``feed.ImageStore``, ``biu_augment_f32_crop``): the map goes from an output TILE pixel to a coordinate in the ITEM --------------
+SOURCE_DTYPE = np.dtype([("offset", "<u8"), ("h", "<i4"), ("w", "<i4")])     # include/biu.h: biu_augf_source, 16 bytes
+assert SOURCE_DTYPE.itemsize == 16
+VALIDATION_EPOCH = 0xFFFFFFFF                                                # the fixed epoch key of validation patches
+
+
+def _after(a, b):
+    """The 2x3 map ``a`` applied to the result of the 2x3 map ``b``, in plain Python floats."""
+    return (a[0] * b[0] + a[1] * b[3], a[0] * b[1] + a[1] * b[4], a[0] * b[2] + a[1] * b[5] + a[2],
+            a[3] * b[0] + a[4] * b[3], a[3] * b[1] + a[4] * b[4], a[3] * b[2] + a[4] * b[5] + a[5])
+
+
+def _crop_matrix(k, angle, scale, ox, oy, h, w):
+    k %= 4
+    ht, wt = (w, h) if k % 2 else (h, w)                     # the turned item
+    # 1. crop origin, 2. scale about pixel centres: tile pixel -> pixel of the scaled image -> coordinate in the turned, rotated item
+    inv = 1.0 / scale
+    shift = 0.5 * inv - 0.5
+    m = (inv, 0.0, ox * inv + shift, 0.0, inv, oy * inv + shift)
+    # 3. rotation about the item centre (``_matrix``'s sign: +90 degrees equals np.rot90(x, 1))
+    if angle != 0:
+        t = math.radians(angle)
+        c, s = math.cos(t), math.sin(t)
+        cx, cy = (wt - 1) / 2.0, (ht - 1) / 2.0
+        m = _after((c, -s, cx - (c * cx - s * cy), s, c, cy - (s * cx + c * cy)), m)
+    # 4. quarter turn: np.rot90(src, k)[y, x] = src[sy, sx], an index permutation
+    if k == 1:
+        m = _after((0.0, -1.0, w - 1.0, 1.0, 0.0, 0.0), m)
+    elif k == 2:
+        m = _after((-1.0, 0.0, w - 1.0, 0.0, -1.0, h - 1.0), m)
+    elif k == 3:
+        m = _after((0.0, 1.0, 0.0, -1.0, 0.0, h - 1.0), m)
+    return tuple(v + 0.0 for v in m)                         # no negative zeros
+
+
+def crop_matrix(rot_k: int, angle: float, scale: float, origin, item_hw, tile_hw=None) -> np.ndarray:
+    """float64 ``[m0 .. m5]``: pixel (x, y) of an output tile samples the ITEM ``[h, w]`` at ``(m0 x + m1 y + m2, m3 x + m4 y + m5)``.  Four
+    steps in one map: the crop ``origin = (ox, oy)`` in the scaled image; ``scale`` about pixel centres (pixel X of the scaled image is
+    ``(X + 0.5) / scale - 0.5``); rotation by ``angle`` degrees about the centre of the turned item; ``rot_k`` quarter turns
+    (``np.rot90(item, rot_k)``, which is ``w x h`` for odd ``rot_k``).  The tile extent does not enter the map (a tile larger than the scaled
+    item simply wraps); ``tile_hw`` is accepted so that a call names everything a crop consists of.  Whole-pixel cases are exact integers."""
+    if not scale > 0:
+        raise ValueError("scale must be positive")
+    return np.array(_crop_matrix(int(rot_k), float(angle), float(scale), float(origin[0]), float(origin[1]), int(item_hw[0]), int(item_hw[1])))
+
+
+def _pack_crop(buf, offset, index, h, w, rot_k, angle, scale, origin, blur_k, shot_s, gauss_sigma, bc):
+    """``_pack_f32`` for a crop out of a whole item ``[h, w]``: the same record, ``m`` from ``_crop_matrix``, ``dx, dy`` the crop origin."""
+    flags = ((ROT_F if angle is not None else 0) | (SCALE_F if scale is not None else 0) | (BLUR_F if blur_k else 0)
+             | (SHOT_F if shot_s is not None else 0) | (GAUSS_F if gauss_sigma is not None else 0) | (BC_F if bc is not None else 0))
+    a = _f32(angle) if angle is not None else 0.0
+    s = _f32(scale) if scale is not None else 1.0
+    ox, oy = float(int(origin[0])), float(int(origin[1]))
+    qc, qs = _QUARTER[rot_k % 4]
+    if a != 0:
+        t = math.radians(a)
+        ca, sa = math.cos(t), math.sin(t)
+        ct, st = qc * ca - qs * sa, qs * ca + qc * sa
+    else:
+        ct, st = qc, qs
+    alpha, beta = bc if bc is not None else (1.0, 0.0)
+    _REC_F32.pack_into(buf, offset, flags, rot_k, blur_k, index, *_crop_matrix(rot_k, a, s, ox, oy, h, w), ct + 0.0, st + 0.0, alpha, beta,
+                       shot_s if shot_s is not None else 0.0, gauss_sigma if gauss_sigma is not None else 0.0, a, s, ox, oy)
+
+
+def record_crop(index: int, item_hw, *, rot_k: int = 0, angle: Optional[float] = None, scale: Optional[float] = None, origin=(0, 0),
+                blur_k: int = 0, shot_s: Optional[float] = None, gauss_sigma: Optional[float] = None, bc=None) -> np.ndarray:
+    """One ``biu_augf_params`` record for ``biu_augment_f32_crop`` from its logical description (``record_f32``'s, with ``origin = (ox, oy)`` the
+    crop's first pixel in the turned, rotated and scaled item).  ``AugmenterF32.draw_crops`` builds its records the same way."""
+    if blur_k and (blur_k % 2 == 0 or not 1 <= blur_k <= MAX_BLUR):
+        raise ValueError(f"blur kernel {blur_k}: odd and at most {MAX_BLUR}")
+    if shot_s is not None and not shot_s > 0:
+        raise ValueError("shot noise needs a positive scale")
+    if scale is not None and not scale > 0:
+        raise ValueError("scale must be positive")
+    buf = bytearray(_REC_F32.size)
+    _pack_crop(buf, 0, int(index), int(item_hw[0]), int(item_hw[1]), int(rot_k), angle, scale, origin, int(blur_k), shot_s, gauss_sigma, bc)
+    return np.frombuffer(buf, dtype=PARAMS_F32_DTYPE)[0]
+
+
 def _pair(v, what):
     v = (v, v) if np.isscalar(v) else tuple(v)
     if len(v) != 2:
@@ -442,6 +528,82 @@ class AugmenterF32(_AugmenterCore):
                       lerp(u[12], gauss_lims) if u[11] < P["gauss_noise"] else None,
                       (1.0 + (2.0 * u[14] - 1.0) * bcl[1], (2.0 * u[15] - 1.0) * bcl[0]) if u[13] < P["brightness_contrast"] else None)
         return pack
+
+    # ---- whole items: crops out of a ``feed.ImageStore`` ---------------------------------------------------------------------------------
+    def _crop_packer(self, h, w, th, tw):
+        """``draw_crops``' record from the same sixteen uniforms behind the same gates as ``_packer``.  What differs: the quarter turns are
+        drawn from {0, 1, 2, 3} whatever the item's shape (the turned item is ``w x h`` and the crop comes out of it), and ``u[5]``, ``u[6]``
+        ALWAYS place the crop -- ``RandomCrop`` has ``p = 1`` -- in the turned item's extent times the scale, rounded."""
+        lerp = lambda u, lim: lim[0] + u * (lim[1] - lim[0])
+        P, sizes, bcl, rotate = STAGE_P_MO2D, self.blur_sizes, self.brightness_contrast, self.random_rotate
+        scale_limit, shot_lims, gauss_lims = self.scale_limit, self.shot_noise_lims, self.gauss_noise_lims
+
+        def pack(buf, offset, index, u):
+            rot_k, angle, scale = 0, None, None
+            if rotate:
+                if u[0] < P["arbitrary_angle"]:
+                    angle = 360.0 * u[1]
+                else:
+                    rot_k = int(u[2] * 4)
+            if u[3] < P["scale"]:
+                scale = _f32(1.0 + lerp(u[4], scale_limit))
+            s = scale if scale is not None else 1.0
+            ht, wt = (w, h) if rot_k % 2 else (h, w)
+            hs, ws = max(int(round(ht * s)), 1), max(int(round(wt * s)), 1)
+            ox = min(int(u[5] * (ws - tw + 1)), ws - tw) if ws >= tw else 0          # a scaled item smaller than the tile: the wrap pads
+            oy = min(int(u[6] * (hs - th + 1)), hs - th) if hs >= th else 0
+            _pack_crop(buf, offset, index, h, w, rot_k, angle, scale, (ox, oy),
+                       sizes[min(int(u[8] * len(sizes)), len(sizes) - 1)] if u[7] < P["blur"] else 0,
+                       lerp(u[10], shot_lims) if u[9] < P["shot_noise"] else None,
+                       lerp(u[12], gauss_lims) if u[11] < P["gauss_noise"] else None,
+                       (1.0 + (2.0 * u[14] - 1.0) * bcl[1], (2.0 * u[15] - 1.0) * bcl[0]) if u[13] < P["brightness_contrast"] else None)
+        return pack
+
+    def draw_crops(self, epoch: int, patch_indices, store, offsets: Optional[Dict[str, np.ndarray]] = None):
+        """Records and sources for the patches ``patch_indices`` of a ``feed.ImageStore`` in epoch ``epoch``: a pure function of
+        ``(seed, epoch, patch index)`` -- Philox key ``(seed, epoch)``, counter = the patch index, ``draw``'s stream.  Returns
+        ``(records [n], {field: sources [n]})``; a source is ``(element offset of the patch's item in the field's arena, h, w)``.
+        ``offsets``: the per-item offsets ``store.to_device`` returned (default: the store's own, which are the same numbers)."""
+        idx = np.atleast_1d(np.asarray(patch_indices, dtype=np.int64))
+        items = store.locate(idx)
+        th, tw = (int(d) for d in store.dim_out)
+        sizes, packers, item_of = store.sizes, {}, dict(zip(idx.tolist(), items.tolist()))
+
+        def pack_of(j):
+            h, w = sizes[item_of[j]]
+            if (h, w) not in packers:
+                packers[(h, w)] = self._crop_packer(int(h), int(w), th, tw)
+            return packers[(h, w)]
+
+        records = self._records(epoch, idx, pack_of)
+        offsets = offsets if offsets is not None else store.offsets
+        sources = {}
+        for name in store.fields:
+            src = np.empty(len(idx), dtype=SOURCE_DTYPE)
+            src["offset"], src["h"], src["w"] = np.asarray(offsets[name])[items], sizes[items, 0], sizes[items, 1]
+            sources[name] = src
+        return records, sources
+
+    def launch_crop(self, name, arena, dst, params_dev, sources_dev, nan_to_val, max_blur, epoch):
+        """One ``biu_augment_f32_crop`` launch on the current stream: field ``name`` of ``dst.shape[0]`` patches ``dst [n, planes, th, tw]`` out
+        of the 1-D device tensor ``arena``; ``params_dev`` / ``sources_dev``: the records and this field's sources on the device, as bytes."""
+        from ._lib import check, lib
+        kind = KINDS_F32[self.kind(name)]
+        if arena.dtype not in self.src_dtypes or not arena.is_cuda or arena.dim() != 1 or not arena.is_contiguous():
+            raise ValueError(f'field "{name}": the arena is a contiguous 1-D {_names(self.src_dtypes)} device tensor')
+        if dst.dtype != torch.float32 or dst.dim() != 4 or not dst.is_contiguous() or dst.device != arena.device:
+            raise ValueError(f'field "{name}": the output is a contiguous float32 tensor [n, planes, th, tw] on the arena\'s device')
+        n, planes, th, tw = dst.shape
+        if kind == KIND_VECTOR and planes % 2:
+            raise ValueError(f'field "{name}": a vector field holds (cos, sin) plane pairs, got {planes} plane(s)')
+        if params_dev.numel() * params_dev.element_size() < n * PARAMS_F32_DTYPE.itemsize or \
+                sources_dev.numel() * sources_dev.element_size() < n * SOURCE_DTYPE.itemsize:
+            raise ValueError(f"{n} patches need {n} parameter records and {n} sources")
+        check(lib.biu_augment_f32_crop(C.c_void_p(arena.data_ptr()), int(arena.dtype == torch.uint8), arena.numel(), C.c_void_p(dst.data_ptr()),
+                                       n, planes, th, tw, kind, C.c_void_p(params_dev.data_ptr()), C.c_void_p(sources_dev.data_ptr()),
+                                       float(nan_to_val), max_blur if kind == KIND_IMAGE else 0, self.seed, int(epoch) & 0xFFFFFFFF,
+                                       field_id(name), C.c_void_p(torch.cuda.current_stream(arena.device).cuda_stream)), "augment_f32_crop")
+        return dst
 
     def _launch(self, lib, name, t, dst, planes, params_dev, max_blur, epoch, stream):
         kind = KINDS_F32[self.kind(name)]

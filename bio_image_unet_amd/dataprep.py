@@ -18,6 +18,9 @@ Contract (what the tests hold it to; every comparison is an equality)
 * ``gather``: tiles with ``np.pad(..., 'reflect')`` beyond the far end (``preprocess.reflect_index``), optional ``255 - v``.
 * The split (``split_starts``, ``origins_2d``, ``origins_3d``) is the reference's, ``add_patch`` quirk of ``unet3d/data.py:188-190`` included.
 * Masks are uint8; a bool mask is taken as 0 / 255.  The reference's ``int8`` round trip of masks is the identity on bytes.
+
+The 2-D multi-output family has a fourth entry point at the end of this file, ``prepare_mo2d``: its ``DataProcess`` keeps every image whole
+and crops at random, so the result is a ``feed.ImageStore`` of whole normalised images and float targets (NaN kept), not a store of tiles.
 """
 from __future__ import annotations
 
@@ -28,7 +31,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib, ptr as _ptr, stream as _stream
-from .feed import TileStore
+from .feed import ImageStore, TileStore
 from .preprocess import DeviceFrontEnd
 from .utils import get_device
 
@@ -351,5 +354,82 @@ def prepare_siam(pairs: Sequence, masks: Sequence, path: str, dim_out=(256, 256)
         m = edit_mask_siam(torch.from_numpy(np.ascontiguousarray(msk[None])).to(device), invert_masks, threshold_masks, skeletonize, dilate_mask, dilate_kernel)
         store.maps["mask"][n:n + len(org)] = gather(m, 1, [(0, y, x) for y, x in org], (1, th, tw)).view(len(org), th, tw).cpu().numpy()
         n += len(org)
+    store.flush()
+    return store
+
+
+# ---- the 2-D multi-output family: whole items, NaN targets ------------------------------------------------------------------------------------
+def _mo2d_items(images, targets, in_channels):
+    """The host half of ``prepare_mo2d``: every item as ``(image [C, H, W], {name: float32 [planes, H, W]})`` plus the planes and the
+    squeeze flag of every field.  Needs no device, so every ``ValueError`` of ``prepare_mo2d`` is raised before one is asked for."""
+    if len(images) == 0:
+        raise ValueError("no images")
+    if not targets:
+        raise ValueError("no targets")
+    for name, seq in targets.items():
+        if name == "image":
+            raise ValueError('a target cannot be named "image"')
+        if len(seq) != len(images):
+            raise ValueError(f'target "{name}": {len(seq)} items for {len(images)} images')
+    items, planes, squeeze = [], {}, {}
+    for i, img in enumerate(images):
+        img = _load(img)
+        unit = img[None] if img.ndim == 2 else img
+        if unit.ndim != 3 or unit.shape[0] != in_channels:
+            raise ValueError(f"image {i}: shape {img.shape} is not [H, W] or [{in_channels}, H, W] (in_channels = {in_channels})")
+        item = {}
+        for name, seq in targets.items():
+            t = _load(seq[i])
+            if t.dtype.kind not in "buif":
+                raise ValueError(f'target "{name}" of item {i}: bool or a real dtype, got {t.dtype}')
+            if t.shape[-2:] != unit.shape[1:] or t.ndim not in (2, 3) or (name == "orientation" and t.ndim != 2):
+                raise ValueError(f"Item: {i}. Shape mismatch: {name} has shape {t.shape} but expected {img.shape}")
+            t = t.astype(np.float32)
+            if name == "orientation":                        # an angle map becomes the rotated pair; NaN in both where the angle is NaN
+                t, sq = np.stack([np.cos(t), np.sin(t)]), False
+            else:
+                t, sq = (t[None], True) if t.ndim == 2 else (t, False)
+            if planes.setdefault(name, t.shape[0]) != t.shape[0] or squeeze.setdefault(name, sq) != sq:
+                raise ValueError(f'target "{name}" of item {i}: {t.shape[0]} plane(s), the items before it have {planes[name]}')
+            item[name] = t
+        items.append((unit, item))
+    return items, planes, squeeze
+
+
+def prepare_mo2d(images: Sequence, targets, path: str, dim_out=(256, 256), in_channels: int = 1, nan_to_val: float = 0,
+                 clip_threshold=(0., 99.99), aug_factor: float = 2, gauss_noise_lims=(0.01, 0.1), shot_noise_lims=(0.001, 0.01),
+                 brightness_contrast=(0.1, 0.1), blur_limit=(3, 5), random_rotate: bool = True, scale_limit=(0, 0), image_dtype: str = "f32",
+                 device="auto") -> ImageStore:
+    """``bio_image_unet.multi_output_unet.DataProcess`` up to its augmentation (``multi_output_unet/data.py:140-185``) from arrays, into a
+    ``feed.ImageStore`` of WHOLE items: ``TrainerMo2d(store, ...)`` then renders ``max(int(H W / (dh dw) aug_factor), 2)`` fresh random
+    crops per item and epoch on the device.  ``images``: ``[H, W]`` or ``[C, H, W]`` of any dtype the device front end uploads, each
+    normalised as one unit by ``DeviceFrontEnd.normalise('single', clip_threshold)`` and read back whole as float32 (``image_dtype="u8"``:
+    as bytes, a quarter of the arena).  ``targets``: ``{name: sequence}`` of ``[H, W]`` or ``[C, H, W]`` arrays, bool or real, stored as
+    float32 with NaN ("no label here") kept; the target named ``orientation`` is an angle map ``[H, W]`` and is stored as the two planes
+    ``(cos, sin)``.  ``add_tile`` and ``val_split`` of the reference do not apply (the Trainer splits patch indices)."""
+    if image_dtype not in ("f32", "u8"):
+        raise ValueError(f'image_dtype "{image_dtype}": "f32" or "u8"')
+    if len(dim_out) != 2 or min(dim_out) < 1:
+        raise ValueError(f"dim_out {dim_out}: (height, width) of a patch")
+    if not aug_factor > 0:
+        raise ValueError("aug_factor must be positive")
+    if not np.isfinite(nan_to_val):
+        raise ValueError("nan_to_val must be finite")
+    items, planes, squeeze = _mo2d_items(images, targets, int(in_channels))
+    device = _device(device)
+    fields = {"image": int(in_channels), **planes}
+    store = ImageStore.create(path, [u.shape[1:] for u, _ in items], fields,
+                              {**_attrs(dim_out, clip_threshold, gauss_noise_lims=gauss_noise_lims, shot_noise_lims=shot_noise_lims,
+                                        brightness_contrast=brightness_contrast, blur_limit=blur_limit, scale_limit=scale_limit),
+                               "random_rotate": bool(random_rotate), "aug_factor": aug_factor, "nan_to_val": float(nan_to_val)},
+                              {"image": image_dtype, **{k: "f32" for k in planes}}, {"image": in_channels == 1, **squeeze})
+    for i, (unit, item) in enumerate(items):
+        c, h, w = unit.shape
+        fe = DeviceFrontEnd(unit, device, depth=c)
+        fe.normalise("single", clip_threshold)
+        t = fe.tiles([(0, 0, 0, 0)], (c, h, w), out="uint8" if image_dtype == "u8" else "float32")
+        store.put(i, "image", t.batch(0, 1)[0].cpu().numpy())
+        for name, v in item.items():
+            store.put(i, name, v)
     store.flush()
     return store

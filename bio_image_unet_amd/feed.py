@@ -23,6 +23,11 @@ The 2-D multi-output family's items are float32 (``multi_output_unet/data.py:318
 ``"f32"`` (file ``<path>.<field>.f32``, written and read back bit for bit, never scaled); the feeder carries float fields as float32 and
 ``augment.AugmenterF32`` (2-D) or ``augment.AugmenterVol`` (volumes) augments them.  A mixed store (``image`` as u8, targets as f32) keeps the image's PCIe traffic at a quarter.
 ``AugmenterF32(target_interp="cubic")`` keeps its spline scratch per field: every augmentation launch of a feeder runs on one stream, so one augmenter serves one feeder.
+
+The reference's ``DataProcess`` of that family keeps every image WHOLE and crops at random out of the rotated image, with NaN in a target
+meaning "no label here" (``multi_output_unet/data.py:140-311``).  ``ImageStore`` holds such items -- whole, of differing size, NaN kept -- and
+``CropFeeder`` renders every training patch from them on the device (``biu_augment_f32_crop``); ``dataprep.prepare_mo2d`` writes one from raw
+arrays.  Both are at the end of this file.
 """
 from __future__ import annotations
 
@@ -253,6 +258,276 @@ class DeviceFeeder:
                 yield {k: v[:nb] for k, v in slot[out_key].items()}
                 done = torch.cuda.Event()
                 done.record(torch.cuda.current_stream(self.device))                  # everything enqueued so far read the slot
+                slot["free"] = done
+                slot["released"].set()
+        finally:
+            stop.set()
+            for slot in self.slots:
+                slot["released"].set()
+            while th.is_alive():
+                try:
+                    filled.get(timeout=0.05)
+                except queue.Empty:
+                    pass
+            th.join()
+
+
+# =====================================================================================================================================
+# whole items: the 2-D multi-output family's DataProcess (``multi_output_unet/data.py:140-311``)
+# =====================================================================================================================================
+_IMAGE_MAGIC = "biu-imagestore-1"
+_ITEM_LIMIT = 2 ** 31 - 4                     # planes * H * W of one item: the crop kernel's index math inside an item is 32-bit
+
+
+def patches_of(h: int, w: int, dim_out, aug_factor) -> int:
+    """The reference's number of crops per image: ``max(int(H W / (dh dw) * aug_factor), 2)`` (``multi_output_unet/data.py:258-259``)."""
+    return max(int((h * w) / (dim_out[0] * dim_out[1]) * aug_factor), 2)
+
+
+class ImageStore(torch.utils.data.Dataset):
+    """Whole items of differing size: per field one flat file ``<path>.<field>.f32`` / ``.u8`` (``TileStore``'s naming) that holds the items
+    one after the other, each ``[planes, H_i, W_i]``, and the header ``<path>.json`` (magic ``biu-imagestore-1``) with the planes and dtype
+    of every field, ``(H_i, W_i)`` of every item and ``attrs`` (``dim_out``, ``aug_factor``, ``nan_to_val``, ``clip_threshold`` and the
+    augmentation limits ``AugmenterF32.store_attrs`` lists).
+
+    Float fields may hold NaN ("no label here"), written and read back bit for bit; the field ``image`` may not.  Its length is the number
+    of PATCHES per epoch, the reference's count per item (``patches_of``) summed; ``locate(j)`` maps a patch index to its item.  Patches are
+    rendered on the device only (``CropFeeder`` / ``biu_augment_f32_crop``): ``__getitem__`` raises.  ``fields`` is the shape of a rendered
+    patch per field, as ``TileStore.fields`` is the shape of a tile."""
+
+    def __init__(self, path: str, mode: str = "r"):
+        with open(path + ".json") as f:
+            hdr = json.load(f)
+        if hdr.get("magic") != _IMAGE_MAGIC:
+            raise ValueError(f"{path}.json is not an image store header")
+        self.path, self.attrs = path, hdr.get("attrs", {})
+        self.sizes = np.asarray(hdr["items"], dtype=np.int64).reshape(-1, 2)
+        self.n_items = len(self.sizes)
+        self.planes = {k: int(v["planes"]) for k, v in hdr["fields"].items()}
+        self.dtypes = {k: v["dtype"] for k, v in hdr["fields"].items()}
+        self.squeeze = {k: bool(v.get("squeeze", False)) for k, v in hdr["fields"].items()}
+        self.dim_out = tuple(int(d) for d in self.attrs["dim_out"])
+        self.aug_factor = self.attrs.get("aug_factor", 2)
+        self.nan_to_val = float(self.attrs.get("nan_to_val", 0.0))
+        for k, v in self.attrs.items():
+            if not hasattr(self, k):
+                setattr(self, k, v)
+        self.fields = {k: self.dim_out if self.squeeze[k] else (p,) + self.dim_out for k, p in self.planes.items()}
+        pixels = self.sizes[:, 0] * self.sizes[:, 1]
+        start = np.concatenate([[0], np.cumsum(pixels)])
+        self.offsets = {k: start[:-1] * p for k, p in self.planes.items()}          # element offset of every item in its field's file
+        self.elements = {k: int(start[-1]) * p for k, p in self.planes.items()}
+        self.counts = np.asarray([patches_of(int(h), int(w), self.dim_out, self.aug_factor) for h, w in self.sizes], dtype=np.int64)
+        self._ends = np.cumsum(self.counts)
+        self.maps = {k: np.memmap(f"{path}.{k}.{self.dtypes[k]}", dtype=_NP_DTYPE[self.dtypes[k]], mode=mode, shape=(self.elements[k],))
+                     for k in self.planes}
+
+    # ---- construction ----------------------------------------------------------------------------------------------
+    @classmethod
+    def create(cls, path: str, sizes, fields: Dict[str, int], attrs: dict, dtypes=None, squeeze: Optional[Dict[str, bool]] = None) -> "ImageStore":
+        """An empty store for items of the extents ``sizes`` ``[(H_i, W_i)]``; ``fields``: planes per field; ``attrs`` needs ``dim_out``.
+        ``squeeze``: fields whose patches are handed out without the plane axis (one plane, given as ``[H, W]``)."""
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        if not sizes or not fields or any(h < 1 or w < 1 for h, w in sizes) or any(int(p) < 1 for p in fields.values()):
+            raise ValueError("an image store needs items and fields of positive extent")
+        if "dim_out" not in (attrs or {}) or len(attrs["dim_out"]) != 2 or min(attrs["dim_out"]) < 1:
+            raise ValueError("attrs needs dim_out = (height, width) of a patch")
+        for name, p in fields.items():
+            for i, (h, w) in enumerate(sizes):
+                if int(p) * h * w >= _ITEM_LIMIT:
+                    raise ValueError(f'field "{name}" of item {i}: {p} x {h} x {w} elements; one item holds fewer than 2^31 - 4 per field')
+        dtypes = _field_dtypes(fields, dtypes if dtypes is not None else "f32")
+        squeeze = {k: bool((squeeze or {}).get(k, False)) and int(fields[k]) == 1 for k in fields}
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        total = sum(h * w for h, w in sizes)
+        for k, p in fields.items():
+            np.memmap(f"{path}.{k}.{dtypes[k]}", dtype=_NP_DTYPE[dtypes[k]], mode="w+", shape=(total * int(p),)).flush()
+        plain = lambda v: [plain(e) for e in v] if isinstance(v, (tuple, list)) else v
+        hdr = {"magic": _IMAGE_MAGIC, "items": [list(s) for s in sizes], "attrs": {k: plain(v) for k, v in attrs.items()},
+               "fields": {k: {"planes": int(p), "dtype": dtypes[k], "squeeze": squeeze[k]} for k, p in fields.items()}}
+        with open(path + ".json", "w") as f:
+            json.dump(hdr, f)
+        return cls(path, mode="r+")
+
+    def item(self, i: int, name: str) -> np.ndarray:
+        """Item ``i`` of field ``name`` as a view ``[planes, H_i, W_i]`` of the map."""
+        h, w = (int(v) for v in self.sizes[i])
+        o, p = int(self.offsets[name][i]), self.planes[name]
+        return self.maps[name][o:o + p * h * w].reshape(p, h, w)
+
+    def put(self, i: int, name: str, value) -> None:
+        """Write item ``i`` of field ``name``: float fields as given (NaN kept, bit for bit), except that the field ``image`` is refused where
+        it is not finite; uint8 fields take bytes, or floats in [0, 1] as multiples of 1/255."""
+        dst = self.item(i, name)
+        v = np.asarray(value)
+        v = v[None] if v.ndim == 2 else v
+        if v.shape != dst.shape:
+            raise ValueError(f'field "{name}" of item {i}: expected {dst.shape}, got {v.shape}')
+        if name == "image" and v.dtype.kind == "f" and not np.isfinite(v).all():
+            raise ValueError(f'field "image" of item {i} holds non-finite values: NaN means "no label" and is for targets only')
+        if self.dtypes[name] == "f32":
+            dst[...] = v.astype(np.float32, copy=False)
+        elif v.dtype == np.uint8:
+            dst[...] = v
+        else:
+            dst[...] = np.clip(np.rint(v.astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
+
+    def flush(self):
+        for m in self.maps.values():
+            m.flush()
+
+    # ---- Dataset contract: patches per epoch -------------------------------------------------------------------------
+    def __len__(self):
+        return int(self._ends[-1])
+
+    def locate(self, j):
+        """Item of patch ``j`` (an index or an array of indices): patches ``0 .. counts[0] - 1`` come from item 0, and so on."""
+        idx = np.asarray(j, dtype=np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= len(self)):
+            raise IndexError(f"patch index outside 0 .. {len(self) - 1}")
+        res = np.searchsorted(self._ends, idx, side="right")
+        return int(res) if res.ndim == 0 else res
+
+    def __getitem__(self, j):
+        raise RuntimeError("ImageStore: patches are rendered on the device only (feed.CropFeeder, biu_augment_f32_crop); there is no CPU path")
+
+    def to_device(self, device):
+        """Upload every field once as ONE device tensor (the arena).  Returns ``(arenas {field: 1-D tensor}, offsets {field: int64 [items]},
+        H [items], W [items])``; the offsets count elements of the field's own arena.  A store that does not fit raises ``RuntimeError``.
+        The upload happens once per device and is kept (a ``put`` after it is not seen there)."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"ImageStore.to_device uploads to a GPU; got device '{device}'")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        cache = self.__dict__.setdefault("_arenas", {})      # the training and the validation feeder of a Trainer share one upload
+        if device not in cache:
+            cache[device] = self._upload(device)
+        return cache[device], {k: v.astype(np.int64) for k, v in self.offsets.items()}, self.sizes[:, 0].copy(), self.sizes[:, 1].copy()
+
+    def _upload(self, device):
+        arenas = {}
+        try:
+            for k, m in self.maps.items():
+                arenas[k] = torch.from_numpy(np.ascontiguousarray(m)).to(device)
+        except torch.cuda.OutOfMemoryError as e:
+            need = sum(self.elements[k] * (1 if self.dtypes[k] == "u8" else 4) for k in self.maps)
+            arenas.clear()
+            raise RuntimeError(f"ImageStore {self.path}: the store ({need} bytes) does not fit in the HBM of {device}; a streamed store is not "
+                               f"supported") from e
+        return arenas
+
+
+class CropFeeder:
+    """Iterable over device batches of random crops out of an ``ImageStore`` (one epoch per ``iter()``), ``depth`` batches in flight: what the
+    Trainer iterates when handed such a store.  The store is uploaded once (``ImageStore.to_device``); per batch a background thread draws
+    the records and sources (``AugmenterF32.draw_crops``), uploads the two small buffers on a copy stream and launches one
+    ``biu_augment_f32_crop`` per field into rotating output buffers in front of a ``ready`` event -- ``DeviceFeeder``'s slot and event hand-over,
+    a failure of the feeder thread surfaces in the consumer.  No tile bytes cross PCIe after the upload.
+
+    ``epoch_key``: ``None`` -- the epoch (``draw_crops``' second argument) advances per ``iter()``; a number -- every ``iter()`` uses it, so the
+    batches are the same every time (the Trainer's validation feeder: ``augment.VALIDATION_EPOCH``)."""
+
+    def __init__(self, store: ImageStore, patch_indices: Sequence[int], batch_size: int, device, augmenter, epoch_key: Optional[int] = None,
+                 depth: int = 3, drop_last: bool = True):
+        from .augment import PARAMS_F32_DTYPE, SOURCE_DTYPE
+        self.store, self.indices, self.batch_size = store, [int(i) for i in patch_indices], int(batch_size)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"CropFeeder renders on a GPU; got device '{device}'")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if augmenter is None or not hasattr(augmenter, "draw_crops"):
+            raise ValueError("CropFeeder needs an augment.AugmenterF32: an ImageStore cannot be read un-augmented")
+        if getattr(augmenter, "target_interp", "linear") == "cubic":
+            raise NotImplementedError('target_interp="cubic" on an ImageStore: the spline coefficients and the clip range of a whole item depend '
+                                      'on the item alone and belong computed once at upload, which is not implemented; use "linear"')
+        self.augmenter, self.epoch_key, self.epoch = augmenter, epoch_key, 0
+        self.drop_last, self.depth = drop_last, max(2, depth)
+        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self.arenas, self.offsets, _, _ = store.to_device(self.device)
+        self.names = list(store.fields)
+        th, tw = store.dim_out
+        rec, src = PARAMS_F32_DTYPE.itemsize, SOURCE_DTYPE.itemsize
+        self._rec_bytes, self._src_bytes = batch_size * rec, batch_size * src
+        small = self._rec_bytes + len(self.names) * self._src_bytes                  # records, then one block of sources per field
+        self.slots = [{"out": {k: torch.empty((batch_size, store.planes[k], th, tw), dtype=torch.float32, device=self.device) for k in self.names},
+                       "host": torch.empty(small, dtype=torch.uint8).pin_memory(),
+                       "dev": torch.empty(small, dtype=torch.uint8, device=self.device),
+                       "ready": None, "free": None, "released": threading.Event()} for _ in range(self.depth)]
+
+    def __len__(self):
+        n = len(self.indices)
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def _view(self, slot, nb):
+        return {k: (v[:nb, 0] if self.store.squeeze[k] else v[:nb]) for k, v in slot["out"].items()}
+
+    def __iter__(self):
+        from .augment import BLUR_F
+        batches = [self.indices[i:i + self.batch_size] for i in range(0, len(self.indices), self.batch_size)]
+        if self.drop_last:
+            batches = [b for b in batches if len(b) == self.batch_size]
+        filled: "queue.Queue" = queue.Queue(maxsize=self.depth - 1)
+        epoch = self.epoch if self.epoch_key is None else int(self.epoch_key)
+        self.epoch += 1
+        stop = threading.Event()
+        for slot in self.slots:
+            slot["released"].set()
+            slot["free"] = None
+        nan_to_val = self.store.nan_to_val
+
+        def producer():
+            try:
+                produce()
+            except BaseException as e:                       # surface a failure of the feeder thread in the training thread
+                filled.put(e)
+
+        def produce():
+            torch.cuda.set_device(self.device)
+            for bi, idx in enumerate(batches):
+                slot = self.slots[bi % self.depth]
+                slot["released"].wait()
+                slot["released"].clear()
+                if stop.is_set():
+                    break
+                if slot["free"] is not None:
+                    slot["free"].synchronize()              # the step that read the slot's output buffers has finished on the GPU
+                params, sources = self.augmenter.draw_crops(epoch, idx, self.store, self.offsets)
+                nb, host = len(idx), slot["host"].numpy()
+                host[:params.nbytes] = params.view(np.uint8)
+                for f, k in enumerate(self.names):
+                    o = self._rec_bytes + f * self._src_bytes
+                    host[o:o + sources[k].nbytes] = sources[k].view(np.uint8)
+                blurs = params["blur_k"][(params["flags"] & BLUR_F) != 0]
+                max_blur = int(blurs.max()) if len(blurs) else 0
+                with torch.cuda.stream(self.copy_stream):
+                    slot["dev"].copy_(slot["host"], non_blocking=True)
+                    for f, k in enumerate(self.names):
+                        o = self._rec_bytes + f * self._src_bytes
+                        self.augmenter.launch_crop(k, self.arenas[k], slot["out"][k][:nb], slot["dev"][:self._rec_bytes],
+                                                   slot["dev"][o:o + self._src_bytes], nan_to_val, max_blur, epoch)
+                    ev = torch.cuda.Event()
+                    ev.record(self.copy_stream)
+                slot["ready"] = ev
+                filled.put((bi, nb))
+            filled.put(None)
+
+        th = threading.Thread(target=producer, daemon=True)
+        th.start()
+        try:
+            while True:
+                item = filled.get()
+                if item is None:
+                    break
+                if isinstance(item, BaseException):
+                    raise RuntimeError("CropFeeder: the feeder thread failed") from item
+                bi, nb = item
+                slot = self.slots[bi % self.depth]
+                torch.cuda.current_stream(self.device).wait_event(slot["ready"])     # device-side wait: the host does not block
+                yield self._view(slot, nb)
+                done = torch.cuda.Event()
+                done.record(torch.cuda.current_stream(self.device))
                 slot["free"] = done
                 slot["released"].set()
         finally:

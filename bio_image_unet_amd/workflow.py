@@ -69,7 +69,18 @@ def _resolve_augment(augment, dataset, device, recipe):
     """``augment`` keyword of the Trainers -> ``augment.Augmenter`` (the uint8 families), ``augment.AugmenterF32`` (recipe ``"mo2d"``),
     ``augment.AugmenterVol`` (recipe ``"mo3d"``) or None.
     On-device augmentation works on the batches of a ``DeviceFeeder``, so anything but a ``TileStore`` on a GPU is refused rather than
-    silently trained un-augmented."""
+    silently trained un-augmented.  A ``feed.ImageStore`` (whole items, recipe ``"mo2d"`` only) is always augmented: ``None`` means ``True``."""
+    from .feed import ImageStore
+    if isinstance(dataset, ImageStore):
+        # whole items (recipe "mo2d" only): every patch is a random crop rendered on the device, so None means True here
+        from .augment import AugmenterF32
+        if recipe != "mo2d" or torch.device(device).type != "cuda":
+            raise ValueError('augment: a feed.ImageStore is the data set of recipe "mo2d" (TrainerMo2d) on a GPU device')
+        if augment is None or augment is True:
+            return AugmenterF32.from_store(dataset, recipe)
+        if not isinstance(augment, AugmenterF32):
+            raise ValueError("augment: None, True or an augment.AugmenterF32 (an ImageStore cannot be trained un-augmented)")
+        return augment
     if augment is None or augment is False:
         return None
     from .augment import Augmenter, AugmenterF32, AugmenterVol
@@ -88,7 +99,13 @@ def _loaders(dataset, train_data, val_data, batch_size, device, augmenter=None):
     """The reference's loaders (``DataLoader(shuffle=False, drop_last=True, num_workers=0, pin_memory=True)``, unet/train.py:92-93)
     -- or, for a memory-mapped ``feed.TileStore``, asynchronous uint8 feeders over the same index split (same order, same
     batches; the tiles cross PCIe as bytes while the previous step computes)."""
-    from .feed import DeviceFeeder, TileStore
+    from .feed import CropFeeder, DeviceFeeder, ImageStore, TileStore
+    if isinstance(dataset, ImageStore):
+        # patches of whole items: training crops are drawn with the running epoch, validation crops with one fixed epoch key -- fully
+        # augmented but the same every epoch, as the reference's validation patches are augmented once and then fixed
+        from .augment import VALIDATION_EPOCH
+        return (CropFeeder(dataset, train_data.indices, batch_size, device, augmenter),
+                CropFeeder(dataset, val_data.indices, batch_size, device, augmenter, epoch_key=VALIDATION_EPOCH))
     if isinstance(dataset, TileStore) and torch.device(device).type == "cuda":
         return (DeviceFeeder(dataset, train_data.indices, batch_size, device, augmenter=augmenter),     # training only, never validation
                 DeviceFeeder(dataset, val_data.indices, batch_size, device))
@@ -487,7 +504,9 @@ class TrainerMo2d(_MultiHeadLoop, metaclass=_OwnKeywords):
                  load_weights: bool = False, device: Union[torch.device, str] = "auto"):
         """``TrainerMo2d(..., augment=None)`` (keyword only, not in the reference, which augments offline; taken by ``_OwnKeywords``): ``True`` or
         an ``augment.AugmenterF32`` -- the training batches of a ``feed.TileStore`` are augmented on the device, fresh every epoch
-        (``augment.py``, recipe ``"mo2d"``); validation batches never."""
+        (``augment.py``, recipe ``"mo2d"``); validation batches never.  A ``feed.ImageStore`` (``multi_output_unet.prepare``) is always
+        augmented: every patch is a random crop of a whole item rendered on the device (``feed.CropFeeder``), validation patches with one
+        fixed epoch key."""
         import random
         from .multi_output_unet.losses import MultiHeadLoss
         self.device = _pick_device(device)

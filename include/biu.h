@@ -779,6 +779,38 @@ int biu_augment_f32_cubic(const void* src, int src_is_u8, const float* coef, con
                           const biu_augf_params* params, biu_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Crop augmentation of whole items: biu_augment_f32 with the source in an arena of whole images (feed.ImageStore.to_device) instead of
+ * a batch of stored tiles.  One launch per field per batch renders dst [n, planes, th, tw] (float32) straight from the arena.
+ *
+ * arena: arena_elems elements, float32 or uint8 (arena_is_u8 != 0, widened as (float)byte / 255.0f); the items of one field one after
+ * the other, each [planes, h_i, w_i].  sources[s] names sample s's item: its element offset in THIS field's arena and its extent.
+ * params[s] is biu_augf_params unchanged; m maps an output-tile pixel (x, y) to a coordinate in the ITEM, and every index wraps in the
+ * item's own (h, w), however often a small item needs it.  Index math inside an item is 32-bit (planes h w < 2^31 - 4), the offset 64-bit.
+ * A sample whose source does not lie inside the arena (or breaks the 32-bit bound) is rendered as nan_to_val; nothing outside the arena is read.
+ *
+ * Kinds, stages, samplers and the Philox counter are biu_augment_f32's; the element of the noise counter is the pixel's index inside the
+ * output tile's field, (p th + y) tw + x.  The blur halo is more gathered item through the same map and wrap.
+ *
+ * NaN in a MASK or VECTOR item means "no label"; dst never holds NaN (nan_to_val itself must not be NaN):
+ *   MASK, nearest    : a NaN source pixel gives nan_to_val
+ *   VECTOR           : if either plane of the pair is NaN at the source pixel, both outputs are nan_to_val and no rotation is applied
+ *   MASK, bilinear   : the four taps are read with NaN replaced by 0; w_nan = the sum of the fp64 weights (1 - ax)(1 - ay), ax (1 - ay),
+ *                      (1 - ax) ay, ax ay of the NaN taps; the output is nan_to_val if w_nan >= 0.5, else the interpolated value of the
+ *                      zero-filled taps (the reference's rotate_array at order = 1: scipy rounds the rotated uint8 NaN mask half up before
+ *                      its > 0.5 test)
+ *   IMAGE            : finite by the store's contract; NaN is not special-cased
+ * Null pointers, dst overlapping the arena or the records, unaligned float or record pointers, non-positive extents, field_id >= 2^28,
+ * an output of 2^31 - 4 elements or more and a NaN nan_to_val return a status and launch nothing.  No atomics, no scratch.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct biu_augf_source {
+    uint64_t offset;          /* element offset of the item in this field's arena */
+    int32_t h, w;             /* the item's extent */
+} biu_augf_source;            /* 16 bytes */
+int biu_augment_f32_crop(const void* arena, int arena_is_u8, unsigned long long arena_elems, float* dst, int n, int planes, int th, int tw,
+                         int kind, const biu_augf_params* params, const biu_augf_source* sources, float nan_to_val, int max_blur_k,
+                         unsigned long long seed, unsigned epoch, unsigned field_id, biu_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
  * On-the-fly training augmentation of float volumes: the 3-D multi-output family (multi_output_unet3d/data.py:152-178, which the
  * reference runs offline through albumentations).  One launch per field per batch; the records are biu_augf_params unchanged.
  *

@@ -62,6 +62,10 @@ class biu_augf_source(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("h", C.c_int32), ("w", C.c_int32)]
 
 
+class biu_augv_source(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("z0", C.c_int32)]
+
+
 _P = C.c_void_p
 _A = C.POINTER(biu_act)
 _X = C.POINTER(biu_xform)
@@ -194,6 +198,7 @@ SIGNATURES = {
     "biu_augment_f32_crop": (_I, [_P, _I, C.c_ulonglong, _P, _I, _I, _I, _I, _I, _P, _P, _F, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "biu_augment_vol_f32": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "biu_augment_vol_chunk": (_I, [_I] * 8),
+    "biu_augment_vol_f32_crop": (_I, [_P, _I, C.c_ulonglong, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _F, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "biu_philox_u32": (_I, [_P, C.c_longlong, C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, C.c_uint, _P]),
     "biu_adam_step": (_I, [_I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _F, _P]),
     "biu_adam_set_hyper": (_I, [_P, _F, _F, _F, _F, _I, _F, _P]),

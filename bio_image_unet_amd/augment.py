@@ -34,6 +34,7 @@ the 3-D multi-output family's volumes a third, ``AugmenterVol`` / ``biu_augment_
 stream and the launch loop (``_AugmenterCore``) and keep their own limits and kernels (the two float classes share the record).
 ``AugmenterF32`` also draws crops out of WHOLE items (``draw_crops`` / ``crop_matrix`` / ``biu_augment_f32_crop``, for ``feed.ImageStore``):
 the same record and stream, the map going from a tile pixel into the item, NaN targets replaced by ``nan_to_val`` on the way.
+``AugmenterVol`` does the same for WHOLE volumes (``draw_crops`` / ``vol_crop_matrix`` / ``biu_augment_vol_f32_crop``, for ``feed.VolumeStore``).
 """
 from __future__ import annotations
 
@@ -164,10 +165,11 @@ class _AugmenterCore:
         pack = self._packer(int(shape[-2]), int(shape[-1]))
         return self._records(epoch, indices, lambda i: pack)
 
-    def _records(self, epoch: int, indices, pack_of) -> np.ndarray:
-        """The record stream under ``draw``: sample ``i`` is packed by ``pack_of(i)`` from its own uniforms."""
+    def _records(self, epoch: int, indices, pack_of, n_uniform: Optional[int] = None) -> np.ndarray:
+        """The record stream under ``draw``: sample ``i`` is packed by ``pack_of(i)`` from its own uniforms (``n_uniform`` of them, default the
+        class's; the generator hands out doubles one after the other, so a longer draw begins with the shorter one's numbers)."""
         idx = np.atleast_1d(np.asarray(indices, dtype=np.int64)).tolist()
-        size, n = self._rec.size, self.n_uniform
+        size, n = self._rec.size, self.n_uniform if n_uniform is None else int(n_uniform)
         buf = bytearray(len(idx) * size)
         key = (self.seed, int(epoch) & 0xFFFFFFFFFFFFFFFF)
         with self._lock:
@@ -456,6 +458,7 @@ class AugmenterF32(_AugmenterCore):
     allowed_kinds = tuple(KINDS_F32)
     store_attrs = ("gauss_noise_lims", "shot_noise_lims", "brightness_contrast", "blur_limit", "random_rotate", "scale_limit")
     src_dtypes, dst_dtype, launch_name = (torch.float32, torch.uint8), torch.float32, "augment_f32"
+    source_dtype = SOURCE_DTYPE                  # feed.CropFeeder sizes its source buffers by it
 
     def __init__(self, *, gauss_noise_lims=(0.01, 0.1), shot_noise_lims=(0.001, 0.01), brightness_contrast=(0.1, 0.1), blur_limit=(3, 5),
                  random_rotate: bool = True, scale_limit=(0, 0), seed: int = 0, kinds: Optional[Dict[str, str]] = None,
@@ -650,14 +653,69 @@ BORDERS_VOL = {"reflect": BORDER_REFLECT, "constant": BORDER_CONSTANT}
 STAGE_P_MO3D = {"shift_scale_rotate": 0.8, "intensity": 0.8, "brightness_contrast": 0.5, "blur": 0.3, "shot_noise": 0.5, "gauss_noise": 0.5}
 
 
+# ---- whole volumes (``feed.VolumeStore``, ``biu_augment_vol_f32_crop``): the map goes from an output TILE pixel into the ITEM's (h, w) plane ------
+SOURCE_VOL_DTYPE = np.dtype([("offset", "<u8"), ("d", "<i4"), ("h", "<i4"), ("w", "<i4"), ("z0", "<i4")])     # include/biu.h: biu_augv_source
+assert SOURCE_VOL_DTYPE.itemsize == 24
+
+
+def _vol_crop_matrix(angle, scale, ox, oy, h, w):
+    # the whole-plane map of ``draw``'s record, then the crop: tile pixel (x, y) is plane pixel (x + ox, y + oy)
+    m = _matrix(0, angle, scale, 0.0, 0.0, h, w)
+    return tuple(v + 0.0 for v in _after(m, (1.0, 0.0, ox, 0.0, 1.0, oy)))      # origin (0, 0): ``_matrix``'s numbers bit for bit
+
+
+def vol_crop_matrix(angle: float, scale: float, origin_xy, item_hw) -> np.ndarray:
+    """float64 ``[m0 .. m5]``: pixel (x, y) of an output tile samples a plane of the ITEM ``[h, w]`` at ``(m0 x + m1 y + m2, m3 x + m4 y + m5)``:
+    shift-scale-rotate of the whole plane about its centre (``inverse_matrix(0, angle, scale, 0, 0, h, w)``), then the crop at
+    ``origin_xy = (ox, oy)``.  Whole-pixel cases are exact integers; with origin ``(0, 0)`` the map is ``inverse_matrix``'s bit for bit."""
+    if not scale > 0:
+        raise ValueError("scale must be positive")
+    return np.array(_vol_crop_matrix(float(angle), float(scale), float(origin_xy[0]), float(origin_xy[1]), int(item_hw[0]), int(item_hw[1])))
+
+
+def _pack_vol_crop(buf, offset, index, h, w, angle, scale, origin, blur_k, shot_s, gauss_sigma, bc):
+    """``_pack_f32`` (no quarter turns, no shift) for a crop out of a whole plane ``[h, w]``: the same record and flags, ``m`` from
+    ``_vol_crop_matrix``, ``dx, dy`` the crop origin."""
+    flags = ((ROT_F if angle is not None else 0) | (SCALE_F if scale is not None else 0) | (BLUR_F if blur_k else 0)
+             | (SHOT_F if shot_s is not None else 0) | (GAUSS_F if gauss_sigma is not None else 0) | (BC_F if bc is not None else 0))
+    a = _f32(angle) if angle is not None else 0.0
+    s = _f32(scale) if scale is not None else 1.0
+    ox, oy = float(int(origin[0])), float(int(origin[1]))
+    if a != 0:
+        t = math.radians(a)
+        ct, st = math.cos(t), math.sin(t)
+    else:
+        ct, st = 1.0, 0.0
+    alpha, beta = bc if bc is not None else (1.0, 0.0)
+    _REC_F32.pack_into(buf, offset, flags, 0, blur_k, index, *_vol_crop_matrix(a, s, ox, oy, h, w), ct + 0.0, st + 0.0, alpha, beta,
+                       shot_s if shot_s is not None else 0.0, gauss_sigma if gauss_sigma is not None else 0.0, a, s, ox, oy)
+
+
+def record_vol_crop(index: int, item_hw, *, angle: Optional[float] = None, scale: Optional[float] = None, origin=(0, 0), blur_k: int = 0,
+                    shot_s: Optional[float] = None, gauss_sigma: Optional[float] = None, bc=None) -> np.ndarray:
+    """One ``biu_augf_params`` record for ``biu_augment_vol_f32_crop`` from its logical description (``record_f32``'s without quarter turns,
+    with ``origin = (ox, oy)`` the crop's first pixel in the transformed plane of an item ``item_hw``).  ``AugmenterVol.draw_crops`` builds
+    its records the same way."""
+    if blur_k and (blur_k % 2 == 0 or not 1 <= blur_k <= MAX_BLUR):
+        raise ValueError(f"blur kernel {blur_k}: odd and at most {MAX_BLUR}")
+    if shot_s is not None and not shot_s > 0:
+        raise ValueError("shot noise needs a positive scale")
+    if scale is not None and not scale > 0:
+        raise ValueError("scale must be positive")
+    buf = bytearray(_REC_F32.size)
+    _pack_vol_crop(buf, 0, int(index), int(item_hw[0]), int(item_hw[1]), angle, scale, origin, int(blur_k), shot_s, gauss_sigma, bc)
+    return np.frombuffer(buf, dtype=PARAMS_F32_DTYPE)[0]
+
+
 class AugmenterVol(_AugmenterCore):
     """Draws ``biu_augf_params`` records on the host and runs ``biu_augment_vol_f32`` on device batches of float32 or uint8 volumes
     ``[B, D, H, W]`` or ``[B, C, D, H, W]`` (the output is always float32): the 3-D multi-output family's recipe ``"mo3d"``.
 
     Limits default to the reference constructor's.  ``border``: what lies outside a plane, ``"reflect"`` (reflect-101, albumentations 1.4's
     default for ``ShiftScaleRotate`` and what this package's uint8 recipes do) or ``"constant"`` (0, albumentations 2's default).  The blur's own
-    border is always reflect-101, as ``cv2.blur``'s.  ``RandomCrop3D(dim_out)`` is the identity here: the tiles of a store already have
-    ``dim_out``, so there is nothing to crop and no offset to draw.
+    border is always reflect-101, as ``cv2.blur``'s.  On a ``feed.TileStore`` ``RandomCrop3D(dim_out)`` is the identity: its tiles already have
+    ``dim_out``, so ``draw`` has nothing to crop and no offset to draw.  On a ``feed.VolumeStore`` of whole volumes ``draw_crops`` places the crop:
+    the same thirteen uniforms behind the same gates, then ``u[13], u[14], u[15]`` for ``z0, oy, ox`` (``biu_augment_vol_f32_crop``).
 
     ``draw`` takes thirteen uniforms per sample, in this order whatever the gates say:
 
@@ -753,6 +811,77 @@ class AugmenterVol(_AugmenterCore):
                       lerp(u[12], gauss_lims) if on and u[11] < P["gauss_noise"] else None,
                       (1.0 + (2.0 * u[5] - 1.0) * bcl[1], (2.0 * u[6] - 1.0) * bcl[0]) if on and u[4] < P["brightness_contrast"] else None)
         return pack
+
+    # ---- whole volumes: crops out of a ``feed.VolumeStore`` --------------------------------------------------------------------------------
+    source_dtype, n_uniform_crop = SOURCE_VOL_DTYPE, 16
+
+    def _crop_packer(self, d, h, w, td, th, tw, z0_out):
+        """``draw_crops``' record from sixteen uniforms: ``u[0..12]`` are ``_packer``'s behind the same gates, so the logical fields equal
+        ``draw``'s; ``u[13], u[14], u[15]`` ALWAYS place ``z0, oy, ox`` -- ``RandomCrop3D`` has ``p = 1`` -- as ``min(int(u (E - t + 1)), E - t)``
+        in the item's own extent (``ShiftScaleRotate`` keeps it).  ``z0`` goes to ``z0_out[index]``: the record has no field for it."""
+        lerp = lambda u, lim: lim[0] + u * (lim[1] - lim[0])
+        P, sizes, bcl = STAGE_P_MO3D, self.blur_sizes, self.brightness_contrast
+        scale_limit, rotate_limit, shot_lims, gauss_lims = self.scale_limit, self.rotate_limit, self.shot_noise_lims, self.gauss_noise_lims
+        place = lambda u, e, t: min(int(u * (e - t + 1)), e - t)
+
+        def pack(buf, offset, index, u):
+            ssr, on = u[0] < P["shift_scale_rotate"], u[3] < P["intensity"]
+            z0_out[offset // _REC_F32.size] = place(u[13], d, td)
+            _pack_vol_crop(buf, offset, index, h, w, lerp(u[2], rotate_limit) if ssr else None, 1.0 + lerp(u[1], scale_limit) if ssr else None,
+                           (place(u[15], w, tw), place(u[14], h, th)),
+                           sizes[min(int(u[8] * len(sizes)), len(sizes) - 1)] if on and u[7] < P["blur"] else 0,
+                           lerp(u[10], shot_lims) if on and u[9] < P["shot_noise"] else None,
+                           lerp(u[12], gauss_lims) if on and u[11] < P["gauss_noise"] else None,
+                           (1.0 + (2.0 * u[5] - 1.0) * bcl[1], (2.0 * u[6] - 1.0) * bcl[0]) if on and u[4] < P["brightness_contrast"] else None)
+        return pack
+
+    def draw_crops(self, epoch: int, patch_indices, store, offsets: Optional[Dict[str, np.ndarray]] = None):
+        """Records and sources for the patches ``patch_indices`` of a ``feed.VolumeStore`` in epoch ``epoch``: a pure function of
+        ``(seed, epoch, patch index)`` -- Philox key ``(seed, epoch)``, counter = the patch index, ``draw``'s stream, sixteen uniforms of
+        which the first thirteen are ``draw``'s.  Returns ``(records [n], {field: sources [n]})``; a source is ``(element offset of the patch's
+        item in the field's arena, d, h, w, z0)``.  ``offsets``: the per-item offsets ``store.to_device`` returned (default: the store's own)."""
+        idx = np.atleast_1d(np.asarray(patch_indices, dtype=np.int64))
+        items = np.atleast_1d(store.locate(idx))
+        td, th, tw = (int(v) for v in store.dim_out)
+        sizes, packers, item_of = store.sizes, {}, dict(zip(idx.tolist(), items.tolist()))
+        z0 = np.zeros(len(idx), dtype=np.int32)
+
+        def pack_of(j):
+            dhw = tuple(int(v) for v in sizes[item_of[j]])
+            if dhw not in packers:
+                packers[dhw] = self._crop_packer(*dhw, td, th, tw, z0)
+            return packers[dhw]
+
+        records = self._records(epoch, idx, pack_of, self.n_uniform_crop)
+        offsets = offsets if offsets is not None else store.offsets
+        sources = {}
+        for name in store.fields:
+            src = np.empty(len(idx), dtype=SOURCE_VOL_DTYPE)
+            src["offset"], src["d"], src["h"], src["w"], src["z0"] = np.asarray(offsets[name])[items], sizes[items, 0], sizes[items, 1], sizes[items, 2], z0
+            sources[name] = src
+        return records, sources
+
+    def launch_crop(self, name, arena, dst, params_dev, sources_dev, nan_to_val, max_blur, epoch):
+        """One ``biu_augment_vol_f32_crop`` launch on the current stream: field ``name`` of ``dst.shape[0]`` patches ``dst [n, C, td, th, tw]`` out
+        of the 1-D device tensor ``arena``; ``params_dev`` / ``sources_dev``: the records and this field's sources on the device, as bytes."""
+        from ._lib import check, lib
+        kind = KINDS_F32[self.kind(name)]
+        if arena.dtype not in self.src_dtypes or not arena.is_cuda or arena.dim() != 1 or not arena.is_contiguous():
+            raise ValueError(f'field "{name}": the arena is a contiguous 1-D {_names(self.src_dtypes)} device tensor')
+        if dst.dtype != torch.float32 or dst.dim() != 5 or not dst.is_contiguous() or dst.device != arena.device:
+            raise ValueError(f'field "{name}": the output is a contiguous float32 tensor [n, C, td, th, tw] on the arena\'s device')
+        n, channels, td, th, tw = dst.shape
+        if kind == KIND_VECTOR and channels % 2:
+            raise ValueError(f'field "{name}": a vector field holds (cos, sin) channel pairs, got {channels} channel(s)')
+        if params_dev.numel() * params_dev.element_size() < n * PARAMS_F32_DTYPE.itemsize or \
+                sources_dev.numel() * sources_dev.element_size() < n * SOURCE_VOL_DTYPE.itemsize:
+            raise ValueError(f"{n} patches need {n} parameter records and {n} sources")
+        check(lib.biu_augment_vol_f32_crop(C.c_void_p(arena.data_ptr()), int(arena.dtype == torch.uint8), arena.numel(), C.c_void_p(dst.data_ptr()),
+                                           n, channels, td, th, tw, kind, BORDERS_VOL[self.border], C.c_void_p(params_dev.data_ptr()),
+                                           C.c_void_p(sources_dev.data_ptr()), float(nan_to_val), max_blur if kind == KIND_IMAGE else 0, self.seed,
+                                           int(epoch) & 0xFFFFFFFF, field_id(name), C.c_void_p(torch.cuda.current_stream(arena.device).cuda_stream)),
+              "augment_vol_f32_crop")
+        return dst
 
     def _launch(self, lib, name, t, dst, channels, params_dev, max_blur, epoch, stream):
         kind = KINDS_F32[self.kind(name)]

@@ -22,18 +22,20 @@
 
 #include "biu_common.h"
 #include "biu_augment_stages.h"
+#include "biu_augment_vol_plan.h"
 
 namespace {
+using biu_augment_vol_plan::Plan;
+using biu_augment_vol_plan::plan_of;
+using biu_augment_vol_plan::TILE;
+using biu_augment_vol_plan::TPB;
 using biu_augment_stages::clip01;
 using biu_augment_stages::shot_gauss;
 using biu_augment_stages::source_of;
 
-constexpr int TPB = 256;
-constexpr int TILE = 64;                        // the tile kernel's output tile is TILE x TILE
 constexpr int RMAX = BIU_AUG_MAX_BLUR / 2;      // 7
 constexpr int IN_MAX = TILE + 2 * RMAX;         // 78 rows / columns of BC(gather)
 constexpr int IN_PITCH = 80;
-constexpr int MAX_CHUNK = 16;                   // planes a lane walks with one set of taps, at most
 
 struct Launch {
     const void* src;
@@ -257,28 +259,8 @@ void launch_point(const Launch& L, bool rows, hipStream_t st) {
     else hipLaunchKernelGGL((k_augv_point<KIND, 1>), dim3(grid), dim3(TPB), 0, st, L, gpp, total);
 }
 
-// How a launch is cut, decided in one place for the launch and for biu_augment_vol_chunk.  Planes per lane (per block of the tile kernel): as
-// many as MAX_CHUNK, halved while the launch would have fewer than 2048 blocks, 8 for each of the 256 compute units.  That figure is a guess
-// at what hides the tail of the last wave of blocks; it has not been measured against other values.
-struct Plan {
-    bool tile, rows;
-    int units, tx, ty, chunk, nchunks;
-};
-Plan plan_of(int n, int channels, int depth, int h, int w, int kind, int max_blur_k, bool aligned16) {
-    Plan p;
-    p.tile = kind == BIU_AUGF_IMAGE && max_blur_k > 1;
-    p.rows = w % 4 == 0 && aligned16;
-    p.units = kind == BIU_AUGF_VECTOR ? channels / 2 * depth : channels * depth;
-    p.tx = (w + TILE - 1) / TILE;
-    p.ty = (h + TILE - 1) / TILE;
-    const i64 work = p.tile ? (i64)n * p.tx * p.ty : (i64)n * (p.rows ? h * (w / 4) : h * w);      // blocks, or lanes, per chunk
-    const i64 want = p.tile ? 2048 : (i64)2048 * TPB;
-    int c = MAX_CHUNK;
-    while (c > 1 && work * ((p.units + c - 1) / c) < want) c >>= 1;
-    p.chunk = p.units < c ? p.units : c;
-    p.nchunks = (p.units + p.chunk - 1) / p.chunk;
-    return p;
-}
+// How a launch is cut is decided in one place for the launch, for biu_augment_vol_chunk and for biu_augment_vol_f32_crop:
+// biu_augment_vol_plan.h.
 bool dims_ok(int n, int channels, int depth, int h, int w, int kind, int max_blur_k) {
     return n > 0 && channels > 0 && depth > 0 && h > 0 && w > 0 && (double)n * channels * depth * h * w < 2147483648.0 &&
            (kind == BIU_AUGF_IMAGE || kind == BIU_AUGF_MASK || (kind == BIU_AUGF_VECTOR && channels % 2 == 0)) && max_blur_k >= 0 &&

@@ -21,6 +21,7 @@ Contract (what the tests hold it to; every comparison is an equality)
 
 The 2-D multi-output family has a fourth entry point at the end of this file, ``prepare_mo2d``: its ``DataProcess`` keeps every image whole
 and crops at random, so the result is a ``feed.ImageStore`` of whole normalised images and float targets (NaN kept), not a store of tiles.
+The 3-D multi-output family's ``prepare_mo3d`` does the same for whole volumes (``feed.VolumeStore``).
 """
 from __future__ import annotations
 
@@ -31,7 +32,7 @@ import numpy as np
 import torch
 
 from ._lib import check, lib, ptr as _ptr, stream as _stream
-from .feed import ImageStore, TileStore
+from .feed import ImageStore, TileStore, VolumeStore
 from .preprocess import DeviceFrontEnd
 from .utils import get_device
 
@@ -429,6 +430,91 @@ def prepare_mo2d(images: Sequence, targets, path: str, dim_out=(256, 256), in_ch
         fe.normalise("single", clip_threshold)
         t = fe.tiles([(0, 0, 0, 0)], (c, h, w), out="uint8" if image_dtype == "u8" else "float32")
         store.put(i, "image", t.batch(0, 1)[0].cpu().numpy())
+        for name, v in item.items():
+            store.put(i, name, v)
+    store.flush()
+    return store
+
+
+# ---- the 3-D multi-output family: whole volumes, NaN targets ------------------------------------------------------------------------------------
+def _mo3d_items(volumes, targets, in_channels, dim_out):
+    """The host half of ``prepare_mo3d``: every item as ``(volume [C, D, H, W], {name: float32 [channels, D, H, W]})`` plus the channels and
+    the squeeze flag of every field.  Needs no device, so every ``ValueError`` of ``prepare_mo3d`` is raised before one is asked for."""
+    if len(volumes) == 0:
+        raise ValueError("no volumes")
+    if not targets:
+        raise ValueError("no targets")
+    for name, seq in targets.items():
+        if name == "volume":
+            raise ValueError('a target cannot be named "volume"')
+        if len(seq) != len(volumes):
+            raise ValueError(f'target "{name}": {len(seq)} items for {len(volumes)} volumes')
+    items, channels, squeeze = [], {}, {}
+    for i, vol in enumerate(volumes):
+        vol = _load(vol)
+        unit = vol[None] if vol.ndim == 3 else vol
+        if unit.ndim != 4 or unit.shape[0] != in_channels:
+            raise ValueError(f"volume {i}: shape {vol.shape} is not [D, H, W] or [{in_channels}, D, H, W] (in_channels = {in_channels})")
+        if any(e < t for e, t in zip(unit.shape[1:], dim_out)):
+            raise ValueError(f"item {i}: {tuple(unit.shape[1:])} is smaller than dim_out {tuple(dim_out)}; a crop cannot be larger than its volume")
+        item = {}
+        for name, seq in targets.items():
+            t = _load(seq[i])
+            if t.dtype.kind not in "buif":
+                raise ValueError(f'target "{name}" of item {i}: bool or a real dtype, got {t.dtype}')
+            if t.shape[-3:] != unit.shape[1:] or t.ndim not in (3, 4) or (name == "orientation" and t.ndim != 3):
+                raise ValueError(f"Item: {i}. Shape mismatch: {name} has shape {t.shape} but expected {vol.shape}")
+            t = t.astype(np.float32)
+            if name == "orientation":                        # an angle volume becomes the rotated pair; NaN in both where the angle is NaN
+                t, sq = np.stack([np.cos(t), np.sin(t)]), False
+            else:
+                t, sq = (t[None], True) if t.ndim == 3 else (t, False)
+            if channels.setdefault(name, t.shape[0]) != t.shape[0] or squeeze.setdefault(name, sq) != sq:
+                raise ValueError(f'target "{name}" of item {i}: {t.shape[0]} channel(s), the items before it have {channels[name]}')
+            item[name] = t
+        items.append((unit, item))
+    return items, channels, squeeze
+
+
+def prepare_mo3d(volumes: Sequence, targets, path: str, dim_out=(128, 128, 128), in_channels: int = 1, nan_to_val: float = 0,
+                 clip_threshold=(0., 99.99), aug_factor: int = 10, scale_limit=(-0.75, 0), rotate_limit=(0, 360), gauss_noise_lims=(0.01, 0.1),
+                 shot_noise_lims=(0.005, 0.01), brightness_contrast=(0.1, 0.1), blur_limit=(3, 7), volume_dtype: str = "f32",
+                 device="auto") -> VolumeStore:
+    """``bio_image_unet.multi_output_unet3d.DataProcess`` up to its augmentation (``multi_output_unet3d/data.py:57-150``) from arrays, into a
+    ``feed.VolumeStore`` of WHOLE volumes: ``TrainerMo3d(store, ...)`` then renders ``aug_factor`` fresh random crops per volume and epoch on
+    the device (shift-scale-rotate of the whole volume, then ``RandomCrop3D(dim_out)``).  The keywords and defaults are the reference
+    ``DataProcess``'s; its ``add_tile``, ``val_split``, ``random_rotate`` and ``create`` do not apply (nothing is tiled or written as TIFF,
+    the Trainer splits patch indices, and the rotation is ``rotate_limit``'s).
+
+    ``volumes``: ``[D, H, W]`` or ``[C, D, H, W]`` of any dtype the device front end uploads, each normalised as one unit by
+    ``DeviceFrontEnd.normalise('single', clip_threshold)`` and read back whole as the field ``volume`` in float32 (``volume_dtype="u8"``: as
+    bytes, a quarter of the arena).  ``targets``: ``{name: sequence}`` of ``[D, H, W]`` or ``[C, D, H, W]`` arrays, bool or real, stored as
+    float32 with NaN ("no label here") kept; the target named ``orientation`` is an angle volume ``[D, H, W]`` and is stored as the two
+    channels ``(cos, sin)``, NaN in both where the angle is NaN."""
+    if volume_dtype not in ("f32", "u8"):
+        raise ValueError(f'volume_dtype "{volume_dtype}": "f32" or "u8"')
+    if len(dim_out) != 3 or min(dim_out) < 1:
+        raise ValueError(f"dim_out {dim_out}: (depth, height, width) of a patch")
+    if int(aug_factor) != aug_factor or aug_factor < 1:
+        raise ValueError("aug_factor: a whole number of patches per volume, at least 1")
+    if not np.isfinite(nan_to_val):
+        raise ValueError("nan_to_val must be finite")
+    dim_out = tuple(int(d) for d in dim_out)
+    items, channels, squeeze = _mo3d_items(volumes, targets, int(in_channels), dim_out)
+    device = _device(device)
+    fields = {"volume": int(in_channels), **channels}
+    store = VolumeStore.create(path, [u.shape[1:] for u, _ in items], fields,
+                               {**_attrs(dim_out, clip_threshold, scale_limit=scale_limit, rotate_limit=rotate_limit, gauss_noise_lims=gauss_noise_lims,
+                                         shot_noise_lims=shot_noise_lims, brightness_contrast=brightness_contrast, blur_limit=blur_limit),
+                                "aug_factor": int(aug_factor), "nan_to_val": float(nan_to_val)},
+                               {"volume": volume_dtype, **{k: "f32" for k in channels}}, {"volume": in_channels == 1, **squeeze})
+    for i, (unit, item) in enumerate(items):
+        c, d, h, w = unit.shape
+        planes = np.ascontiguousarray(unit).reshape(c * d, h, w)     # one unit for the percentiles: every channel and plane of the volume
+        fe = DeviceFrontEnd(planes, device, depth=c * d)
+        fe.normalise("single", clip_threshold)
+        t = fe.tiles([(0, 0, 0, 0)], (c * d, h, w), out="uint8" if volume_dtype == "u8" else "float32")
+        store.put(i, "volume", t.batch(0, 1)[0].cpu().numpy().reshape(c, d, h, w))
         for name, v in item.items():
             store.put(i, name, v)
     store.flush()

@@ -27,7 +27,8 @@ The 2-D multi-output family's items are float32 (``multi_output_unet/data.py:318
 The reference's ``DataProcess`` of that family keeps every image WHOLE and crops at random out of the rotated image, with NaN in a target
 meaning "no label here" (``multi_output_unet/data.py:140-311``).  ``ImageStore`` holds such items -- whole, of differing size, NaN kept -- and
 ``CropFeeder`` renders every training patch from them on the device (``biu_augment_f32_crop``); ``dataprep.prepare_mo2d`` writes one from raw
-arrays.  Both are at the end of this file.
+arrays.  ``VolumeStore`` is the same for the 3-D multi-output family (``multi_output_unet3d/data.py:152-230``): whole volumes, the same feeder,
+``biu_augment_vol_f32_crop``, ``dataprep.prepare_mo3d``.  All three are at the end of this file.
 """
 from __future__ import annotations
 
@@ -294,6 +295,7 @@ class ImageStore(torch.utils.data.Dataset):
     of PATCHES per epoch, the reference's count per item (``patches_of``) summed; ``locate(j)`` maps a patch index to its item.  Patches are
     rendered on the device only (``CropFeeder`` / ``biu_augment_f32_crop``): ``__getitem__`` raises.  ``fields`` is the shape of a rendered
     patch per field, as ``TileStore.fields`` is the shape of a tile."""
+    recipe = "mo2d"                              # the augmenter that draws its crops: augment.AugmenterF32
 
     def __init__(self, path: str, mode: str = "r"):
         with open(path + ".json") as f:
@@ -393,17 +395,21 @@ class ImageStore(torch.utils.data.Dataset):
 
     def to_device(self, device):
         """Upload every field once as ONE device tensor (the arena).  Returns ``(arenas {field: 1-D tensor}, offsets {field: int64 [items]},
-        H [items], W [items])``; the offsets count elements of the field's own arena.  A store that does not fit raises ``RuntimeError``.
+        H [items], W [items])`` (a ``VolumeStore``: ``D, H, W``); the offsets count elements of the field's own arena.  A store that does not fit raises ``RuntimeError``.
         The upload happens once per device and is kept (a ``put`` after it is not seen there)."""
+        extents = (self.sizes[:, a].copy() for a in range(self.sizes.shape[1]))       # H, W (a VolumeStore: D, H, W)
+        return (self._arenas_on(device), {k: v.astype(np.int64) for k, v in self.offsets.items()}, *extents)
+
+    def _arenas_on(self, device):
         device = torch.device(device)
         if device.type != "cuda":
-            raise RuntimeError(f"ImageStore.to_device uploads to a GPU; got device '{device}'")
+            raise RuntimeError(f"{type(self).__name__}.to_device uploads to a GPU; got device '{device}'")
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         cache = self.__dict__.setdefault("_arenas", {})      # the training and the validation feeder of a Trainer share one upload
         if device not in cache:
             cache[device] = self._upload(device)
-        return cache[device], {k: v.astype(np.int64) for k, v in self.offsets.items()}, self.sizes[:, 0].copy(), self.sizes[:, 1].copy()
+        return cache[device]
 
     def _upload(self, device):
         arenas = {}
@@ -413,16 +419,125 @@ class ImageStore(torch.utils.data.Dataset):
         except torch.cuda.OutOfMemoryError as e:
             need = sum(self.elements[k] * (1 if self.dtypes[k] == "u8" else 4) for k in self.maps)
             arenas.clear()
-            raise RuntimeError(f"ImageStore {self.path}: the store ({need} bytes) does not fit in the HBM of {device}; a streamed store is not "
+            raise RuntimeError(f"{type(self).__name__} {self.path}: the store ({need} bytes) does not fit in the HBM of {device}; a streamed store is not "
                                f"supported") from e
         return arenas
 
 
+_VOLUME_MAGIC = "biu-volumestore-1"
+
+
+class VolumeStore(ImageStore):
+    """``ImageStore`` for whole VOLUMES of differing size ``(D_i, H_i, W_i)``: the same file layout (one flat file per field, the items one
+    after the other, each ``[channels, D_i, H_i, W_i]``; header magic ``biu-volumestore-1``) and the same API.  ``attrs`` holds a 3-tuple
+    ``dim_out``, an integer ``aug_factor``, ``nan_to_val``, ``clip_threshold`` and the limits ``AugmenterVol.store_attrs`` lists.
+
+    Float fields may hold NaN ("no label here"), written and read back bit for bit; the field ``volume`` may not.  Its length is
+    ``n_items * aug_factor`` -- the reference draws ``aug_factor`` patches per volume (``multi_output_unet3d/data.py:192``) -- and
+    ``locate(j) = j // aug_factor``.  Patches are rendered on the device only (``CropFeeder`` / ``biu_augment_vol_f32_crop``): ``__getitem__``
+    raises.  ``planes`` is the number of channels per field, ``fields`` the shape of a rendered patch."""
+    recipe = "mo3d"                              # augment.AugmenterVol
+
+    def __init__(self, path: str, mode: str = "r"):
+        with open(path + ".json") as f:
+            hdr = json.load(f)
+        if hdr.get("magic") != _VOLUME_MAGIC:
+            raise ValueError(f"{path}.json is not a volume store header")
+        self.path, self.attrs = path, hdr.get("attrs", {})
+        self.sizes = np.asarray(hdr["items"], dtype=np.int64).reshape(-1, 3)
+        self.n_items = len(self.sizes)
+        self.planes = {k: int(v["channels"]) for k, v in hdr["fields"].items()}
+        self.dtypes = {k: v["dtype"] for k, v in hdr["fields"].items()}
+        self.squeeze = {k: bool(v.get("squeeze", False)) for k, v in hdr["fields"].items()}
+        self.dim_out = tuple(int(d) for d in self.attrs["dim_out"])
+        self.aug_factor = int(self.attrs.get("aug_factor", 10))
+        self.nan_to_val = float(self.attrs.get("nan_to_val", 0.0))
+        for k, v in self.attrs.items():
+            if not hasattr(self, k):
+                setattr(self, k, v)
+        self.fields = {k: self.dim_out if self.squeeze[k] else (c,) + self.dim_out for k, c in self.planes.items()}
+        start = np.concatenate([[0], np.cumsum(self.sizes.prod(axis=1))])
+        self.offsets = {k: start[:-1] * c for k, c in self.planes.items()}          # element offset of every item in its field's file
+        self.elements = {k: int(start[-1]) * c for k, c in self.planes.items()}
+        self.maps = {k: np.memmap(f"{path}.{k}.{self.dtypes[k]}", dtype=_NP_DTYPE[self.dtypes[k]], mode=mode, shape=(self.elements[k],))
+                     for k in self.planes}
+
+    @classmethod
+    def create(cls, path: str, sizes, fields: Dict[str, int], attrs: dict, dtypes=None, squeeze: Optional[Dict[str, bool]] = None) -> "VolumeStore":
+        """An empty store for items of the extents ``sizes`` ``[(D_i, H_i, W_i)]``; ``fields``: channels per field; ``attrs`` needs ``dim_out``
+        (3 extents).  ``squeeze``: fields whose patches are handed out without the channel axis (one channel, given as ``[D, H, W]``).  An
+        item smaller than ``dim_out`` in any axis is refused (``RandomCrop3D`` would raise there)."""
+        sizes = [tuple(int(v) for v in sz) for sz in sizes]
+        if not sizes or not fields or any(len(sz) != 3 or min(sz) < 1 for sz in sizes) or any(int(c) < 1 for c in fields.values()):
+            raise ValueError("a volume store needs items (D, H, W) and fields of positive extent")
+        if "dim_out" not in (attrs or {}) or len(attrs["dim_out"]) != 3 or min(attrs["dim_out"]) < 1:
+            raise ValueError("attrs needs dim_out = (depth, height, width) of a patch")
+        if int(attrs.get("aug_factor", 10)) != attrs.get("aug_factor", 10) or int(attrs.get("aug_factor", 10)) < 1:
+            raise ValueError("aug_factor: a whole number of patches per volume, at least 1")
+        dim_out = tuple(int(d) for d in attrs["dim_out"])
+        for i, sz in enumerate(sizes):
+            if any(e < t for e, t in zip(sz, dim_out)):
+                raise ValueError(f"item {i}: {sz} is smaller than dim_out {dim_out}; a crop cannot be larger than its volume")
+            for name, c in fields.items():
+                if int(c) * sz[0] * sz[1] * sz[2] >= _ITEM_LIMIT:
+                    raise ValueError(f'field "{name}" of item {i}: {c} x {sz[0]} x {sz[1]} x {sz[2]} elements; one item holds fewer than 2^31 - 4 per field')
+        dtypes = _field_dtypes(fields, dtypes if dtypes is not None else "f32")
+        squeeze = {k: bool((squeeze or {}).get(k, False)) and int(fields[k]) == 1 for k in fields}
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        total = sum(d * h * w for d, h, w in sizes)
+        for k, c in fields.items():
+            np.memmap(f"{path}.{k}.{dtypes[k]}", dtype=_NP_DTYPE[dtypes[k]], mode="w+", shape=(total * int(c),)).flush()
+        plain = lambda v: [plain(e) for e in v] if isinstance(v, (tuple, list)) else v
+        hdr = {"magic": _VOLUME_MAGIC, "items": [list(sz) for sz in sizes], "attrs": {k: plain(v) for k, v in attrs.items()},
+               "fields": {k: {"channels": int(c), "dtype": dtypes[k], "squeeze": squeeze[k]} for k, c in fields.items()}}
+        with open(path + ".json", "w") as f:
+            json.dump(hdr, f)
+        return cls(path, mode="r+")
+
+    def item(self, i: int, name: str) -> np.ndarray:
+        """Item ``i`` of field ``name`` as a view ``[channels, D_i, H_i, W_i]`` of the map."""
+        d, h, w = (int(v) for v in self.sizes[i])
+        o, c = int(self.offsets[name][i]), self.planes[name]
+        return self.maps[name][o:o + c * d * h * w].reshape(c, d, h, w)
+
+    def put(self, i: int, name: str, value) -> None:
+        """Write item ``i`` of field ``name``: float fields as given (NaN kept, bit for bit), except that the field ``volume`` is refused where
+        it is not finite; uint8 fields take bytes, or floats in [0, 1] as multiples of 1/255."""
+        dst = self.item(i, name)
+        v = np.asarray(value)
+        v = v[None] if v.ndim == 3 else v
+        if v.shape != dst.shape:
+            raise ValueError(f'field "{name}" of item {i}: expected {dst.shape}, got {v.shape}')
+        if name == "volume" and v.dtype.kind == "f" and not np.isfinite(v).all():
+            raise ValueError(f'field "volume" of item {i} holds non-finite values: NaN means "no label" and is for targets only')
+        if self.dtypes[name] == "f32":
+            dst[...] = v.astype(np.float32, copy=False)
+        elif v.dtype == np.uint8:
+            dst[...] = v
+        else:
+            dst[...] = np.clip(np.rint(v.astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
+
+    def __len__(self):
+        return self.n_items * self.aug_factor
+
+    def locate(self, j):
+        """Item of patch ``j`` (an index or an array of indices): ``j // aug_factor``."""
+        idx = np.asarray(j, dtype=np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= len(self)):
+            raise IndexError(f"patch index outside 0 .. {len(self) - 1}")
+        res = idx // self.aug_factor
+        return int(res) if res.ndim == 0 else res
+
+    def __getitem__(self, j):
+        raise RuntimeError("VolumeStore: patches are rendered on the device only (feed.CropFeeder, biu_augment_vol_f32_crop); there is no CPU path")
+
+
 class CropFeeder:
-    """Iterable over device batches of random crops out of an ``ImageStore`` (one epoch per ``iter()``), ``depth`` batches in flight: what the
-    Trainer iterates when handed such a store.  The store is uploaded once (``ImageStore.to_device``); per batch a background thread draws
-    the records and sources (``AugmenterF32.draw_crops``), uploads the two small buffers on a copy stream and launches one
-    ``biu_augment_f32_crop`` per field into rotating output buffers in front of a ``ready`` event -- ``DeviceFeeder``'s slot and event hand-over,
+    """Iterable over device batches of random crops out of an ``ImageStore`` or a ``VolumeStore`` (one epoch per ``iter()``), ``depth`` batches
+    in flight: what the Trainer iterates when handed such a store.  The store is uploaded once (``to_device``); per batch a background thread
+    draws the records and sources (``AugmenterF32.draw_crops`` / ``AugmenterVol.draw_crops``), uploads the two small buffers on a copy stream
+    and launches one ``biu_augment_f32_crop`` / ``biu_augment_vol_f32_crop`` per field (the augmenter's ``launch_crop``) into rotating output
+    buffers in front of a ``ready`` event -- ``DeviceFeeder``'s slot and event hand-over,
     a failure of the feeder thread surfaces in the consumer.  No tile bytes cross PCIe after the upload.
 
     ``epoch_key``: ``None`` -- the epoch (``draw_crops``' second argument) advances per ``iter()``; a number -- every ``iter()`` uses it, so the
@@ -430,7 +545,6 @@ class CropFeeder:
 
     def __init__(self, store: ImageStore, patch_indices: Sequence[int], batch_size: int, device, augmenter, epoch_key: Optional[int] = None,
                  depth: int = 3, drop_last: bool = True):
-        from .augment import PARAMS_F32_DTYPE, SOURCE_DTYPE
         self.store, self.indices, self.batch_size = store, [int(i) for i in patch_indices], int(batch_size)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -438,20 +552,23 @@ class CropFeeder:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         if augmenter is None or not hasattr(augmenter, "draw_crops"):
-            raise ValueError("CropFeeder needs an augment.AugmenterF32: an ImageStore cannot be read un-augmented")
+            raise ValueError("CropFeeder needs an augment.AugmenterF32 (ImageStore) or augment.AugmenterVol (VolumeStore): such a store cannot "
+                             "be read un-augmented")
+        if augmenter.recipe != store.recipe:
+            raise ValueError(f'{type(augmenter).__name__} (recipe "{augmenter.recipe}") does not draw crops out of a {type(store).__name__}')
         if getattr(augmenter, "target_interp", "linear") == "cubic":
             raise NotImplementedError('target_interp="cubic" on an ImageStore: the spline coefficients and the clip range of a whole item depend '
                                       'on the item alone and belong computed once at upload, which is not implemented; use "linear"')
         self.augmenter, self.epoch_key, self.epoch = augmenter, epoch_key, 0
         self.drop_last, self.depth = drop_last, max(2, depth)
         self.copy_stream = torch.cuda.Stream(device=self.device)
-        self.arenas, self.offsets, _, _ = store.to_device(self.device)
+        self.arenas, self.offsets = store.to_device(self.device)[:2]
         self.names = list(store.fields)
-        th, tw = store.dim_out
-        rec, src = PARAMS_F32_DTYPE.itemsize, SOURCE_DTYPE.itemsize
+        # what is store-specific: the patch extent (2 or 3 axes) and the size of a source record; draw_crops and launch_crop are the augmenter's
+        rec, src = augmenter.params_dtype.itemsize, augmenter.source_dtype.itemsize
         self._rec_bytes, self._src_bytes = batch_size * rec, batch_size * src
         small = self._rec_bytes + len(self.names) * self._src_bytes                  # records, then one block of sources per field
-        self.slots = [{"out": {k: torch.empty((batch_size, store.planes[k], th, tw), dtype=torch.float32, device=self.device) for k in self.names},
+        self.slots = [{"out": {k: torch.empty((batch_size, store.planes[k], *store.dim_out), dtype=torch.float32, device=self.device) for k in self.names},
                        "host": torch.empty(small, dtype=torch.uint8).pin_memory(),
                        "dev": torch.empty(small, dtype=torch.uint8, device=self.device),
                        "ready": None, "free": None, "released": threading.Event()} for _ in range(self.depth)]
@@ -464,7 +581,7 @@ class CropFeeder:
         return {k: (v[:nb, 0] if self.store.squeeze[k] else v[:nb]) for k, v in slot["out"].items()}
 
     def __iter__(self):
-        from .augment import BLUR_F
+        blur_flag = self.augmenter.blur_flag
         batches = [self.indices[i:i + self.batch_size] for i in range(0, len(self.indices), self.batch_size)]
         if self.drop_last:
             batches = [b for b in batches if len(b) == self.batch_size]
@@ -499,7 +616,7 @@ class CropFeeder:
                 for f, k in enumerate(self.names):
                     o = self._rec_bytes + f * self._src_bytes
                     host[o:o + sources[k].nbytes] = sources[k].view(np.uint8)
-                blurs = params["blur_k"][(params["flags"] & BLUR_F) != 0]
+                blurs = params["blur_k"][(params["flags"] & blur_flag) != 0]
                 max_blur = int(blurs.max()) if len(blurs) else 0
                 with torch.cuda.stream(self.copy_stream):
                     slot["dev"].copy_(slot["host"], non_blocking=True)

@@ -69,17 +69,20 @@ def _resolve_augment(augment, dataset, device, recipe):
     """``augment`` keyword of the Trainers -> ``augment.Augmenter`` (the uint8 families), ``augment.AugmenterF32`` (recipe ``"mo2d"``),
     ``augment.AugmenterVol`` (recipe ``"mo3d"``) or None.
     On-device augmentation works on the batches of a ``DeviceFeeder``, so anything but a ``TileStore`` on a GPU is refused rather than
-    silently trained un-augmented.  A ``feed.ImageStore`` (whole items, recipe ``"mo2d"`` only) is always augmented: ``None`` means ``True``."""
+    silently trained un-augmented.  A ``feed.ImageStore`` (whole items, recipe ``"mo2d"`` only) or ``feed.VolumeStore`` (whole volumes, recipe
+    ``"mo3d"`` only) is always augmented: ``None`` means ``True``."""
     from .feed import ImageStore
     if isinstance(dataset, ImageStore):
-        # whole items (recipe "mo2d" only): every patch is a random crop rendered on the device, so None means True here
-        from .augment import AugmenterF32
-        if recipe != "mo2d" or torch.device(device).type != "cuda":
-            raise ValueError('augment: a feed.ImageStore is the data set of recipe "mo2d" (TrainerMo2d) on a GPU device')
+        # whole items: every patch is a random crop rendered on the device, so None means True here
+        from .augment import AugmenterF32, AugmenterVol
+        cls, store = {"mo2d": AugmenterF32, "mo3d": AugmenterVol}[dataset.recipe], type(dataset).__name__
+        if recipe != dataset.recipe or torch.device(device).type != "cuda":
+            raise ValueError(f'augment: a feed.{store} is the data set of recipe "{dataset.recipe}" '
+                             f'({"TrainerMo2d" if dataset.recipe == "mo2d" else "TrainerMo3d"}) on a GPU device')
         if augment is None or augment is True:
-            return AugmenterF32.from_store(dataset, recipe)
-        if not isinstance(augment, AugmenterF32):
-            raise ValueError("augment: None, True or an augment.AugmenterF32 (an ImageStore cannot be trained un-augmented)")
+            return cls.from_store(dataset, recipe)
+        if not isinstance(augment, cls):
+            raise ValueError(f"augment: None, True or an augment.{cls.__name__} (such a store cannot be trained un-augmented)")
         return augment
     if augment is None or augment is False:
         return None
@@ -101,8 +104,9 @@ def _loaders(dataset, train_data, val_data, batch_size, device, augmenter=None):
     batches; the tiles cross PCIe as bytes while the previous step computes)."""
     from .feed import CropFeeder, DeviceFeeder, ImageStore, TileStore
     if isinstance(dataset, ImageStore):
-        # patches of whole items: training crops are drawn with the running epoch, validation crops with one fixed epoch key -- fully
-        # augmented but the same every epoch, as the reference's validation patches are augmented once and then fixed
+        # patches of whole items (ImageStore, or its 3-D subclass VolumeStore): training crops are drawn with the running epoch, validation
+        # crops with one fixed epoch key -- fully augmented but the same every epoch, as the reference's validation patches are augmented
+        # once and then fixed
         from .augment import VALIDATION_EPOCH
         return (CropFeeder(dataset, train_data.indices, batch_size, device, augmenter),
                 CropFeeder(dataset, val_data.indices, batch_size, device, augmenter, epoch_key=VALIDATION_EPOCH))
@@ -415,7 +419,9 @@ class TrainerMo3d(_MultiHeadLoop):
                  save_iter=False, load_weights=False, loss_function="BCEDice", loss_params=(0.5, 0.5), time_loss_weight=0.1,
                  device: Union[torch.device, str] = "auto", fp32_products: Optional[str] = None, augment=None):
         """``augment`` (not in the reference, which augments offline): ``True`` or an ``augment.AugmenterVol`` -- the training batches of a
-        ``feed.TileStore`` are augmented on the device, fresh every epoch (``augment.py``, recipe ``"mo3d"``); validation batches never."""
+        ``feed.TileStore`` are augmented on the device, fresh every epoch (``augment.py``, recipe ``"mo3d"``); validation batches never.
+        A ``feed.VolumeStore`` (``multi_output_unet3d.prepare``) is always augmented: every patch is a random crop of a whole volume
+        rendered on the device (``feed.CropFeeder``), validation patches with one fixed epoch key; ``augment=False`` is refused."""
         _set_fp32_products(fp32_products, three_d=True)             # see Trainer3D
         self.device = _pick_device(device)
         augmenter = _resolve_augment(augment, dataset, self.device, "mo3d")

@@ -844,6 +844,55 @@ int biu_augment_vol_f32(const void* src, int src_is_u8, float* dst, int n, int c
 int biu_augment_vol_chunk(int n, int channels, int depth, int h, int w, int kind, int max_blur_k, int dst_aligned16);
 
 /* ------------------------------------------------------------------------------------------------
+ * Crop augmentation of whole volumes: biu_augment_vol_f32 with the source in an arena of whole volumes (feed.VolumeStore.to_device)
+ * instead of a batch of stored tiles: the reference's ShiftScaleRotate of the whole volume followed by RandomCrop3D(dim_out)
+ * (multi_output_unet3d/data.py:152-230).  One launch per field per batch renders dst [n, channels, td, th, tw] (float32).
+ *
+ * arena: arena_elems elements, float32 or uint8 (arena_is_u8 != 0, widened as (float)byte / 255.0f); the items of one field one after
+ * the other, each [channels, d_i, h_i, w_i].  sources[s] names sample s's item -- its element offset in THIS field's arena and its
+ * extent -- and the first z-plane z0 of the crop.  params[s] is biu_augf_params unchanged.
+ *
+ * Gather.  Output voxel (c, z, y, x) of sample s reads plane (c, z0 + z) of the item at the in-plane coordinate m (x, y, 1): m is the
+ * fp64 2x3 map from TILE pixel to ITEM pixel, i.e. the whole-plane shift-scale-rotate map about the centre of the item's (h, w) plane
+ * (augment._matrix's sign) composed with the crop origin (ox, oy) (augment.vol_crop_matrix).  Nothing wraps; `border` (BIU_AUGV_REFLECT /
+ * BIU_AUGV_CONSTANT) applies in the ITEM's (h, w), exactly as in biu_augment_vol_f32.  z is never resampled.
+ *
+ * Kinds, stages, samplers, stage ids and the Philox counter are biu_augment_vol_f32's: IMAGE is bilinear in fp64, then BC (product and sum
+ * rounded one after the other) -> BLUR -> SHOT -> GAUSS; the blur's halo is the reflect-101 of the OUTPUT tile th x tw (cv2.blur on the
+ * cropped patch), and the noise element is the voxel's index inside the OUTPUT sample's field, ((c td + z) th + y) tw + x.  MASK is
+ * nearest.  VECTOR takes channel pairs (2j, 2j + 1), a whole item volume d h w apart, gathers both nearest at one voxel, then rotates by
+ * (cos_t, sin_t).
+ *
+ * NaN in a MASK or VECTOR item means "no label"; dst never holds NaN (nan_to_val itself must not be NaN):
+ *   MASK    : a NaN source voxel gives nan_to_val
+ *   VECTOR  : if either plane of the pair is NaN at the source voxel, both outputs are nan_to_val and no rotation is applied
+ *   IMAGE   : finite by the store's contract; NaN is not special-cased
+ * A constant-border tap outside the plane reads 0, as in biu_augment_vol_f32, not nan_to_val.
+ *
+ * Equivalence law.  For an item whose (d, h, w) equals (td, th, tw), with z0 = 0 and origin (0, 0), the output equals biu_augment_vol_f32 on
+ * that item for the same record bit for bit, for every kind and border, on NaN-free data.
+ *
+ * Safety.  The item base is a 64-bit offset, index math inside an item is 32-bit.  Per sample the kernel checks d, h, w > 0,
+ * channels d h w < 2^31 - 4, 0 <= z0, z0 + td <= d and that the item lies inside [arena, arena + arena_elems); a sample that fails is
+ * rendered as nan_to_val, and nothing outside the arena is ever read.  Null pointers, dst overlapping the arena or the records,
+ * unaligned float, record or source pointers, non-positive extents, an unknown kind or border, odd VECTOR channels,
+ * max_blur_k > BIU_AUG_MAX_BLUR, field_id >= 2^28, an output of 2^31 elements or more and a NaN nan_to_val return a status and launch
+ * nothing.  No atomics, no scratch.
+ *
+ * The launch is cut as biu_augment_vol_f32 is, from the OUTPUT shape: biu_augment_vol_chunk(n, channels, td, th, tw, kind, max_blur_k,
+ * dst_aligned16) answers for this launch too.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct biu_augv_source {
+    uint64_t offset;          /* element offset of the item [channels, d, h, w] in this field's arena */
+    int32_t d, h, w;          /* the item's extent */
+    int32_t z0;               /* first z-plane of the crop */
+} biu_augv_source;            /* 24 bytes */
+int biu_augment_vol_f32_crop(const void* arena, int arena_is_u8, unsigned long long arena_elems, float* dst,
+                             int n, int channels, int td, int th, int tw, int kind, int border,
+                             const biu_augf_params* params, const biu_augv_source* sources, float nan_to_val,
+                             int max_blur_k, unsigned long long seed, unsigned epoch, unsigned field_id, biu_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused multi-tensor Adam                                                              [K14]
  * replaces torch.optim.Adam(lr) step: unet/train.py:102,139 (betas 0.9/0.999, eps 1e-8, no decay).
  * One launch updates `n` parameter tensors; ptrs are device arrays of device pointers.

@@ -12,6 +12,14 @@ bf16 -- and compares them with what the kernel wrote.  Every conv / ConvT / pool
 BatchNorm-statistics, BatchNorm-backward-sums and BatchNorm-backward-apply path and both members of every two-source
 (concat) call is checked on the shapes and fusions of the real network, to ~1 ulp of the storage type.
 
+Gradients are followed leaf by leaf: the first source of a nested U-Net's two-source call is a pitched span of several producers'
+slices (engine.Buf.span), whose leaves may have been written only in part when the whole prefix gradient arrives (deep supervision) --
+the expectation accumulates onto the stored gradient where a leaf was written and onto zero where the engine zero-fills it
+(span_before).  The head backward is checked per trunk, as the engine groups it.  A backward behind an eval-mode forward is checked
+with the running statistics as constants (bn_bwd_expect): dy = gamma * invstd * dz and a live conv-bias gradient; behind batch
+statistics that gradient must be the exact zero.  The formulas the hooks apply are plain functions, pinned against float64 autograd
+without an engine in tests/test_insitu_host.py.
+
 Test infrastructure only (uses Engine.trace, a hook the product never sets).
 """
 import math
@@ -72,6 +80,97 @@ def dact(raw, xf):
     return torch.where(t > 0, torch.ones_like(t), sl.expand_as(t)), t
 
 
+# ---- the checker's own formulas: plain functions of CPU float64 tensors, shared by the hooks below and by tests/test_insitu_host.py,
+# which pins them against torch autograd without an engine -------------------------------------------------------------------------
+_DIMS = (0, 2, 3, 4)
+
+
+def resample_ref(kind, a, out_space):
+    """The five forms of ResampleNode on an NCDHW tensor: 2-D ``bilinear`` is the nested U-Net's nn.Upsample(align_corners=True)
+    (models._NestedUNet), ``trilinear`` the 3-D networks' F.interpolate(align_corners=False) (csrc/biu_extra.hip)."""
+    if kind == "maxpool":
+        return F.max_pool3d(a, (2 if a.shape[2] > 1 else 1, 2, 2))
+    if kind == "down":
+        return a[:, :, ::2 if a.shape[2] > 1 else 1, ::2, ::2]
+    sf = (2 if out_space[1] == 2 * a.shape[2] else 1, 2, 2)
+    if kind == "up":
+        return F.interpolate(a, scale_factor=sf, mode="nearest")
+    if kind == "bilinear":
+        assert a.shape[2] == 1 and sf[0] == 1, "bilinear is the 2-D form"
+        return F.interpolate(a.squeeze(2), scale_factor=2, mode="bilinear", align_corners=True).unsqueeze(2)
+    assert kind == "trilinear", kind
+    return F.interpolate(a, scale_factor=sf, mode="trilinear", align_corners=False)
+
+
+def bn_bwd_expect(dz, y, mean, invstd, gamma, batch_stats):
+    """BatchNorm backward behind a conv, from dz = d loss / d (BatchNorm output) and the raw conv output y (NCDHW; mean, invstd, gamma: [C]).
+    ``batch_stats``: the forward normalised with the statistics of y itself, so mean and invstd depend on y and the conv bias cancels
+    (its gradient is identically zero); else they are constants (running statistics): dy = gamma * invstd * dz and the conv bias
+    gradient sum_v dy is a real number.  -> dict(dbeta, dgamma, dy, dbias, gis)."""
+    v = lambda t: t.double().view(1, -1, 1, 1, 1)
+    m = y.numel() / y.shape[1]
+    yhat = (y - v(mean)) * v(invstd)
+    s1, s2 = dz.sum(dim=_DIMS), (dz * yhat).sum(dim=_DIMS)
+    gis = v(gamma.double() * invstd.double())
+    if batch_stats:
+        dy = gis * (dz - v(s1) / m - yhat * v(s2) / m)
+        dbias = torch.zeros_like(s1)
+    else:
+        dy = gis * dz
+        dbias = gis.flatten() * s1
+    return dict(dbeta=s1, dgamma=s2, dy=dy, dbias=dbias, gis=gis)
+
+
+def span_before(flags, widths, grad):
+    """What a kernel that writes the whole gradient of a span accumulates onto, per leaf: the stored gradient where the leaf was written,
+    zero where it was not but another leaf of the span was (Act.g_accumulate zero-fills it; the buffer itself may hold anything there),
+    and nothing at all (None) when no leaf was written -- the kernel then writes.  ``grad``: the span's gradient [N, sum(widths), ...]
+    as the buffer holds it; ``flags``: written? per leaf."""
+    if not any(flags):
+        return None
+    out, o = grad.clone(), 0
+    for f, c in zip(flags, widths):
+        if not f:
+            out[:, o:o + c] = 0
+        o += c
+    return out
+
+
+def accumulated(contrib, before):
+    return contrib if before is None else contrib + before
+
+
+_HEAD_DERIV = {0: lambda a: torch.ones_like(a), 1: lambda a: a * (1 - a), 2: lambda a: 1 - a * a, 3: lambda a: (a > 0).double()}
+
+
+def head_dlogits(act, gl, ga, a):
+    """d loss / d logits of a head from the gradients on its logits (gl) and on its activated output (ga), the activation's derivative
+    taken from the activated output a (engine.HeadNode.dlogits): act 0 none, 1 sigmoid, 2 tanh, 3 relu."""
+    dl = gl if gl is not None else 0.0
+    if ga is not None:
+        dl = dl + ga * _HEAD_DERIV[act](a)
+    return dl
+
+
+def group_by_trunk(live):
+    """[(head, d logits)] -> [[(head, d logits), ...] per trunk], heads grouped by the Act they read, in first-seen order -- as
+    Engine._backward_heads groups them (the deep-supervision heads of a nested U-Net sit on x0_1 ... x0_L)."""
+    groups = {}
+    for h, dl in live:
+        groups.setdefault(id(h.xin), []).append((h, dl))
+    return list(groups.values())
+
+
+def head_group_expect(a, heads, before=None):
+    """The 1x1 heads of one trunk: a = T(trunk) [N,C,D,H,W], heads = [(weight [cout, C], d logits [N,cout,D,H,W]), ...] ->
+    (d trunk = sum over the heads (+ the gradient the trunk already held), [(dW, dbias) per head])."""
+    dx, per = torch.zeros_like(a), []
+    for w, dl in heads:
+        dx = dx + torch.einsum("nodhw,oc->ncdhw", dl, w)
+        per.append((torch.einsum("nodhw,ncdhw->oc", dl, a), dl.sum(dim=_DIMS)))
+    return accumulated(dx, before), per
+
+
 class Report:
     def __init__(self):
         self.rows = []          # (label, what, worst normalised deviation, fraction within tolerance)
@@ -103,6 +202,8 @@ class InSitu:
         self.strict_frac = strict_frac
         # one storage ulp: 2^-8 relative for bf16 (value = 1.xxxxxxx * 2^e, 7 fraction bits), fp32 accumulation noise otherwise
         self.rel = 2.0 ** -7 if bf16 else 2e-5
+        self.partial_spans = []     # (label, written? per leaf) of every span found written only in part when a node was about to write all of it
+        self.head_groups = 0        # trunks the last head backward served
         eng.trace = self
 
     # ---- comparison ------------------------------------------------------------------------------------------------
@@ -135,10 +236,40 @@ class InSitu:
             self.failures.append(f"{label}: {what}: deviation {dev:.2f}x tolerance (rel {rel})")
 
     # ---- helpers ---------------------------------------------------------------------------------------------------
-    def _mfma(self, cin, cout, dil=1, k=3):
-        if cin == 1 and self.bf16 and dil == 1 and k == 3 and cout >= 16 and cout % 16 == 0:
+    def _mfma(self, cin, cout, dil=1, k=3, c1=True):
+        """Does the MFMA path (bf16 operands in bf16 mode) serve a forward with these channel counts?  A data gradient is the forward
+        with the counts swapped and ``c1=False``: the first-layer kernels are forward / weight-gradient kernels only, so the data gradient
+        of a block with ONE output channel (Unet_v0's decode9) stays on the direct kernel with fp32 weights."""
+        if c1 and cin == 1 and self.bf16 and dil == 1 and k == 3 and cout >= 16 and cout % 16 == 0:
             return True                     # first layer through the im2col MFMA kernels (csrc/biu_c1.hip): bf16 weights
         return dil == 1 and k != 1 and cin >= 16 and cin % (16 if self.bf16 else 8) == 0 and cout >= 16 and cout % 8 == 0
+
+    def _aligned(self, *acts):
+        """Pointer and row pitch of every tensor on 16 bytes: the other half of biu_mfma_conv_ok / biu_mfma_wgrad_ok (a channel slice of a
+        row or concat buffer starts c0 elements into its row)."""
+        es = 2 if self.bf16 else 4
+        return all((a.buf.t.data_ptr() + a.c0 * es) % 16 == 0 and (a.buf.shape[4] * es) % 16 == 0
+                   for x in acts for a in self._parts(x) if a.buf.t is not None)       # (None: released, a folded op never reads it)
+
+    def _check_dispatch(self, nd):
+        """The predicates that decide where this model rounds bf16 operands against what the library says of the same layer: a packed
+        weight image exists exactly for the channel counts biu_mfma_conv_ok takes (forward: K = Cin, data gradient: K = Cout), the weight
+        gradient has a workspace exactly for those biu_mfma_wgrad_ok takes, a two-source block is one biu_conv_cat_ok accepts."""
+        cin, cout, k = nd.xin.c, nd.y.c, (nd.kh, nd.kw)
+        if cin == 1:               # first layer: csrc/biu_c1.hip, no packed image either way
+            return
+        want_f = nd.dil == 1 and k == (3, 3) and nd.pk_f.buf is not None
+        want_b = nd.dil == 1 and k == (3, 3) and nd.pk_b.buf is not None
+        want_w = nd.dil == 1 and k == (3, 3) and lib.biu_conv_bwd_weight_workspace(cin, cout, nd.kd, nd.kh, nd.kw, self.eng.dtype) > 0
+        got = (self._mfma(cin, cout, nd.dil, nd.kw), self._mfma(cout, cin, nd.dil, nd.kw, c1=False), self._wgrad_mfma(nd))
+        assert got == (want_f, want_b, want_w), f"{nd.label}: the checker's MFMA predicates {got} != the library's {(want_f, want_b, want_w)}"
+        if nd.form == "cat":
+            p0, p1 = nd.xin.parts
+            assert lib.biu_conv_cat_ok(p0.a(), p1.a(), nd.y.a(), nd.kd, nd.kh, nd.kw, nd.dil, self.eng.dtype) == 1, nd.label
+        assert not any(got) or self._aligned(nd.xin, nd.y), f"{nd.label}: a tensor off the 16-byte grid takes the direct kernels: model it before relying on this check"
+
+    def _wgrad_mfma(self, nd):
+        return nd.xin.c >= 16 and nd.xin.c % 8 == 0 and nd.y.c >= 16 and nd.y.c % 8 == 0 and nd.dil == 1 and nd.kw == 3
 
     def _conv(self, x, w, b, dil, transposed=False):
         nd3 = w.dim() == 5
@@ -244,8 +375,17 @@ class InSitu:
         return torch.cat([act_T(p) for p in self._parts(xin)], 1)
 
     def _gsnap(self, a):
-        """gradient of an Act before a node accumulates into it (None when nothing has been written yet)."""
-        return act_grad(a) if a.g_written() else None
+        """gradient of an Act before a node accumulates into it (None when nothing has been written yet), leaf by leaf for a span
+        (span_before).  Reads the flags only: Act.g_written() asserts on a span written in part, Act.g_accumulate() would zero-fill it."""
+        flags = [a.buf.leaves[k] for k in a.leaves]
+        if not any(flags):
+            return None
+        if not all(flags):
+            self.partial_spans.append((lib.label, tuple(flags)))
+        return span_before(flags, [k[1] for k in a.leaves], act_grad(a))
+
+    def _all_marked(self, a, lab):
+        assert all(a.buf.leaves[k] for k in a.leaves), f"{lab}: a leaf of the gradient just written is not marked written"
 
     # ---- dispatcher ------------------------------------------------------------------------------------------------
     def __call__(self, phase, node, when):
@@ -274,6 +414,7 @@ class InSitu:
 
     def fwd_ConvBlockNode_post(self, nd, s):
         lab = nd.label + ":fwd"
+        self._check_dispatch(nd)
         if getattr(nd, "foldt", None) is not None:
             want = self._foldt_fwd(nd)
             if not self.bf16:            # the folded op is the same function as ConvT -> concat -> conv
@@ -337,16 +478,7 @@ class InSitu:
         self.close(nd.label + ":fwd", "ConvT output", act_raw(nd.y), want)
 
     def _resample(self, kind, a, out_space):
-        if kind == "maxpool":
-            return F.max_pool3d(a, (2 if a.shape[2] > 1 else 1, 2, 2))
-        if kind == "down":
-            return a[:, :, ::2 if a.shape[2] > 1 else 1, ::2, ::2]
-        sf = (2 if out_space[1] == 2 * a.shape[2] else 1, 2, 2)
-        if kind == "up":
-            return F.interpolate(a, scale_factor=sf, mode="nearest")
-        if a.shape[2] == 1 and sf[0] == 1:
-            return F.interpolate(a.squeeze(2), scale_factor=2, mode="bilinear", align_corners=False).unsqueeze(2)
-        return F.interpolate(a, scale_factor=sf, mode="trilinear", align_corners=False)
+        return resample_ref(kind, a, out_space)
 
     def fwd_ResampleNode_post(self, nd, s):
         if getattr(nd, "skip", False):             # its reader folds forward and backward onto the coarse tensor: nothing was computed
@@ -389,29 +521,28 @@ class InSitu:
             if g is None:
                 continue
             gl, ga, a = (None if t is None else t.detach().float().cpu().double() for t in g)
-            dl = gl if gl is not None else 0.0
-            if ga is not None:                     # the activation's derivative from the activated output (engine.HeadNode.dlogits)
-                d = {0: lambda a: torch.ones_like(ga), 1: lambda a: a * (1 - a), 2: lambda a: 1 - a * a, 3: lambda a: (a > 0).double()}[h.act](a)
-                dl = dl + ga * d
-            live.append((h, dl))
-        return dict(live=live)
+            dl = head_dlogits(h.act, gl, ga, a)
+            live.append((h, dl if self.eng.nd == 3 else dl.unsqueeze(2)))
+        # one backward per trunk, as Engine._backward_heads runs them; each trunk with the gradient it held before (none, as far as the
+        # engine goes today: the heads run first)
+        return dict(groups=[(grp, self._gsnap(grp[0][0].xin)) for grp in group_by_trunk(live)])
 
     def bwd_Heads_post(self, hg, s):
-        if not s["live"]:
-            return
-        x = s["live"][0][0].xin
-        a = act_T(x)
-        dx = torch.zeros_like(a)
-        for h, dl in s["live"]:
-            lab = h.label + ":bwd"
-            if self.eng.nd == 2:
-                dl = dl.unsqueeze(2)
-            w = h.conv.weight.detach().cpu().double().reshape(h.cout, x.c)
-            dx += torch.einsum("nodhw,oc->ncdhw", dl, w)
-            self.vec_close(lab, "head dW", self.eng.grads[h.conv.weight].cpu().reshape(h.cout, x.c), torch.einsum("nodhw,ncdhw->oc", dl, a), rel=1e-4, floor=1e-5)
-            self.vec_close(lab, "head dbias", self.eng.grads[h.conv.bias].cpu(), dl.sum(dim=(0, 2, 3, 4)), rel=1e-4, floor=1e-5)
-        self.close("heads:bwd", "d trunk output", act_grad(x), dx)
-        self._check_red(x, "heads:bwd")
+        self.head_groups = len(s["groups"])
+        for grp, before in s["groups"]:
+            x = grp[0][0].xin
+            assert all(h.xin is x for h, _ in grp)
+            glab = "heads:bwd" if len(s["groups"]) == 1 else f"heads@{grp[0][0].label}:bwd"
+            a = act_T(x)
+            dx, per = head_group_expect(a, [(h.conv.weight.detach().cpu().double().reshape(h.cout, x.c), dl) for h, dl in grp], before)
+            for (h, _), (dw, db) in zip(grp, per):
+                lab = h.label + ":bwd"
+                self.vec_close(lab, "head dW", self.eng.grads[h.conv.weight].cpu().reshape(h.cout, x.c), dw, rel=1e-4, floor=1e-5)
+                self.vec_close(lab, "head dbias", self.eng.grads[h.conv.bias].cpu(), db, rel=1e-4, floor=1e-5)
+            if self.eng.wants_grad(x):
+                self.close(glab, "d trunk output" + (" (accumulated)" if before is not None else ""), act_grad(x), dx)
+                self._all_marked(x, glab)
+                self._check_red(x, glab)
 
     def _check_red(self, xin_act, lab):
         """If the node just handed the producer of `xin_act` its BatchNorm-backward partial sums, check them against the
@@ -441,9 +572,9 @@ class InSitu:
         parts = self._parts(nd.xin)
         extra = list(nd.foldt.params) if getattr(nd, "foldt", None) is not None else []
         if extra:                   # folded ConvT + concat + conv: gradients go to the ConvT's coarse input and to the skip tensor
-            return dict(da=act_grad(nd.y), gx=[self._gsnap(nd.foldt.xin), self._gsnap(parts[1])],
+            return dict(da=act_grad(nd.y), red=nd.red_nblk, gx=[self._gsnap(nd.foldt.xin), self._gsnap(parts[1])],
                         pg={p: (self.eng.grads[p].detach().cpu().double().clone() if p in self.eng.grads else None) for p in list(nd.params) + extra})
-        return dict(da=act_grad(nd.y), gx=[self._gsnap(p) for p in parts],
+        return dict(da=act_grad(nd.y), red=nd.red_nblk, gx=[self._gsnap(p) for p in parts],
                     gfold=self._gsnap(nd.fold_src) if getattr(nd, "fold_dg_slot", None) is not None else None,
                     pg={p: (self.eng.grads[p].detach().cpu().double().clone() if p in self.eng.grads else None) for p in nd.params})
 
@@ -460,32 +591,45 @@ class InSitu:
         fac, t = dact(y, xf)
         near = t.abs() < 1e-6 * float(t.abs().max())            # LeakyReLU decision closer than fp32 rounding: either branch is right
         dz = da * fac
-        mean, invstd = nd.save_mean.cpu().double().view(1, -1, 1, 1, 1), nd.save_invstd.cpu().double().view(1, -1, 1, 1, 1)
-        yhat = (y - mean) * invstd
-        m = y.numel() / y.shape[1]
-        s1, s2 = dz.sum(dim=(0, 2, 3, 4)), (dz * yhat).sum(dim=(0, 2, 3, 4))
-        self.vec_close(lab, "dbeta", self._pgrad(nd, s, nd.bn.bias), s1, rel=1e-4, floor=3e-5)
-        self.vec_close(lab, "dgamma", self._pgrad(nd, s, nd.bn.weight), s2, rel=1e-4, floor=3e-5)
-        gis = (nd.bn.weight.detach().cpu().double() * nd.save_invstd.cpu().double()).view(1, -1, 1, 1, 1)
-        dy = gis * (dz - s1.view(1, -1, 1, 1, 1) / m - yhat * s2.view(1, -1, 1, 1, 1) / m)
+        bn = nd.bn
+        if nd.batch_stats:
+            mean, invstd = nd.save_mean.cpu().double(), nd.save_invstd.cpu().double()
+        else:           # eval-mode backward: the running statistics are constants of the forward
+            mean, invstd = bn.running_mean.detach().cpu().double(), torch.rsqrt(bn.running_var.detach().cpu().double() + bn.eps)
+            assert s["red"] == 0, f"{lab}: fused BatchNorm-backward sums were handed to a block that normalised with running statistics"
+        ex = bn_bwd_expect(dz, y, mean, invstd, bn.weight.detach().cpu(), nd.batch_stats)
+        gis, dy = ex["gis"], ex["dy"]
+        self.vec_close(lab, "dbeta", self._pgrad(nd, s, bn.bias), ex["dbeta"], rel=1e-4, floor=3e-5)
+        self.vec_close(lab, "dgamma", self._pgrad(nd, s, bn.weight), ex["dgamma"], rel=1e-4, floor=3e-5)
+        if nd.conv.bias is not None:
+            db = self._pgrad(nd, s, nd.conv.bias)
+            if nd.batch_stats:      # removed again by the batch mean: the engine emits the exact zero (ConvBlockNode.bwd)
+                nz = int(torch.count_nonzero(db))
+                self.rep.add(lab, "conv dbias == 0", float(nz), 0.0 if nz else 1.0)
+                if nz:
+                    self.failures.append(f"{lab}: conv bias gradient in front of a batch-statistics BatchNorm has {nz} non-zero entries")
+            else:
+                self.vec_close(lab, "conv dbias (eval)", db, ex["dbias"], rel=1e-4, floor=3e-5)
         dy_got = act_grad(nd.y)
-        # the result is a difference of nearly equal terms where |dy| << |dz|: tolerance relative to the operands
-        self.close(lab, "dy (BN+LReLU bwd)", dy_got, dy, abs_frac=(2.0 ** -8 if self.bf16 else 1e-5) * float(dz.pow(2).mean().sqrt() * gis.abs().max() / (dy.pow(2).mean().sqrt() + 1e-30) + 1.0), ignore=near)
+        if nd.batch_stats:
+            # the result is a difference of nearly equal terms where |dy| << |dz|: tolerance relative to the operands
+            self.close(lab, "dy (BN+LReLU bwd)", dy_got, dy, abs_frac=(2.0 ** -8 if self.bf16 else 1e-5) * float(dz.pow(2).mean().sqrt() * gis.abs().max() / (dy.pow(2).mean().sqrt() + 1e-30) + 1.0), ignore=near)
+        else:
+            self.close(lab, "dy (eval BN+LReLU bwd)", dy_got, dy, ignore=near)       # one product per element: the plain rule
         if getattr(nd, "foldt", None) is not None:
-            self._bwd_foldt_check(nd, s, lab, dy_got)
+            self._bwd_foldt_check(nd, s, lab, dy_got, ex["dbias"])
             return
         # weight gradient from the dy the engine actually stored
         if getattr(nd, "fold_all", False):          # the up-sampled tensor was never materialised: rebuild it from the coarse one
             a = F.interpolate(act_T(nd.fold_src), scale_factor=2, mode="nearest")
         else:
             a = self._T_cat(nd.xin)
-        wgrad_mfma = nd.xin.c >= 16 and nd.xin.c % 8 == 0 and nd.y.c >= 16 and nd.y.c % 8 == 0 and nd.dil == 1 and nd.kw == 3
-        if self.bf16 and wgrad_mfma:
+        if self.bf16 and self._wgrad_mfma(nd):
             a = _r(a.float(), True).double()
         w = nd.conv.weight.detach().cpu().double()
         wv = w.clone().requires_grad_(True)
         av = a.clone().requires_grad_(True)
-        wq = _r(w.float(), True).double() if (self.bf16 and self._mfma(nd.y.c, nd.xin.c, nd.dil, nd.kw)) else w     # dgrad: K = Cout
+        wq = _r(w.float(), True).double() if (self.bf16 and self._mfma(nd.y.c, nd.xin.c, nd.dil, nd.kw, c1=False)) else w     # dgrad: K = Cout
         out = self._conv(av, wv, None, nd.dil)
         (gw,) = torch.autograd.grad(out, wv, dy_got, retain_graph=False)
         self.vec_close(lab, "dW", self._pgrad(nd, s, nd.conv.weight), gw, rel=2e-4, floor=3e-5)
@@ -507,14 +651,13 @@ class InSitu:
                 if isinstance(p, E.Act) and not self.eng.wants_grad(p):
                     o += p.c
                     continue
-                want = gx[:, o:o + p.c]
-                if before is not None:
-                    want = want + before
+                want = accumulated(gx[:, o:o + p.c], before)        # (before: leaf by leaf where p is a span, _gsnap)
                 self.close(lab, f"dx[{o}:{o + p.c}]" + (" (accumulated)" if before is not None else ""), act_grad(p), want)
+                self._all_marked(p, lab)
                 self._check_red(p, lab)
                 o += p.c
 
-    def _bwd_foldt_check(self, nd, s, lab, dy_got):
+    def _bwd_foldt_check(self, nd, s, lab, dy_got, dy_sum):
         """Gradients of the folded ConvT + concat + conv from the dy the engine stored: autograd through the unfolded expression with the
         operands as the kernels see them (inputs in the storage type, the up-sampled tensor never rounded, weights fp32 in the chain rule;
         the data gradients use the packed -- rounded -- weights)."""
@@ -531,8 +674,10 @@ class InSitu:
         # the ConvT bias reaches dW_conv (b_T[c] S_k) and db_T (W_conv . S_k) through S_k = sum of dy over the voxels whose tap k stays inside,
         # which the kernel takes as MINUS the border sums: sum_v dy = 0 exactly behind a train-mode BatchNorm.  The STORED dy carries its
         # rounding (bf16: |sum_v dy| ~ sqrt(N) 2^-9 |dy|), which autograd on the stored dy includes and the kernel -- closer to the fp32
-        # reference there -- does not: that residue is allowed for
-        tot = float(dy_got.sum(dim=(0, 2, 3, 4)).abs().max())
+        # reference there -- does not: that residue is allowed for.  Behind an eval-mode BatchNorm sum_v dy is a real number, which the
+        # kernel takes from the fp32 sums (``dy_sum`` = gamma * invstd * sum dz, bn_bwd_expect's conv dbias): the residue is then the
+        # distance of the stored dy's sum from THAT
+        tot = float((dy_got.sum(dim=(0, 2, 3, 4)) - dy_sum).abs().max())
         resid_w = tot * float(bt.detach().abs().max())
         self.vec_close(lab, "dW (conv, folded)", self._pgrad(nd, s, nd.conv.weight), gwc, rel=2e-4, floor=3e-5 + resid_w / (float(gwc.abs().max()) + 1e-30))
         self.vec_close(lab, "dW (ConvT, folded)", self._pgrad(nd, s, ct.up.weight), gwt, rel=2e-4, floor=3e-5)
@@ -600,7 +745,7 @@ class InSitu:
         self.vec_close(lab, "dW", self._pgrad(nd, s, nd.up.weight), gw, rel=2e-4, floor=3e-5)
         self.vec_close(lab, "dbias", self._pgrad(nd, s, nd.up.bias), dy.sum(dim=(0, 2, 3, 4)), rel=2e-4, floor=3e-5)
         if self.eng.wants_grad(nd.xin):
-            wq = _r(w.float(), True).double() if (self.bf16 and self._mfma(nd.y.c, nd.xin.c)) else w
+            wq = _r(w.float(), True).double() if (self.bf16 and self._mfma(nd.y.c, nd.xin.c, c1=False)) else w
             (gx,) = torch.autograd.grad(self._conv(av, wq, None, 1, transposed=True), av, dy)
             if s["gx"] is not None:
                 gx = gx + s["gx"]
@@ -622,6 +767,21 @@ class InSitu:
         if s["gx"] is not None:
             gx = gx + s["gx"]
         self.close(lab, f"{nd.kind} dx" + (" (accumulated)" if s["gx"] is not None else ""), act_grad(nd.xin), gx, rel=2.0 ** -8 if self.bf16 else 1e-6)
+        self._check_red(nd.xin, lab)
+
+    def bwd_CopyNode_pre(self, nd):
+        if not nd.y.g_written() or not self.eng.wants_grad(nd.xin):
+            return None
+        return dict(gx=self._gsnap(nd.xin))
+
+    def bwd_CopyNode_post(self, nd, s):
+        """grad(xin) == before + grad(y): the copy's source holds d loss / d T(x), which is what the copy's gradient is (biu_act_add)."""
+        if s is None:
+            return
+        lab = nd.label + ":bwd"
+        self.close(lab, "copy dx" + (" (accumulated)" if s["gx"] is not None else ""), act_grad(nd.xin), accumulated(act_grad(nd.y), s["gx"]),
+                   rel=2.0 ** -8 if self.bf16 else 1e-6)
+        self._all_marked(nd.xin, lab)
         self._check_red(nd.xin, lab)
 
     def bwd_MaxJoinNode_pre(self, nd):

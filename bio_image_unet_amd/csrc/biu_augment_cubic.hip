@@ -20,7 +20,9 @@
 #include "biu_augment_stages.h"
 
 namespace {
+using biu_augment_stages::overlap;
 using biu_augment_stages::source_of;
+using biu_augment_stages::wrap;
 
 constexpr int TPB = 256;
 constexpr int RANGE_TPB = 1024;                 // the range kernel's one block per sample
@@ -48,11 +50,6 @@ struct Launch {
 
 __device__ __forceinline__ float load(const Launch& L, int i) {
     return L.u8 ? (float)static_cast<const uint8_t*>(L.src)[i] / 255.0f : static_cast<const float*>(L.src)[i];
-}
-__device__ __forceinline__ int wrap(int i, int n) {
-    if ((unsigned)i < (unsigned)n) return i;
-    i %= n;
-    return i < 0 ? i + n : i;
 }
 
 // grid = n; one block of RANGE_TPB lanes walks the sample's field, 16 bytes per lane and step where the field allows it (a single block has
@@ -243,12 +240,6 @@ __global__ __launch_bounds__(TPB) void k_spline_gather(Launch L, int total) {
             }
         }
     }
-}
-
-// do [a, a + na) and [b, b + nb) share a byte
-bool overlap(const void* a, i64 na, const void* b, i64 nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
 }
 }  // namespace
 

@@ -799,6 +799,12 @@ int biu_augment_f32_cubic(const void* src, int src_is_u8, const float* coef, con
  *                      zero-filled taps (the reference's rotate_array at order = 1: scipy rounds the rotated uint8 NaN mask half up before
  *                      its > 0.5 test)
  *   IMAGE            : finite by the store's contract; NaN is not special-cased
+ *
+ * Equivalence law.  For items whose (h, w) equals (th, tw), the output equals biu_augment_f32 on the batch of those items for the same
+ * records bit for bit, for every kind, on NaN-free data.  One exception: where tw % 4 == 0 and dst is 16-byte aligned, biu_augment_f32
+ * rotates a VECTOR pair with the cos_t product fused into the sum, and this entry point rounds both products as biu_augment_f32 does on
+ * its other path; under an arbitrary angle (cos_t, sin_t not in {0, 1, -1}) the two then differ by that one rounding.
+ *
  * Null pointers, dst overlapping the arena or the records, unaligned float or record pointers, non-positive extents, field_id >= 2^28,
  * an output of 2^31 - 4 elements or more and a NaN nan_to_val return a status and launch nothing.  No atomics, no scratch.
  * ---------------------------------------------------------------------------------------------- */

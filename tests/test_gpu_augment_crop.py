@@ -15,6 +15,8 @@ Bounds (none of them comes from what the kernel gives; they are those of ``tests
   ``3 sqrt(2) 2^-24`` (that file's reasoning: three roundings on ``|c cos_t| + |s sin_t| <= sqrt(2)``).
 * bilinear MASK with NaN: the NaN decision equal wherever ``|w_nan - 0.5| > 1e-6``; values within six times the deviation of the fp32 numpy
   restatement from the float64 oracle on the same inputs; no NaN in ``dst``.  Blur, Gauss noise, brightness/contrast, a chain: the same margin.
+* the equivalence law (items of the tile's extent, the same record bytes, NaN-free data in [0.05, 0.9] -> ``biu_augment_f32``'s bytes): bit for
+  bit, but for the one rounding ``test_equivalence_law`` names, which is held to ``2 VECTOR_BOUND``.
 * shot noise: counts differ from the oracle's by at most one, on at most six times the share of pixels on which the fp32 restatement differs,
   pooled over the cases.
 """
@@ -305,6 +307,77 @@ def test_noise_is_that_of_the_tile_kernel_bit_for_bit():
                                   int(kw.get("blur_k", 0)), SEED, EPOCH, FID, C.c_void_p(torch.cuda.current_stream().cuda_stream)), "augment_f32")
         torch.cuda.synchronize()
         assert _same(got, dst.cpu().numpy()), kw
+
+
+def _law_records(h, w):
+    """Every record kind of the law once; the first nine do not blur.  ``record_f32`` turns square tiles only, so the quarter turns are
+    ``record_crop``'s: to either entry point a record is a map, a pair rotation and stages."""
+    return np.stack([A.record_crop(0, (h, w), rot_k=1, origin=(2, 1)), A.record_f32(1, h, w, angle=33.7), A.record_f32(2, h, w, scale=1.21),
+                     A.record_f32(3, h, w, shift=(w + 5, -(2 * h + 3))), A.record_f32(4, h, w, shot_s=0.004), A.record_f32(5, h, w, gauss_sigma=0.07),
+                     A.record_f32(6, h, w, bc=(1.1, -0.05)), A.record_f32(7, h, w, angle=151.0, scale=0.93, shot_s=0.01, gauss_sigma=0.03, bc=(1.05, -0.02)),
+                     A.record_f32(8, h, w), A.record_f32(9, h, w, angle=17.3, blur_k=3),
+                     A.record_crop(10, (h, w), rot_k=3, origin=(1, 3), blur_k=A.MAX_BLUR, shot_s=0.01, gauss_sigma=0.03, bc=(0.95, 0.03))])
+
+
+# (h, w), dst one float behind a 16-byte boundary: 2 x 2 blocks with partial edges on the 16-byte row path; the same on the unaligned path; the
+# per-pixel path (w % 4 != 0)
+LAW_CASES = [((72, 68), False), ((72, 68), True), ((40, 38), False)]
+
+
+@pytest.mark.parametrize("source", SOURCES)
+@pytest.mark.parametrize("case", LAW_CASES, ids=["rows", "rows-offset-dst", "pixels"])
+@pytest.mark.parametrize("kind", [CO.IMAGE, CO.MASK, CO.VECTOR], ids=["image", "mask", "vector"])
+def test_equivalence_law(kind, case, source):
+    """include/biu.h: items whose extent is the tile's, the same record bytes, NaN-free data -> the bytes of ``biu_augment_f32``.
+
+    One restriction, found when the two sources still had a kernel file each and kept since: ``biu_augment_f32`` rotates a VECTOR pair with
+    the ``cos_t`` product fused into the sum where a lane stores four pixels of a row (``w % 4 == 0`` and an aligned ``dst``), and with both
+    products rounded everywhere else, as ``biu_augment_f32_crop`` does on every path.  So on the row path the records with an arbitrary angle
+    (``cos_t``, ``sin_t`` not in {0, 1, -1}) are held to ``2 VECTOR_BOUND`` (each side is within ``VECTOR_BOUND`` of the exact pair) instead
+    of to equality; every other record, kind and path is bit for bit."""
+    from bio_image_unet_amd._lib import check
+    (h, w), offset_dst = case
+    recs = _law_records(h, w)
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for these in (recs[:9], recs):                                  # without a blurring sample: the point kernels; with: the tile kernels
+        n = len(these)
+        rng = np.random.default_rng(8)
+        batch = rng.integers(13, 230, size=(n, 2, h, w), dtype=np.uint8) if source == "u8" else (0.05 + 0.85 * rng.random((n, 2, h, w))).astype(np.float32)
+        blur = int(these["blur_k"].max()) if kind == CO.IMAGE else 0
+        par = torch.from_numpy(these.view(np.uint8).copy()).cuda()
+        src = torch.from_numpy(batch).cuda()
+        arena = torch.cat([src.new_zeros(8), src.reshape(-1)])      # the items behind 8 elements, so that no offset is 0
+        sources = np.empty(n, dtype=A.SOURCE_DTYPE)
+        for j in range(n):
+            sources[j] = (8 + j * 2 * h * w, h, w)
+        sources = torch.from_numpy(sources.view(np.uint8).copy()).cuda()
+        outs = []
+        for crop in (False, True):
+            whole = torch.full((n * 2 * h * w + 4,), 7.0, dtype=torch.float32, device="cuda")
+            dst = whole[1:1 + n * 2 * h * w] if offset_dst else whole[:n * 2 * h * w]
+            assert (dst.data_ptr() % 16 == 4) == offset_dst
+            if crop:
+                check(lib.biu_augment_f32_crop(C.c_void_p(arena.data_ptr()), int(source == "u8"), arena.numel(), C.c_void_p(dst.data_ptr()), n, 2, h, w, kind,
+                                               C.c_void_p(par.data_ptr()), C.c_void_p(sources.data_ptr()), 0.0, blur, SEED, EPOCH, FID, stream()), "augment_f32_crop")
+            else:
+                check(lib.biu_augment_f32(C.c_void_p(src.data_ptr()), int(source == "u8"), C.c_void_p(dst.data_ptr()), n, 2, h, w, kind,
+                                          C.c_void_p(par.data_ptr()), blur, SEED, EPOCH, FID, stream()), "augment_f32")
+            torch.cuda.synchronize()
+            outs.append(dst.view(n, 2, h, w).cpu().numpy())
+            assert bool((whole[1 + n * 2 * h * w:] == 7.0).all())
+        want, got = outs
+        fused = kind == CO.VECTOR and w % 4 == 0 and not offset_dst
+        ok = []
+        for j, r in enumerate(these):
+            if fused and r["flags"] & A.ROT_F:
+                d = float(np.abs(got[j].astype(np.float64) - want[j]).max())
+                print(f"equivalence kind {kind} {h} x {w} {source} record {j}: fused against rounded rotation, max |diff| {d:.3e}, bound {2 * VECTOR_BOUND:.3e}")
+                ok.append(d <= 2 * VECTOR_BOUND)
+            else:
+                ok.append(_same(got[j], want[j]))
+        print(f"equivalence kind {kind} {h} x {w} offset dst {offset_dst} {source} max blur {blur}: {sum(ok)} of {len(ok)} records hold")
+        assert all(ok)
+        assert not _same(got[0], got[8]) and not np.isnan(got).any()            # the records really do different things
 
 
 def test_argument_errors_launch_nothing():

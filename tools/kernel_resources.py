@@ -27,4 +27,4 @@ for name, r in rows.items():
     short = re.sub(r"\(anonymous namespace\)::|__hip_bfloat16|void ", "", dm)[:90]
     if flt and flt not in short:
         continue
-    print(f"{short:<92} vgpr {r.get('VGPRs','?'):>4} agpr {r.get('AGPRs','?'):>4} vspill {r.get('VGPRs Spill','?'):>3} sspill {r.get('SGPRs Spill','?'):>3} scratch {r.get('ScratchSize','?'):>4} occ {r.get('Occupancy','?')}")
+    print(f"{short:<92} vgpr {r.get('VGPRs','?'):>4} agpr {r.get('AGPRs','?'):>4} vspill {r.get('VGPRs Spill','?'):>3} sspill {r.get('SGPRs Spill','?'):>3} scratch {r.get('ScratchSize','?'):>4} lds {r.get('LDS Size','?'):>5} occ {r.get('Occupancy','?')}")

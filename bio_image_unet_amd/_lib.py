@@ -62,6 +62,10 @@ class biu_augf_source(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("h", C.c_int32), ("w", C.c_int32)]
 
 
+class biu_spline_item(C.Structure):
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("has_nan", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class biu_augv_source(C.Structure):
     _fields_ = [("offset", C.c_uint64), ("d", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("z0", C.c_int32)]
 
@@ -196,6 +200,8 @@ SIGNATURES = {
     "biu_spline_prefilter_f32": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "biu_augment_f32_cubic": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "biu_augment_f32_crop": (_I, [_P, _I, C.c_ulonglong, _P, _I, _I, _I, _I, _I, _P, _P, _F, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
+    "biu_spline_prefilter_items": (_I, [_P, _I, C.c_ulonglong, _P, _P, _P, _I, _I, _P, _P]),
+    "biu_augment_f32_crop_cubic": (_I, [_P, _I, C.c_ulonglong, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _F, _P]),
     "biu_augment_vol_f32": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),
     "biu_augment_vol_chunk": (_I, [_I] * 8),
     "biu_augment_vol_f32_crop": (_I, [_P, _I, C.c_ulonglong, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _F, _I, C.c_ulonglong, C.c_uint, C.c_uint, _P]),

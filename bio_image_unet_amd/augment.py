@@ -451,7 +451,10 @@ class AugmenterF32(_AugmenterCore):
     ``target_interp``: how "mask" fields are resampled under an arbitrary-angle rotation.  ``"linear"`` (the default) gathers bilinearly;
     ``"cubic"`` is the reference's ``scipy.ndimage.rotate(order=3, mode='grid-wrap')`` with its clip into the target's own range
     (``biu_spline_prefilter_f32`` + ``biu_augment_f32_cubic``, three launches for such a field instead of one).  The mode draws no uniform:
-    the records of both are the same, and batches without an arbitrary-angle sample take the one ``biu_augment_f32`` launch either way."""
+    the records of both are the same, and batches without an arbitrary-angle sample take the one ``biu_augment_f32`` launch either way.
+    On a ``feed.ImageStore`` the coefficients, the clip range and the NaN indicator are those of the whole item, computed once per store
+    (``ImageStore.spline_tables``, handed to ``feed.CropFeeder(..., spline=)``) and read by one ``biu_augment_f32_crop_cubic`` launch per
+    such field and batch; NaN is carried as the reference's ``rotate_array`` carries it at ``order=3``."""
 
     recipe = "mo2d"
     params_dtype, _rec, n_uniform, blur_flag = PARAMS_F32_DTYPE, _REC_F32, 16, BLUR_F
@@ -459,6 +462,7 @@ class AugmenterF32(_AugmenterCore):
     store_attrs = ("gauss_noise_lims", "shot_noise_lims", "brightness_contrast", "blur_limit", "random_rotate", "scale_limit")
     src_dtypes, dst_dtype, launch_name = (torch.float32, torch.uint8), torch.float32, "augment_f32"
     source_dtype = SOURCE_DTYPE                  # feed.CropFeeder sizes its source buffers by it
+    rot_flag = ROT_F                             # ... and reads from the records whether a batch needs the cubic launch
 
     def __init__(self, *, gauss_noise_lims=(0.01, 0.1), shot_noise_lims=(0.001, 0.01), brightness_contrast=(0.1, 0.1), blur_limit=(3, 5),
                  random_rotate: bool = True, scale_limit=(0, 0), seed: int = 0, kinds: Optional[Dict[str, str]] = None,
@@ -587,11 +591,21 @@ class AugmenterF32(_AugmenterCore):
             sources[name] = src
         return records, sources
 
-    def launch_crop(self, name, arena, dst, params_dev, sources_dev, nan_to_val, max_blur, epoch):
+    def spline_fields(self, store) -> list:
+        """The fields of ``store`` that ``target_interp="cubic"`` resamples with the spline: those of kind "mask"."""
+        return [k for k in store.fields if self.kind(k) == "mask"]
+
+    def launch_crop(self, name, arena, dst, params_dev, sources_dev, nan_to_val, max_blur, epoch, spline=None, item_index_dev=None):
         """One ``biu_augment_f32_crop`` launch on the current stream: field ``name`` of ``dst.shape[0]`` patches ``dst [n, planes, th, tw]`` out
-        of the 1-D device tensor ``arena``; ``params_dev`` / ``sources_dev``: the records and this field's sources on the device, as bytes."""
+        of the 1-D device tensor ``arena``; ``params_dev`` / ``sources_dev``: the records and this field's sources on the device, as bytes.
+
+        ``spline`` (the field's ``feed.SplineTables``) with ``item_index_dev`` (the item of every patch, int32 on the device, as bytes or
+        numbers): the caller has read from the records that some patch of the batch has the ROT flag, as it reads ``max_blur``; a "mask" field
+        of a cubic augmenter then takes the one ``biu_augment_f32_crop_cubic`` launch instead.  Every other field, batch and augmenter
+        keeps the launch above."""
         from ._lib import check, lib
         kind = KINDS_F32[self.kind(name)]
+        cubic = spline is not None and kind == KIND_MASK and self.target_interp == "cubic"
         if arena.dtype not in self.src_dtypes or not arena.is_cuda or arena.dim() != 1 or not arena.is_contiguous():
             raise ValueError(f'field "{name}": the arena is a contiguous 1-D {_names(self.src_dtypes)} device tensor')
         if dst.dtype != torch.float32 or dst.dim() != 4 or not dst.is_contiguous() or dst.device != arena.device:
@@ -602,6 +616,17 @@ class AugmenterF32(_AugmenterCore):
         if params_dev.numel() * params_dev.element_size() < n * PARAMS_F32_DTYPE.itemsize or \
                 sources_dev.numel() * sources_dev.element_size() < n * SOURCE_DTYPE.itemsize:
             raise ValueError(f"{n} patches need {n} parameter records and {n} sources")
+        if cubic:
+            if item_index_dev is None or item_index_dev.numel() * item_index_dev.element_size() < 4 * n or \
+                    spline.coef.numel() != arena.numel() or spline.coef.device != arena.device:
+                raise ValueError(f'field "{name}": the spline tables are those of this arena, with one item index per patch')
+            ind = spline.indicator
+            check(lib.biu_augment_f32_crop_cubic(C.c_void_p(arena.data_ptr()), int(arena.dtype == torch.uint8), arena.numel(), C.c_void_p(spline.coef.data_ptr()),
+                                                 C.c_void_p(ind.data_ptr()) if ind is not None else None, C.c_void_p(spline.table.data_ptr()), spline.n_items,
+                                                 C.c_void_p(item_index_dev.data_ptr()), C.c_void_p(dst.data_ptr()), n, planes, th, tw,
+                                                 C.c_void_p(params_dev.data_ptr()), C.c_void_p(sources_dev.data_ptr()), float(nan_to_val),
+                                                 C.c_void_p(torch.cuda.current_stream(arena.device).cuda_stream)), "augment_f32_crop_cubic")
+            return dst
         check(lib.biu_augment_f32_crop(C.c_void_p(arena.data_ptr()), int(arena.dtype == torch.uint8), arena.numel(), C.c_void_p(dst.data_ptr()),
                                        n, planes, th, tw, kind, C.c_void_p(params_dev.data_ptr()), C.c_void_p(sources_dev.data_ptr()),
                                        float(nan_to_val), max_blur if kind == KIND_IMAGE else 0, self.seed, int(epoch) & 0xFFFFFFFF,

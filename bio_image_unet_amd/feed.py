@@ -28,7 +28,9 @@ The reference's ``DataProcess`` of that family keeps every image WHOLE and crops
 meaning "no label here" (``multi_output_unet/data.py:140-311``).  ``ImageStore`` holds such items -- whole, of differing size, NaN kept -- and
 ``CropFeeder`` renders every training patch from them on the device (``biu_augment_f32_crop``); ``dataprep.prepare_mo2d`` writes one from raw
 arrays.  ``VolumeStore`` is the same for the 3-D multi-output family (``multi_output_unet3d/data.py:152-230``): whole volumes, the same feeder,
-``biu_augment_vol_f32_crop``, ``dataprep.prepare_mo3d``.  All three are at the end of this file.
+``biu_augment_vol_f32_crop``, ``dataprep.prepare_mo3d``.  All three are at the end of this file.  With ``AugmenterF32(target_interp="cubic")``
+an ``ImageStore`` resamples its scalar targets with the reference's cubic spline: ``ImageStore.spline_tables`` computes what depends on the
+items alone once per device, ``CropFeeder(..., spline=tables)`` reads it every batch (``biu_augment_f32_crop_cubic``).
 """
 from __future__ import annotations
 
@@ -423,6 +425,81 @@ class ImageStore(torch.utils.data.Dataset):
                                f"supported") from e
         return arenas
 
+    def spline_tables(self, device, names) -> Dict[str, "SplineTables"]:
+        """What ``AugmenterF32(target_interp="cubic")`` needs of the fields ``names`` (its "mask" fields: ``AugmenterF32.spline_fields(store)``)
+        to resample them with the reference's cubic spline: per field a ``SplineTables`` on ``device`` -- the coefficients of the periodic
+        cubic B-spline through every item (NaN read as 0) in an fp32 arena with the field arena's layout, the same through ``isnan(item)``
+        if some item of the field holds a NaN (else no second arena), and per item its value range and whether it holds a NaN
+        (``biu_spline_prefilter_items``, ``include/biu.h``).  They depend on the items alone, so they are computed once per (store, device)
+        after ``to_device`` and kept as the arenas are: the feeders of a Trainer share them (hand the result to ``CropFeeder(..., spline=)``).
+        They cost HBM: 4 bytes per element of the field, twice that with NaN; tables that do not fit raise ``RuntimeError``."""
+        if self.sizes.shape[1] != 2:
+            raise NotImplementedError(f"{type(self).__name__}: cubic-spline tables exist for 2-D items only (the reference resamples 3-D masks nearest)")
+        arenas = self._arenas_on(device)
+        device = next(iter(arenas.values())).device
+        cache = self.__dict__.setdefault("_splines", {}).setdefault(device, {})
+        for name in names:
+            if name not in arenas:
+                raise KeyError(f'{type(self).__name__} {self.path} has no field "{name}"')
+            if name not in cache:
+                cache[name] = SplineTables.build(arenas[name], self.planes[name], self.offsets[name], self.sizes, f'{self.path} field "{name}"')
+        return {name: cache[name] for name in names}
+
+
+SPLINE_ITEM_DTYPE = np.dtype([("lo", "<f4"), ("hi", "<f4"), ("has_nan", "<u4"), ("reserved", "<u4")])       # include/biu.h: biu_spline_item
+
+
+class SplineTables:
+    """The cubic-spline tables of one field of an ``ImageStore`` on one device (``ImageStore.spline_tables``): ``coef`` (float32, the
+    arena's layout), ``indicator`` (the same, or ``None`` if no item holds a NaN), ``table`` (device bytes: one ``biu_spline_item`` per
+    item) and its host copy ``items`` (``SPLINE_ITEM_DTYPE``: ``lo``, ``hi``, ``has_nan``)."""
+
+    def __init__(self, coef, indicator, table, items):
+        self.coef, self.indicator, self.table, self.items, self.n_items = coef, indicator, table, items, len(items)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.coef, self.indicator, self.table) if t is not None)
+
+    @classmethod
+    def build(cls, arena: torch.Tensor, planes: int, offsets, sizes, what: str = "arena") -> "SplineTables":
+        """Run ``biu_spline_prefilter_items`` on the 1-D device tensor ``arena`` (float32 or uint8) whose items ``[planes, h_i, w_i]`` start at
+        the element ``offsets``; ``sizes [items, 2]``.  The indicator arena is allocated only after the table says that some item has a NaN."""
+        import ctypes as C
+        from ._lib import check, lib
+        from .augment import SOURCE_DTYPE
+        if not arena.is_cuda or arena.dim() != 1 or not arena.is_contiguous() or arena.dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"{what}: the arena is a contiguous 1-D float32 or uint8 device tensor")
+        n, sizes = len(offsets), np.asarray(sizes)
+        src = np.empty(n, dtype=SOURCE_DTYPE)
+        src["offset"], src["h"], src["w"] = np.asarray(offsets), sizes[:, 0], sizes[:, 1]
+        stream = C.c_void_p(torch.cuda.current_stream(arena.device).cuda_stream)
+        need = arena.numel() * 4
+
+        def alloc():
+            try:
+                return torch.empty(arena.numel(), dtype=torch.float32, device=arena.device)
+            except torch.cuda.OutOfMemoryError as e:
+                raise RuntimeError(f"{what}: a cubic-spline table ({need} bytes; two of them if the field holds NaN) does not fit in the HBM of "
+                                   f"{arena.device}") from e
+
+        def run(coef, indicator):
+            check(lib.biu_spline_prefilter_items(C.c_void_p(arena.data_ptr()), int(arena.dtype == torch.uint8), arena.numel(),
+                                                 C.c_void_p(coef.data_ptr()) if coef is not None else None,
+                                                 C.c_void_p(indicator.data_ptr()) if indicator is not None else None, C.c_void_p(table.data_ptr()),
+                                                 n, int(planes), src.ctypes.data_as(C.c_void_p), stream), "spline_prefilter_items")
+
+        with torch.cuda.device(arena.device):
+            coef, table = alloc(), torch.empty(n * SPLINE_ITEM_DTYPE.itemsize, dtype=torch.uint8, device=arena.device)
+            run(coef, None)
+            items = table.cpu().numpy().view(SPLINE_ITEM_DTYPE).copy()             # synchronises: the table is complete
+            indicator = None
+            if items["has_nan"].any():
+                indicator = alloc()
+                run(None, indicator)
+                torch.cuda.current_stream(arena.device).synchronize()              # the feeders read the tables on streams of their own
+        return cls(coef, indicator, table, items)
+
 
 _VOLUME_MAGIC = "biu-volumestore-1"
 
@@ -540,11 +617,15 @@ class CropFeeder:
     buffers in front of a ``ready`` event -- ``DeviceFeeder``'s slot and event hand-over,
     a failure of the feeder thread surfaces in the consumer.  No tile bytes cross PCIe after the upload.
 
+    ``spline``: ``store.spline_tables(device, augmenter.spline_fields(store))``, required by ``AugmenterF32(target_interp="cubic")`` (without
+    it that augmenter raises ``NotImplementedError`` here): "mask" fields of batches with an arbitrary-angle record are then rendered by
+    ``biu_augment_f32_crop_cubic``; the feeder uploads the item index of every patch behind the sources.
+
     ``epoch_key``: ``None`` -- the epoch (``draw_crops``' second argument) advances per ``iter()``; a number -- every ``iter()`` uses it, so the
     batches are the same every time (the Trainer's validation feeder: ``augment.VALIDATION_EPOCH``)."""
 
     def __init__(self, store: ImageStore, patch_indices: Sequence[int], batch_size: int, device, augmenter, epoch_key: Optional[int] = None,
-                 depth: int = 3, drop_last: bool = True):
+                 depth: int = 3, drop_last: bool = True, spline: Optional[Dict[str, "SplineTables"]] = None):
         self.store, self.indices, self.batch_size = store, [int(i) for i in patch_indices], int(batch_size)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -556,9 +637,16 @@ class CropFeeder:
                              "be read un-augmented")
         if augmenter.recipe != store.recipe:
             raise ValueError(f'{type(augmenter).__name__} (recipe "{augmenter.recipe}") does not draw crops out of a {type(store).__name__}')
+        self.spline = None
         if getattr(augmenter, "target_interp", "linear") == "cubic":
-            raise NotImplementedError('target_interp="cubic" on an ImageStore: the spline coefficients and the clip range of a whole item depend '
-                                      'on the item alone and belong computed once at upload, which is not implemented; use "linear"')
+            # the tables are HBM of the store's, up to twice the field's arena, shared by its feeders: the caller asks for them as for to_device
+            if spline is None:
+                raise NotImplementedError('target_interp="cubic" on an ImageStore needs the store\'s spline tables: pass '
+                                          'spline=store.spline_tables(device, augmenter.spline_fields(store)), as workflow._loaders does')
+            missing = [k for k in augmenter.spline_fields(store) if k not in spline]
+            if missing:
+                raise ValueError(f'target_interp="cubic": no spline tables for the field(s) {missing}')
+            self.spline = dict(spline)
         self.augmenter, self.epoch_key, self.epoch = augmenter, epoch_key, 0
         self.drop_last, self.depth = drop_last, max(2, depth)
         self.copy_stream = torch.cuda.Stream(device=self.device)
@@ -568,6 +656,9 @@ class CropFeeder:
         rec, src = augmenter.params_dtype.itemsize, augmenter.source_dtype.itemsize
         self._rec_bytes, self._src_bytes = batch_size * rec, batch_size * src
         small = self._rec_bytes + len(self.names) * self._src_bytes                  # records, then one block of sources per field
+        self._idx_off = small                                                          # cubic targets: then the item of every patch (int32)
+        if self.spline is not None:
+            small += batch_size * 4
         self.slots = [{"out": {k: torch.empty((batch_size, store.planes[k], *store.dim_out), dtype=torch.float32, device=self.device) for k in self.names},
                        "host": torch.empty(small, dtype=torch.uint8).pin_memory(),
                        "dev": torch.empty(small, dtype=torch.uint8, device=self.device),
@@ -593,6 +684,7 @@ class CropFeeder:
             slot["released"].set()
             slot["free"] = None
         nan_to_val = self.store.nan_to_val
+        rot_flag = getattr(self.augmenter, "rot_flag", 0)
 
         def producer():
             try:
@@ -618,12 +710,17 @@ class CropFeeder:
                     host[o:o + sources[k].nbytes] = sources[k].view(np.uint8)
                 blurs = params["blur_k"][(params["flags"] & blur_flag) != 0]
                 max_blur = int(blurs.max()) if len(blurs) else 0
+                cubic = {}
+                if self.spline is not None and bool((params["flags"] & rot_flag).any()):      # read from the records, as max_blur is
+                    host[self._idx_off:self._idx_off + 4 * nb] = self.store.locate(idx).astype(np.int32).view(np.uint8)
+                    cubic = {"item_index_dev": slot["dev"][self._idx_off:self._idx_off + 4 * nb]}
                 with torch.cuda.stream(self.copy_stream):
                     slot["dev"].copy_(slot["host"], non_blocking=True)
                     for f, k in enumerate(self.names):
                         o = self._rec_bytes + f * self._src_bytes
                         self.augmenter.launch_crop(k, self.arenas[k], slot["out"][k][:nb], slot["dev"][:self._rec_bytes],
-                                                   slot["dev"][o:o + self._src_bytes], nan_to_val, max_blur, epoch)
+                                                   slot["dev"][o:o + self._src_bytes], nan_to_val, max_blur, epoch,
+                                                   **({"spline": self.spline[k], **cubic} if cubic and k in self.spline else {}))
                     ev = torch.cuda.Event()
                     ev.record(self.copy_stream)
                 slot["ready"] = ev

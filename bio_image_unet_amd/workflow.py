@@ -108,8 +108,11 @@ def _loaders(dataset, train_data, val_data, batch_size, device, augmenter=None):
         # crops with one fixed epoch key -- fully augmented but the same every epoch, as the reference's validation patches are augmented
         # once and then fixed
         from .augment import VALIDATION_EPOCH
-        return (CropFeeder(dataset, train_data.indices, batch_size, device, augmenter),
-                CropFeeder(dataset, val_data.indices, batch_size, device, augmenter, epoch_key=VALIDATION_EPOCH))
+        # cubic-spline targets: the tables of the store's "mask" fields, built once and shared by both feeders
+        spline = (dataset.spline_tables(device, augmenter.spline_fields(dataset))
+                  if getattr(augmenter, "target_interp", "linear") == "cubic" else None)
+        return (CropFeeder(dataset, train_data.indices, batch_size, device, augmenter, spline=spline),
+                CropFeeder(dataset, val_data.indices, batch_size, device, augmenter, epoch_key=VALIDATION_EPOCH, spline=spline))
     if isinstance(dataset, TileStore) and torch.device(device).type == "cuda":
         return (DeviceFeeder(dataset, train_data.indices, batch_size, device, augmenter=augmenter),     # training only, never validation
                 DeviceFeeder(dataset, val_data.indices, batch_size, device))

@@ -817,6 +817,58 @@ int biu_augment_f32_crop(const void* arena, int arena_is_u8, unsigned long long 
                          unsigned long long seed, unsigned epoch, unsigned field_id, biu_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Cubic-spline resampling of the MASK fields of whole items: biu_spline_prefilter_f32 + biu_augment_f32_cubic with the source in an arena
+ * (above), and with the reference's exact semantics (rotate_array at order = 3, multi_output_unet/data.py:213-242): the periodic spline of
+ * the whole item, the clip range of the whole item, and NaN carried through the rotation.  What depends on the item alone -- coefficients,
+ * range, "holds a NaN" -- is computed once per store (biu_spline_prefilter_items) and read by every batch (biu_augment_f32_crop_cubic).
+ *
+ * biu_spline_prefilter_items: the tables of n_items items of ONE field's arena (arena, arena_is_u8, arena_elems, planes: as above).
+ *   items     : n_items biu_augf_source records IN HOST MEMORY (the others are device pointers): each item's element offset and extent.
+ *               Every item is checked before the first launch: one that does not lie inside the arena, or has planes h w >= 2^31 - 4,
+ *               returns a status and nothing is launched.
+ *   table     : n_items biu_spline_item on the device, 16-byte aligned; always written:
+ *                 lo, hi  : min and max of the item's loaded values over all planes, NaN aside, exact (bytes: the min and max of the bytes,
+ *                           divided by 255.0f once); an item that holds nothing but NaN gives lo = +inf, hi = -inf
+ *                 has_nan : 1 if some element of the item is NaN, else 0 (a byte arena: always 0)
+ *   coef      : arena_elems floats with the arena's layout and offsets (or null: not computed): per item and plane the coefficients of
+ *               the periodic cubic B-spline through the loaded values with NaN read as 0 -- biu_spline_prefilter_f32's definition (cut at
+ *               BIU_SPLINE_R, fp32 taps, symmetric pairs added first, outermost first, x then y); indices wrap in the item's own (h, w), as
+ *               often as a small item needs.  Elements of the arena that belong to no item are not written.
+ *   indicator : the same spline through isnan(item) as 0 / 1 (or null: not computed).  Written only for the items whose has_nan is 1; the
+ *               others' elements are left as they are and are never read by the gather.  A caller reads the table after a first call with
+ *               indicator = null and needs no indicator arena at all if no item holds a NaN.  At least one of coef and indicator is given.
+ * Up to three launches per item on `stream` (range, value prefilter, indicator prefilter); no atomics, nothing cleared beforehand.
+ *
+ * biu_augment_f32_crop_cubic renders dst [n, planes, th, tw] of one MASK field; params, sources, nan_to_val and the validation of a
+ * sample's source are biu_augment_f32_crop's.  item_index [n] (device, int32) names the row of each sample's item in `table`; a sample
+ * whose index is outside 0 .. n_items - 1 is rendered as nan_to_val, as is one whose source does not lie inside the arena.
+ *   records without BIU_AUGF_ROT : biu_augment_f32_crop's MASK output bit for bit (nearest gather from the arena, NaN -> nan_to_val);
+ *                                  coef, indicator and the table are not read.
+ *   records with BIU_AUGF_ROT    : biu_augment_f32_cubic's gather at the crop's one affine map m: fp64 coordinate and fraction, the four
+ *                                  B-spline weights per axis in fp64 rounded once, v = the sum of 4 x 4 wrapped coefficients in fp32, rows
+ *                                  first.  If the item's has_nan is set and indicator is not null, w_nan = the same sum over the indicator
+ *                                  coefficients, and the output is nan_to_val if w_nan >= 0.5 (scipy rounds the rotated uint8 NaN mask half
+ *                                  up before the reference's > 0.5 test).  Otherwise the output is v, clipped to the item's [lo, hi] iff
+ *                                  lo >= 0 and hi <= 1.
+ * dst never holds NaN; an item of nothing but NaN renders nan_to_val everywhere (its indicator coefficients sum to 1).
+ * Equivalence law: NaN-free items of exactly (th, tw) with the same record bytes give biu_augment_f32_cubic's bytes.
+ *
+ * Both: null pointers (but a null coef or indicator where it is optional), buffers that overlap (the arena, coef, indicator and the table
+ * among each other; dst with any input), unaligned pointers, non-positive extents, an output of 2^31 - 4 elements or more and a NaN
+ * nan_to_val return a status and launch nothing.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct biu_spline_item {
+    float lo, hi;             /* the item's value range over all planes, NaN aside */
+    uint32_t has_nan;         /* 1: some element is NaN */
+    uint32_t reserved;        /* written as 0 */
+} biu_spline_item;            /* 16 bytes */
+int biu_spline_prefilter_items(const void* arena, int arena_is_u8, unsigned long long arena_elems, float* coef, float* indicator,
+                               biu_spline_item* table, int n_items, int planes, const biu_augf_source* items, biu_stream stream);
+int biu_augment_f32_crop_cubic(const void* arena, int arena_is_u8, unsigned long long arena_elems, const float* coef, const float* indicator,
+                               const biu_spline_item* table, int n_items, const int32_t* item_index, float* dst, int n, int planes, int th,
+                               int tw, const biu_augf_params* params, const biu_augf_source* sources, float nan_to_val, biu_stream stream);
+
+/* ------------------------------------------------------------------------------------------------
  * On-the-fly training augmentation of float volumes: the 3-D multi-output family (multi_output_unet3d/data.py:152-178, which the
  * reference runs offline through albumentations).  One launch per field per batch; the records are biu_augf_params unchanged.
  *

@@ -1,7 +1,7 @@
 """What rendering training patches straight from whole items costs (feed.CropFeeder, biu_augment_f32_crop) against augmenting stored tiles
 (feed.DeviceFeeder + AugmenterF32, biu_augment_f32), and whether the feeder keeps ahead of the training step.
 
-    python tools/bench_augment_crop.py [--rounds 6]
+    python tools/bench_augment_crop.py [feeders | cubic] [--rounds 6]
 
 feeders : an epoch of CropFeeder over an ImageStore of 8 items (512 x 640 and 640 x 512; image u8; mask, distance, orientation f32 with NaN
           holes; aug_factor 2, i.e. 80 patches of 256^2) and an epoch of DeviceFeeder + AugmenterF32 over a TileStore with the same number of
@@ -9,6 +9,10 @@ feeders : an epoch of CropFeeder over an ImageStore of 8 items (512 x 640 and 64
           batch as median (min .. max) over --rounds epochs (a first epoch warms up and is dropped).
 step    : the synchronised TrainerMo2d step (MultiOutputNestedUNet(n_filter=32), batch 4, 256^2, a mask, a distance and an orientation head)
           fed by the CropFeeder, in the same process: what the feeder has to keep ahead of.
+cubic   : what AugmenterF32(target_interp="cubic") costs on the same ImageStore.  The table build (ImageStore.spline_tables' work, once per
+          store and device: SplineTables.build per "mask" field, synchronised; the first build and --rounds repeats), then an epoch of the
+          CropFeeder with the linear and with the cubic augmenter, alternating as above, then the synchronised TrainerMo2d step fed by the
+          cubic CropFeeder.
 """
 import argparse
 import os
@@ -24,7 +28,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from bio_image_unet_amd import augment as A  # noqa: E402
-from bio_image_unet_amd.feed import CropFeeder, DeviceFeeder, ImageStore, TileStore  # noqa: E402
+from bio_image_unet_amd.feed import CropFeeder, DeviceFeeder, ImageStore, SplineTables, TileStore  # noqa: E402
 
 HEADS = {"mask": {"channels": 1, "activation": "sigmoid", "loss": "BCEDiceLoss", "weight": 1.0},
          "distance": {"channels": 1, "activation": "relu", "loss": "WeightedDistanceGradientLoss", "weight": 0.25},
@@ -74,6 +78,7 @@ def _spread(v):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("mode", nargs="?", default="feeders", choices=["feeders", "cubic"])
     ap.add_argument("--rounds", type=int, default=6)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU"
@@ -83,10 +88,29 @@ def main():
     print(f"box: {torch.cuda.get_device_name(0)} ({torch.cuda.get_device_properties(0).gcnArchName}), torch {torch.__version__}, HIP {torch.version.hip}")
     with tempfile.TemporaryDirectory() as tmp:
         whole = _image_store(tmp)
-        tiles = _tile_store(tmp, len(whole))
         idx = list(range(len(whole)))
-        feeders = {"CropFeeder, ImageStore": CropFeeder(whole, idx, 4, "cuda", A.AugmenterF32.from_store(whole, seed=1)),
-                   "DeviceFeeder + AugmenterF32, TileStore": DeviceFeeder(tiles, idx, 4, "cuda", augmenter=A.AugmenterF32.from_store(tiles, seed=1))}
+        augment, first = None, "CropFeeder, ImageStore"
+        feeders = {first: CropFeeder(whole, idx, 4, "cuda", A.AugmenterF32.from_store(whole, seed=1))}
+        if a.mode == "cubic":
+            augment, first = A.AugmenterF32.from_store(whole, seed=1, target_interp="cubic"), "CropFeeder, cubic targets"
+            arenas = whole.to_device("cuda")[0]
+            names = augment.spline_fields(whole)
+            build = []
+            for rnd in range(a.rounds + 1):                      # the first build is reported on its own: it is the one a Trainer pays
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                tabs = {k: SplineTables.build(arenas[k], whole.planes[k], whole.offsets[k], whole.sizes) for k in names}
+                torch.cuda.synchronize()
+                build.append((time.perf_counter() - t0) * 1e3)
+            print(f"table build, {whole.n_items} items of 512 x 640, fields {names}: first {build[0]:.3f} ms, then {_spread(build[1:])} ms; "
+                  + ", ".join(f"{k}: {t.nbytes} bytes{'' if t.indicator is None else ' with the indicator'}" for k, t in tabs.items())
+                  + f"; the field arenas: {', '.join(str(arenas[k].numel() * arenas[k].element_size()) for k in names)} bytes")
+            del tabs
+            feeders = {"CropFeeder, linear targets": feeders.pop("CropFeeder, ImageStore"),
+                       first: CropFeeder(whole, idx, 4, "cuda", augment, spline=whole.spline_tables("cuda", names))}
+        else:
+            tiles = _tile_store(tmp, len(whole))
+            feeders["DeviceFeeder + AugmenterF32, TileStore"] = DeviceFeeder(tiles, idx, 4, "cuda", augmenter=A.AugmenterF32.from_store(tiles, seed=1))
         times = {k: [] for k in feeders}
         for rnd in range(a.rounds + 1):                          # round 0 warms up and is dropped
             for k, fd in feeders.items():
@@ -104,7 +128,7 @@ def main():
             print(f"  {k:40s} {_spread(v)}")
         torch.manual_seed(0)
         tr = TrainerMo2d(whole, 1, network=MultiOutputNestedUNet, batch_size=4, output_heads=HEADS, n_filter=32, val_split=0.2,
-                         save_dir=os.path.join(tmp, "out"), device="cuda")
+                         save_dir=os.path.join(tmp, "out"), device="cuda", augment=augment)
         steps = []
         for rnd in range(a.rounds + 1):
             torch.cuda.synchronize()
@@ -121,9 +145,9 @@ def main():
                     steps.append((t1 - t0) * 1e3)
                 t0 = t1
         steps.sort()
-        print(f"TrainerMo2d MultiOutputNestedUNet n_filter=32 batch 4 (256, 256) fed by the CropFeeder: synchronised step time, ms, {len(steps)} steps")
+        print(f"TrainerMo2d MultiOutputNestedUNet n_filter=32 batch 4 (256, 256) fed by the {first}: synchronised step time, ms, {len(steps)} steps")
         print(f"  median {statistics.median(steps):8.3f}   p10 {steps[len(steps) // 10]:8.3f}   p90 {steps[(9 * len(steps)) // 10]:8.3f}")
-        crop = statistics.median(times["CropFeeder, ImageStore"])
+        crop = statistics.median(times[first])
         print(f"the feeder needs {crop:.3f} ms per batch, the step {statistics.median(steps):.3f} ms: "
               f"{'the feeder keeps ahead of the step' if crop < statistics.median(steps) else 'THE FEEDER IS SLOWER THAN THE STEP'}")
 

@@ -96,6 +96,8 @@ SIGNATURES = {
     "biu_conv_bwd_data_bnred": (_I, [_A, _P, _P, _I, _I, _I, _I, _A, _A, _P, _P, _P, _P, _P, _P, _Z, C.POINTER(C.c_int), _P, _Z, _I, _P]),
     "biu_convt_bwd_data_bnred": (_I, [_A, _P, _P, _I, _A, _A, _P, _P, _P, _P, _P, _P, _Z, C.POINTER(C.c_int), _I, _P]),
     "biu_conv_bwd_weight_workspace": (_Z, [_I, _I, _I, _I, _I, _I]),
+    "biu_conv_first_ok": (_I, [_A, _A, _I, _I, _I, _I, _I]),
+    "biu_conv_first_workspace": (_Z, [_I, _I, _I, _I]),
     "biu_conv_bwd_weight": (_I, [_A, _X, _A, _I, _I, _I, _I, _P, _P, _P, _Z, _I, _P]),
     "biu_conv_bwd_weight_bn": (_I, [_A, _X, _A, _A, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _Z, _I, _P]),
     "biu_conv_bwd_weight_bn_rank1_ok": (_I, [_A, _A, _A, _I, _I, _I, _I, _I, _I]),

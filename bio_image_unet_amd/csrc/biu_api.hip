@@ -9,7 +9,7 @@
 
 // Every token BIU_DISABLE takes: INTEGRATION.md's table (sidechain, prepack, capturefork and headrank1 are read by the Python side alone)
 static const char* const kOffTokens[] = {
-    "conv_fwd", "conv_dgrad", "conv_wgrad", "convt_fwd", "convt_dgrad", "convt_wgrad", "convt_all", "c1", "c1_mfma", "cat",
+    "conv_fwd", "conv_dgrad", "conv_wgrad", "convt_fwd", "convt_dgrad", "convt_wgrad", "convt_all", "c1", "c1_mfma", "cn", "cat",
     "fused_stats", "wgrad_bn", "dgrad_bnred", "pool_pair", "pool_pipe", "pool_bnred", "head_bnred", "ksplit", "m16", "m16x2", "rr16",
     "wroll", "wroll16", "wroll2d", "upconv", "foldt", "foldall", "foldck8", "foldgemm", "croll", "froll", "prepack", "wsplitbn",
     "capturefork", "sidechain", "headrank1",
@@ -81,7 +81,7 @@ bool biu_off(const char* token) {
     return i >= 0 && ((biu_env().off >> i) & 1);
 }
 
-// The any-shape kernels are a correctness tier: a large layer landing on them (odd channel counts, dilation != 1, a sample
+// The any-shape kernels are a correctness tier: a large layer landing on them (odd channel counts above 4, dilation != 1, a sample
 // beyond the 4 GB descriptor range, an unaligned slice) runs orders of magnitude below the MFMA path.  Say so, once per op.
 static void warn_slow_path(const char* op, const biu_act* x, const biu_act* y, int taps) {
     const double macs = (double)nvox(y) * x->c * y->c * taps;
@@ -90,7 +90,7 @@ static void warn_slow_path(const char* op, const biu_act* x, const biu_act* y, i
     if (shown++ < 8)
         fprintf(stderr, "[biu] %s: %d->%d channels on %lld voxels takes the any-shape kernel (%.1f GMAC): expect it to be slow; "
                         "the MFMA path needs channel counts that are multiples of 8 (>= 16), dilation 1, 16-byte aligned slices "
-                        "and samples under 4 GB\n", op, x->c, y->c, (long long)nvox(y), macs * 1e-9);
+                        "and samples under 4 GB; 1 to 4 input channels take the first-layer kernels\n", op, x->c, y->c, (long long)nvox(y), macs * 1e-9);
 }
 
 static bool conv_args_ok(const biu_act* x, const biu_act* y, int kd, int kh, int kw, int dil) {
@@ -264,10 +264,25 @@ extern "C" int biu_convt_bwd_data_bnred(const biu_act* dy, const float* w, const
 
 extern "C" size_t biu_conv_bwd_weight_workspace(int cin, int cout, int kd, int kh, int kw, int dtype) {
     if (cin == 1 && kh == 3 && kw == 3) {
-        const size_t a = biu_c1_wgrad_workspace(cout, kd), b = biu_c1m_wgrad_workspace(cout, kd);
+        const size_t a = biu_c1_wgrad_workspace(1, cout, kd), b = biu_c1m_wgrad_workspace(1, cout, kd);
         return a > b ? a : b;
     }
-    return biu_mfma_wgrad_workspace(cin, cout, kd, kh, kw, dtype);
+    return biu_mfma_wgrad_workspace(cin, cout, kd, kh, kw, dtype);      // (0 for 2..4 input channels: biu_conv_first_workspace)
+}
+
+// First layers (1 to 4 input channels, 3x3(x3), dilation 1): does a first-layer kernel serve this one, and weight-gradient scratch that is
+// enough for whichever of them will.  Host arithmetic on the descriptors only.
+extern "C" int biu_conv_first_ok(const biu_act* x, const biu_act* y, int kd, int kh, int kw, int dilation, int dtype) {
+    if (!x || !y || (dtype != BIU_BF16 && dtype != BIU_F32) || biu_off("c1")) return 0;
+    return (biu_c1m_ok(x, y, kd, kh, kw, dilation, dtype) || biu_c1_conv_ok(x, y, kd, kh, kw, dilation, dtype)) ? 1 : 0;
+}
+extern "C" size_t biu_conv_first_workspace(int cin, int cout, int kd, int dtype) {
+    if (cin < 1 || cin > 4 || (kd != 1 && kd != 3) || (dtype != BIU_BF16 && dtype != BIU_F32) || biu_off("c1") || (cin > 1 && biu_off("cn"))) return 0;
+    if (cout < 8 || cout % 8 != 0) return 0;
+    // the larger of the two forms' scratch, as biu_conv_bwd_weight_workspace does for one channel: a layer the matrix-core form refuses for its
+    // alignment still finds enough for the vector-ALU one
+    const size_t a = biu_c1_wgrad_workspace(cin, cout, kd), b = biu_c1m_wgrad_workspace(cin, cout, kd);
+    return a > b ? a : b;
 }
 
 extern "C" int biu_conv_bwd_weight(const biu_act* x, const biu_xform* xf, const biu_act* dy, int kd, int kh, int kw,
@@ -275,12 +290,12 @@ extern "C" int biu_conv_bwd_weight(const biu_act* x, const biu_xform* xf, const 
                                    biu_stream stream) {
     BIU_REQUIRE(conv_args_ok(x, dy, kd, kh, kw, dilation), BIU_ERR_SHAPE, "conv_bwd_weight: x/dy extents differ");
     BIU_REQUIRE(dw, BIU_ERR_SHAPE, "conv_bwd_weight: null dw");
-    if (!biu_off("c1") && biu_c1m_ok(x, dy, kd, kh, kw, dilation, dtype) && ws && ws_bytes >= biu_c1m_wgrad_workspace(dy->c, kd)) {
+    if (!biu_off("c1") && biu_c1m_ok(x, dy, kd, kh, kw, dilation, dtype) && ws && ws_bytes >= biu_c1m_wgrad_workspace(x->c, dy->c, kd)) {
         int rc = biu_c1m_wgrad(x, xf, dy, nullptr, kd, dw, ws, ws_bytes, (hipStream_t)stream);
         if (rc == BIU_OK && dbias) rc = biu_chan_sum(dy, dbias, dtype, (hipStream_t)stream);
         return rc;
     }
-    if (!biu_off("c1") && biu_c1_conv_ok(x, dy, kd, kh, kw, dilation, dtype) && ws && ws_bytes >= biu_c1_wgrad_workspace(dy->c, kd)) {
+    if (!biu_off("c1") && biu_c1_conv_ok(x, dy, kd, kh, kw, dilation, dtype) && ws && ws_bytes >= biu_c1_wgrad_workspace(x->c, dy->c, kd)) {
         int rc = biu_c1_conv_wgrad(x, xf, dy, kd, dw, ws, ws_bytes, dtype, (hipStream_t)stream);
         if (rc == BIU_OK && dbias) rc = biu_chan_sum(dy, dbias, dtype, (hipStream_t)stream);
         return rc;
@@ -307,7 +322,7 @@ extern "C" int biu_conv_bwd_weight_bn(const biu_act* x, const biu_xform* xf, con
     const bool yok = ((uintptr_t)y->p % 16) == 0 && ((size_t)y->pitch * es) % 16 == 0 &&
                      (i64)y->d * y->h * y->w * y->pitch * (i64)es < (1LL << 32) - 65536;
     if (!biu_off("c1") && !biu_off("wgrad_bn") && yok && biu_c1m_ok(x, da, kd, kh, kw, dilation, dtype) && ws &&
-        ws_bytes >= biu_c1m_wgrad_workspace(da->c, kd)) {
+        ws_bytes >= biu_c1m_wgrad_workspace(x->c, da->c, kd)) {
         // first layer: BatchNorm backward in the dy staging of the im2col weight gradient (da -> dy written back in the same pass)
         BnBwdFuse bn{y, scale, shift, slope, coefA, coefB, coefC};
         return biu_c1m_wgrad(x, xf, da, &bn, kd, dw, ws, ws_bytes, (hipStream_t)stream);

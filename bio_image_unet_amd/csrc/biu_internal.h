@@ -134,7 +134,7 @@ int biu_mfma_convt_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* d
 // biu_special.hip
 bool biu_c1_conv_ok(const biu_act* x, const biu_act* y, int kd, int kh, int kw, int dil, int dtype);
 int biu_c1_conv_fwd(const biu_act* x, const biu_xform* xf, const float* w, const float* bias, int kd, const biu_act* y, int dtype, hipStream_t st);
-size_t biu_c1_wgrad_workspace(int cout, int kd);
+size_t biu_c1_wgrad_workspace(int cin, int cout, int kd);
 int biu_c1_conv_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* dy, int kd, float* dw, void* ws, size_t ws_bytes, int dtype, hipStream_t st);
 bool biu_vec_reduce_ok(const biu_act* a, int dtype);
 int biu_bn_stats_vec(const biu_act* y, float* partial, int* nblk_out, int dtype, hipStream_t st);
@@ -172,6 +172,6 @@ int biu_convt_all_dgrad(const biu_act* dy, const void* packed, int kd, const biu
 bool biu_c1m_ok(const biu_act* x, const biu_act* y, int kd, int kh, int kw, int dil, int dtype);
 int biu_c1m_fwd_rows(const biu_act* y, int kd);
 int biu_c1m_fwd(const biu_act* x, const biu_xform* xf, const float* w, const float* bias, int kd, const biu_act* y, float* bn_partial, hipStream_t st);
-size_t biu_c1m_wgrad_workspace(int cout, int kd);
+size_t biu_c1m_wgrad_workspace(int cin, int cout, int kd);
 int biu_c1m_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* da, const BnBwdFuse* bn, int kd, float* dw, void* ws, size_t ws_bytes,
                   hipStream_t st);

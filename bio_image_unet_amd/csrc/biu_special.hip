@@ -1,5 +1,6 @@
 // Bandwidth-bound special cases of the hot path, written for the shapes the real networks hit:
-//   * first layer (Cin = 1): 3x3(x3) conv forward and weight gradient on the vector ALUs (no MFMA: K = 27)
+//   * first layer (Cin = 1 .. 4): 3x3(x3) conv forward and weight gradient on the vector ALUs in fp32 FMAs (fp32 tensors, and bf16 ones
+//     whose channel count the matrix-core form of biu_c1.hip does not take)
 //   * 1x1 head backward fused: dx, dW and dbias in ONE pass over (x, dlogits)
 //   * per-channel two-term reductions (BatchNorm statistics, BatchNorm backward sums, channel sums) with 16-byte
 //     loads and deterministic per-block partials
@@ -29,44 +30,47 @@ __device__ __forceinline__ Vox4 unvox4(i64 v, int D, int H, int W) {
 }
 
 // =====================================================================================================================
-// Cin = 1 convolution forward:  y[v, co] = b[co] + sum_tap T(x)[v + off(tap)] * w[co][tap]
+// First-layer convolution forward (CIN = 1 .. 4):  y[v, co] = b[co] + sum_ci sum_tap T(x)[v + off(tap), ci] * w[co][ci][tap]
 // One thread per voxel, all COUT channels in registers, weights broadcast from LDS.  Writes COUT*sizeof(T) contiguous
 // bytes per lane.  VALU-bound (27*COUT FMA per voxel) at ~0.2 ms for 8.4 M voxels x 16 channels.
 // =====================================================================================================================
-template <typename T, int COUT, int KD>
+template <typename T, int COUT, int KD, int CIN = 1>
 __global__ __launch_bounds__(TPB) void k_conv_c1_fwd(DAct x, DXf xf, const float* __restrict__ w, const float* __restrict__ bias,
                                                      DAct y, int co0) {
-    constexpr int TAPS = KD * 9;
-    __shared__ float ws[TAPS * COUT + COUT];
-    for (int i = threadIdx.x; i < TAPS * COUT; i += TPB) {
-        const int tap = i / COUT, co = i % COUT;
-        ws[i] = w[(i64)(co0 + co) * TAPS + tap];                   // PyTorch (Cout, 1, taps)
+    constexpr int TAPS = KD * 9, CT = CIN * TAPS;                 // (ci, tap) pairs: the reduction dimension
+    __shared__ float ws[CT * COUT + COUT];
+    for (int i = threadIdx.x; i < CT * COUT; i += TPB) {
+        const int ct = i / COUT, co = i % COUT;
+        ws[i] = w[(i64)(co0 + co) * CT + ct];                      // PyTorch (Cout, Cin, taps)
     }
-    for (int i = threadIdx.x; i < COUT; i += TPB) ws[TAPS * COUT + i] = bias ? bias[co0 + i] : 0.f;
+    for (int i = threadIdx.x; i < COUT; i += TPB) ws[CT * COUT + i] = bias ? bias[co0 + i] : 0.f;
     __syncthreads();
-    const float s = xf.scale ? xf.scale[0] : 1.f, b = xf.shift ? xf.shift[0] : 0.f, sl = xf.slope ? xf.slope[0] : 1.f;
     const i64 total = (i64)y.n * y.d * y.h * y.w;
     for (i64 v = (i64)blockIdx.x * TPB + threadIdx.x; v < total; v += (i64)gridDim.x * TPB) {
         const Vox4 p = unvox4(v, y.d, y.h, y.w);
         float acc[COUT];
 #pragma unroll
-        for (int c = 0; c < COUT; ++c) acc[c] = ws[TAPS * COUT + c];
+        for (int c = 0; c < COUT; ++c) acc[c] = ws[CT * COUT + c];
 #pragma unroll 1
-        for (int a = 0; a < KD; ++a) {
-            const int id = p.d + a - KD / 2;
+        for (int ci = 0; ci < CIN; ++ci) {
+            const float s = xf.scale ? xf.scale[ci] : 1.f, b = xf.shift ? xf.shift[ci] : 0.f, sl = xf.slope ? xf.slope[ci] : 1.f;
 #pragma unroll 1
-            for (int bb = 0; bb < 3; ++bb) {
-                const int ih = p.h + bb - 1;
+            for (int a = 0; a < KD; ++a) {
+                const int id = p.d + a - KD / 2;
+#pragma unroll 1
+                for (int bb = 0; bb < 3; ++bb) {
+                    const int ih = p.h + bb - 1;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int iw = p.w + c - 1;
-                    const bool ok = id >= 0 && id < x.d && ih >= 0 && ih < x.h && iw >= 0 && iw < x.w;
-                    const i64 iv = ok ? (((i64)p.n * x.d + id) * x.h + ih) * x.w + iw : 0;
-                    const float t = fmaf(s, to_f(((const T*)x.p)[iv * x.pitch]), b);
-                    const float xv = ok ? (t > 0.f ? t : sl * t) : 0.f;
-                    const float* wr = ws + ((a * 3 + bb) * 3 + c) * COUT;
+                    for (int c = 0; c < 3; ++c) {
+                        const int iw = p.w + c - 1;
+                        const bool ok = id >= 0 && id < x.d && ih >= 0 && ih < x.h && iw >= 0 && iw < x.w;
+                        const i64 iv = ok ? (((i64)p.n * x.d + id) * x.h + ih) * x.w + iw : 0;
+                        const float t = fmaf(s, to_f(((const T*)x.p)[iv * x.pitch + ci]), b);
+                        const float xv = ok ? (t > 0.f ? t : sl * t) : 0.f;
+                        const float* wr = ws + (ci * TAPS + (a * 3 + bb) * 3 + c) * COUT;
 #pragma unroll
-                    for (int co = 0; co < COUT; ++co) acc[co] = fmaf(xv, wr[co], acc[co]);
+                        for (int co = 0; co < COUT; ++co) acc[co] = fmaf(xv, wr[co], acc[co]);
+                    }
                 }
             }
         }
@@ -83,15 +87,19 @@ __global__ __launch_bounds__(TPB) void k_conv_c1_fwd(DAct x, DXf xf, const float
 }
 
 // =====================================================================================================================
-// Cin = 1 weight gradient:  dw[co][tap] = sum_v T(x)[v + off(tap)] * dy[v][co]
-// Block = NW waves; wave q owns taps [q*TPW, q*TPW + TPW); a lane walks voxels and keeps TPW x COUT partial sums.
+// First-layer weight gradient (CIN = 1 .. 4):  dw[co][ci][tap] = sum_v T(x)[v + off(tap), ci] * dy[v][co]
+// Block = NW waves; the (ci, tap) pairs are the rows of dw[co]: wave q owns rows [q*TPW, q*TPW + TPW) of CIN x TAPS; a lane walks voxels and
+// keeps TPW x COUT partial sums.  One pass over dy whatever CIN is: more input channels mean more waves (up to 16), and where those leave
+// fewer registers per lane the host launches 8-channel pieces instead of 16-channel ones (c1_wgrad_t).
 // Per-block partials -> fp64 merge (deterministic).
 // =====================================================================================================================
-template <typename T, int COUT, int KD, int TPW>
-__global__ __launch_bounds__(576) void k_conv_c1_wgrad(DAct x, DXf xf, DAct dy, int co0, float* __restrict__ partial /* [nblk][TAPS*COUT] */) {
-    constexpr int TAPS = KD * 9;
+template <typename T, int COUT, int KD, int TPW, int CIN = 1>
+__global__ __launch_bounds__(CIN == 1 ? 576 : 64 * ((CIN * KD * 9 + TPW - 1) / TPW))
+void k_conv_c1_wgrad(DAct x, DXf xf, DAct dy, int co0, float* __restrict__ partial /* [nblk][CIN*TAPS*COUT] */) {
+    constexpr int TAPS = KD * 9, NCT = CIN * TAPS;
     constexpr int G = 16 / sizeof(T);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // (several channels: the wave index is made scalar, so that the rows' channels, taps and transforms live in scalar registers)
+    const int lane = threadIdx.x & 63, wave = CIN == 1 ? (int)(threadIdx.x >> 6) : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int tap0 = wave * TPW;
     float acc[TPW][COUT];
 #pragma unroll
@@ -99,6 +107,14 @@ __global__ __launch_bounds__(576) void k_conv_c1_wgrad(DAct x, DXf xf, DAct dy, 
 #pragma unroll
         for (int c = 0; c < COUT; ++c) acc[t][c] = 0.f;
     const float s = xf.scale ? xf.scale[0] : 1.f, b = xf.shift ? xf.shift[0] : 0.f, sl = xf.slope ? xf.slope[0] : 1.f;
+    float sN[TPW], bN[TPW], slN[TPW];                            // several channels: the transform of each row's input channel (scalar registers)
+    if (CIN > 1) {
+#pragma unroll
+        for (int t = 0; t < TPW; ++t) {
+            const int ci = min(tap0 + t, NCT - 1) / TAPS;
+            sN[t] = xf.scale ? xf.scale[ci] : 1.f; bN[t] = xf.shift ? xf.shift[ci] : 0.f; slN[t] = xf.slope ? xf.slope[ci] : 1.f;
+        }
+    }
     const i64 total = (i64)dy.n * dy.d * dy.h * dy.w;
     for (i64 v = (i64)blockIdx.x * 64 + lane; v < total; v += (i64)gridDim.x * 64) {
         const Vox4 p = unvox4(v, dy.d, dy.h, dy.w);
@@ -112,14 +128,21 @@ __global__ __launch_bounds__(576) void k_conv_c1_wgrad(DAct x, DXf xf, DAct dy, 
         }
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
-            const int tap = tap0 + t;
-            if (tap < TAPS) {
+            const int ct = tap0 + t;
+            if (ct < NCT) {
+                const int ci = CIN == 1 ? 0 : ct / TAPS, tap = ct - ci * TAPS;
                 const int a = tap / 9, bb = (tap / 3) % 3, c = tap % 3;
                 const int id = p.d + a - KD / 2, ih = p.h + bb - 1, iw = p.w + c - 1;
                 const bool ok = id >= 0 && id < x.d && ih >= 0 && ih < x.h && iw >= 0 && iw < x.w;
                 const i64 iv = ok ? (((i64)p.n * x.d + id) * x.h + ih) * x.w + iw : 0;
-                const float tt = fmaf(s, to_f(((const T*)x.p)[iv * x.pitch]), b);
-                const float xv = ok ? (tt > 0.f ? tt : sl * tt) : 0.f;
+                const float tt = fmaf(CIN == 1 ? s : sN[t], to_f(((const T*)x.p)[iv * x.pitch + ci]), CIN == 1 ? b : bN[t]);
+                float xv;
+                if (CIN == 1) {
+                    xv = ok ? (tt > 0.f ? tt : sl * tt) : 0.f;
+                } else {
+                    const float neg = slN[t] * tt;
+                    xv = ok ? (tt > 0.f ? tt : neg) : 0.f;
+                }
 #pragma unroll
                 for (int co = 0; co < COUT; ++co) acc[t][co] = fmaf(xv, g[co], acc[t][co]);
             }
@@ -127,16 +150,16 @@ __global__ __launch_bounds__(576) void k_conv_c1_wgrad(DAct x, DXf xf, DAct dy, 
     }
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
-        const int tap = tap0 + t;
+        const int ct = tap0 + t;
 #pragma unroll
         for (int co = 0; co < COUT; ++co) {
             const float r = wave_sum(acc[t][co]);
-            if (lane == 0 && tap < TAPS) partial[(i64)blockIdx.x * (TAPS * COUT) + tap * COUT + co] = r;
+            if (lane == 0 && ct < NCT) partial[(i64)blockIdx.x * (NCT * COUT) + ct * COUT + co] = r;
         }
     }
 }
 
-// out[co0 + co][tap] (+ layout cout x taps) = sum_b partial[b][tap*COUT + co]
+// out[co0 + co][tap] (+ layout cout x taps) = sum_b partial[b][tap*COUT + co]   (`taps` = Cin x taps for several input channels)
 __global__ void k_c1_wgrad_finalize(const float* __restrict__ partial, int nblk, int taps, int cout_chunk, int co0, float* __restrict__ dw) {
     __shared__ double red[TPB];
     const int o = blockIdx.x;             // tap * cout_chunk + co
@@ -156,18 +179,17 @@ __global__ void k_c1_wgrad_finalize(const float* __restrict__ partial, int nblk,
 
 // ---- 4 voxels per thread (consecutive along W): every LDS weight read (4 channels, 16 B, broadcast) feeds 16 FMAs,
 //      and each input row of 6 values serves 3 taps x 4 voxels.  Needs W % 4 == 0.
-template <typename T, int COUT, int KD>
+template <typename T, int COUT, int KD, int CIN = 1>
 __global__ __launch_bounds__(TPB) void k_conv_c1_fwd4(DAct x, DXf xf, const float* __restrict__ w, const float* __restrict__ bias,
                                                       DAct y, int co0) {
-    constexpr int TAPS = KD * 9;
-    __shared__ __attribute__((aligned(16))) float ws[TAPS * COUT + COUT];
-    for (int i = threadIdx.x; i < TAPS * COUT; i += TPB) {
-        const int tap = i / COUT, co = i % COUT;
-        ws[i] = w[(i64)(co0 + co) * TAPS + tap];
+    constexpr int TAPS = KD * 9, CT = CIN * TAPS;
+    __shared__ __attribute__((aligned(16))) float ws[CT * COUT + COUT];
+    for (int i = threadIdx.x; i < CT * COUT; i += TPB) {
+        const int ct = i / COUT, co = i % COUT;
+        ws[i] = w[(i64)(co0 + co) * CT + ct];
     }
-    for (int i = threadIdx.x; i < COUT; i += TPB) ws[TAPS * COUT + i] = bias ? bias[co0 + i] : 0.f;
+    for (int i = threadIdx.x; i < COUT; i += TPB) ws[CT * COUT + i] = bias ? bias[co0 + i] : 0.f;
     __syncthreads();
-    const float s = xf.scale ? xf.scale[0] : 1.f, b = xf.shift ? xf.shift[0] : 0.f, sl = xf.slope ? xf.slope[0] : 1.f;
     const unsigned W4 = (unsigned)y.w / 4u;          // 32-bit index arithmetic (nvox < 2^31, checked on the host)
     const unsigned total = (unsigned)y.n * (unsigned)y.d * (unsigned)y.h * W4;
     for (unsigned gidx = blockIdx.x * (unsigned)TPB + threadIdx.x; gidx < total; gidx += gridDim.x * (unsigned)TPB) {
@@ -180,9 +202,11 @@ __global__ __launch_bounds__(TPB) void k_conv_c1_fwd4(DAct x, DXf xf, const floa
 #pragma unroll
         for (int vx = 0; vx < 4; ++vx)
 #pragma unroll
-            for (int c = 0; c < COUT; ++c) acc[vx][c] = ws[TAPS * COUT + c];
+            for (int c = 0; c < COUT; ++c) acc[vx][c] = ws[CT * COUT + c];
 #pragma unroll 1
-        for (int a = 0; a < KD; ++a) {        // rolled: a fully unrolled 27-tap body spills ~2 KB per lane
+        for (int ca = 0; ca < CIN * KD; ++ca) {        // (ci, a) rolled: a fully unrolled 27-tap body spills ~2 KB per lane
+            const int ci = ca / KD, a = ca % KD;
+            const float s = xf.scale ? xf.scale[ci] : 1.f, b = xf.shift ? xf.shift[ci] : 0.f, sl = xf.slope ? xf.slope[ci] : 1.f;
             const int id = pdd + a - KD / 2;
 #pragma unroll 1
             for (int bb = 0; bb < 3; ++bb) {
@@ -195,12 +219,12 @@ __global__ __launch_bounds__(TPB) void k_conv_c1_fwd4(DAct x, DXf xf, const floa
                     const int iw = w0 - 1 + k;
                     // branch-free: a clamped address and a select keep the six loads of a row in flight together
                     const bool ok = rowok && iw >= 0 && iw < x.w;
-                    const float tt = fmaf(s, to_f(((const T*)x.p)[ok ? (i64)(rowbase + (unsigned)iw) * x.pitch : 0]), b);
+                    const float tt = fmaf(s, to_f(((const T*)x.p)[ok ? (i64)(rowbase + (unsigned)iw) * x.pitch + ci : 0]), b);
                     xr[k] = ok ? (tt > 0.f ? tt : sl * tt) : 0.f;
                 }
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const float4* wr = (const float4*)(ws + ((a * 3 + bb) * 3 + c) * COUT);
+                    const float4* wr = (const float4*)(ws + (ci * TAPS + (a * 3 + bb) * 3 + c) * COUT);
 #pragma unroll
                     for (int c4 = 0; c4 < COUT / 4; ++c4) {
                         const float4 wv = wr[c4];
@@ -233,11 +257,12 @@ __global__ __launch_bounds__(TPB) void k_conv_c1_fwd4(DAct x, DXf xf, const floa
 }
 
 // weight gradient, 4 voxels per lane: wave q owns taps [q*TPW, ...); acc[t][co] += sum_vx x[vx + tap] * dy[vx][co]
-template <typename T, int COUT, int KD, int TPW>
-__global__ __launch_bounds__(64 * ((KD * 9 + TPW - 1) / TPW)) void k_conv_c1_wgrad4(DAct x, DXf xf, DAct dy, int co0, float* __restrict__ partial) {
-    constexpr int TAPS = KD * 9;
+template <typename T, int COUT, int KD, int TPW, int CIN = 1>
+__global__ __launch_bounds__(64 * ((CIN * KD * 9 + TPW - 1) / TPW)) void k_conv_c1_wgrad4(DAct x, DXf xf, DAct dy, int co0, float* __restrict__ partial) {
+    constexpr int TAPS = KD * 9, NCT = CIN * TAPS;
     constexpr int G = 16 / sizeof(T);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // (several channels: the wave index is made scalar, so that the rows' channels, taps and transforms live in scalar registers)
+    const int lane = threadIdx.x & 63, wave = CIN == 1 ? (int)(threadIdx.x >> 6) : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int tap0 = wave * TPW;
     float acc[TPW][COUT];
 #pragma unroll
@@ -245,6 +270,14 @@ __global__ __launch_bounds__(64 * ((KD * 9 + TPW - 1) / TPW)) void k_conv_c1_wgr
 #pragma unroll
         for (int c = 0; c < COUT; ++c) acc[t][c] = 0.f;
     const float s = xf.scale ? xf.scale[0] : 1.f, b = xf.shift ? xf.shift[0] : 0.f, sl = xf.slope ? xf.slope[0] : 1.f;
+    float sN[TPW], bN[TPW], slN[TPW];                            // several channels: the transform of each row's input channel (scalar registers)
+    if (CIN > 1) {
+#pragma unroll
+        for (int t = 0; t < TPW; ++t) {
+            const int ci = min(tap0 + t, NCT - 1) / TAPS;
+            sN[t] = xf.scale ? xf.scale[ci] : 1.f; bN[t] = xf.shift ? xf.shift[ci] : 0.f; slN[t] = xf.slope ? xf.slope[ci] : 1.f;
+        }
+    }
     // 32-bit index arithmetic throughout (the host checks nvox < 2^31): the 64-bit divisions of a linear voxel index cost as
     // many VALU instructions per iteration as the 448 FMAs they fed
     const unsigned W4 = (unsigned)dy.w / 4u;
@@ -269,8 +302,9 @@ __global__ __launch_bounds__(64 * ((KD * 9 + TPW - 1) / TPW)) void k_conv_c1_wgr
         }
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
-            const int tap = tap0 + t;
-            if (tap < TAPS) {
+            const int ct = tap0 + t;
+            if (ct < NCT) {
+                const int ci = CIN == 1 ? 0 : ct / TAPS, tap = ct - ci * TAPS;
                 const int a = tap / 9, bb = (tap / 3) % 3, c = tap % 3;
                 const int id = pdd + a - KD / 2, ih = ph + bb - 1;
                 const bool rowok = id >= 0 && id < x.d && ih >= 0 && ih < x.h;
@@ -279,8 +313,14 @@ __global__ __launch_bounds__(64 * ((KD * 9 + TPW - 1) / TPW)) void k_conv_c1_wgr
                 for (int vx = 0; vx < 4; ++vx) {
                     const int iw = w0 + vx + c - 1;
                     const bool ok = rowok && iw >= 0 && iw < x.w;          // branch-free (loads stay in flight together)
-                    const float q = fmaf(s, to_f(((const T*)x.p)[ok ? (i64)(rowbase + (unsigned)iw) * x.pitch : 0]), b);
-                    const float xv = ok ? (q > 0.f ? q : sl * q) : 0.f;
+                    const float q = fmaf(CIN == 1 ? s : sN[t], to_f(((const T*)x.p)[ok ? (i64)(rowbase + (unsigned)iw) * x.pitch + ci : 0]), CIN == 1 ? b : bN[t]);
+                    float xv;
+                    if (CIN == 1) {
+                        xv = ok ? (q > 0.f ? q : sl * q) : 0.f;
+                    } else {                                              // (the product first: a select, not a branch around it)
+                        const float neg = slN[t] * q;
+                        xv = ok ? (q > 0.f ? q : neg) : 0.f;
+                    }
 #pragma unroll
                     for (int co = 0; co < COUT; ++co) acc[t][co] = fmaf(xv, g[vx][co], acc[t][co]);
                 }
@@ -289,11 +329,11 @@ __global__ __launch_bounds__(64 * ((KD * 9 + TPW - 1) / TPW)) void k_conv_c1_wgr
     }
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
-        const int tap = tap0 + t;
+        const int ct = tap0 + t;
 #pragma unroll
         for (int co = 0; co < COUT; ++co) {
             const float r = wave_sum(acc[t][co]);
-            if (lane == 0 && tap < TAPS) partial[(i64)blockIdx.x * (TAPS * COUT) + tap * COUT + co] = r;
+            if (lane == 0 && ct < NCT) partial[(i64)blockIdx.x * (NCT * COUT) + ct * COUT + co] = r;
         }
     }
 }
@@ -301,7 +341,7 @@ __global__ __launch_bounds__(64 * ((KD * 9 + TPW - 1) / TPW)) void k_conv_c1_wgr
 #define C1_MAX_BLOCKS 2048
 
 static bool c1_ok(const biu_act* x, const biu_act* y, int kd, int kh, int kw, int dil, int dtype) {
-    if (x->c != 1 || dil != 1 || kh != 3 || kw != 3 || (kd != 1 && kd != 3)) return false;
+    if (x->c < 1 || x->c > 4 || (x->c > 1 && biu_off("cn")) || dil != 1 || kh != 3 || kw != 3 || (kd != 1 && kd != 3)) return false;
     if (y->c % 8 != 0 || y->c < 8) return false;
     if (nvox(y) >= (1LL << 31) || nvox(x) >= (1LL << 31)) return false;          // 32-bit voxel indices in the 4-voxel kernels
     const size_t es = dsize(dtype);
@@ -309,8 +349,33 @@ static bool c1_ok(const biu_act* x, const biu_act* y, int kd, int kh, int kw, in
 }
 bool biu_c1_conv_ok(const biu_act* x, const biu_act* y, int kd, int kh, int kw, int dil, int dtype) { return c1_ok(x, y, kd, kh, kw, dil, dtype); }
 
+// 2 to 4 input channels: 16- and 8-channel pieces (the reduction is Cin times as long, so a piece's weights are re-read from LDS as often)
+template <typename T, int KD, int CIN>
+static void cn_fwd_launch(const biu_act* x, const biu_xform* xf, const float* w, const float* bias, const biu_act* y, hipStream_t st) {
+    const int grid = grid_for(nvox(y), TPB, 16384), grid4 = grid_for(nvox(y) / 4, TPB, 16384);
+    const bool w4 = y->w % 4 == 0;
+    for (int co0 = 0; co0 < y->c;) {
+        if (y->c - co0 >= 16) {
+            if (w4) hipLaunchKernelGGL((k_conv_c1_fwd4<T, 16, KD, CIN>), dim3(grid4), dim3(TPB), 0, st, dact(x), dxf(xf), w, bias, dact(y), co0);
+            else hipLaunchKernelGGL((k_conv_c1_fwd<T, 16, KD, CIN>), dim3(grid), dim3(TPB), 0, st, dact(x), dxf(xf), w, bias, dact(y), co0);
+            co0 += 16;
+        } else {
+            if (w4) hipLaunchKernelGGL((k_conv_c1_fwd4<T, 8, KD, CIN>), dim3(grid4), dim3(TPB), 0, st, dact(x), dxf(xf), w, bias, dact(y), co0);
+            else hipLaunchKernelGGL((k_conv_c1_fwd<T, 8, KD, CIN>), dim3(grid), dim3(TPB), 0, st, dact(x), dxf(xf), w, bias, dact(y), co0);
+            co0 += 8;
+        }
+    }
+}
+
 template <typename T, int KD>
 static int c1_fwd_t(const biu_act* x, const biu_xform* xf, const float* w, const float* bias, const biu_act* y, hipStream_t st) {
+    if (x->c > 1) {
+        if (x->c == 2) cn_fwd_launch<T, KD, 2>(x, xf, w, bias, y, st);
+        else if (x->c == 3) cn_fwd_launch<T, KD, 3>(x, xf, w, bias, y, st);
+        else cn_fwd_launch<T, KD, 4>(x, xf, w, bias, y, st);
+        BIU_CHECK_LAUNCH("conv_c1_fwd");
+        return BIU_OK;
+    }
     const int grid = grid_for(nvox(y), TPB, 16384);
     int co0 = 0;
     while (co0 < y->c) {
@@ -334,11 +399,15 @@ int biu_c1_conv_fwd(const biu_act* x, const biu_xform* xf, const float* w, const
     return kd == 3 ? c1_fwd_t<float, 3>(x, xf, w, bias, y, st) : c1_fwd_t<float, 1>(x, xf, w, bias, y, st);
 }
 
-size_t biu_c1_wgrad_workspace(int cout, int kd) { return (size_t)C1_MAX_BLOCKS * kd * 9 * 32 * sizeof(float); }
+size_t biu_c1_wgrad_workspace(int cin, int cout, int kd) { return (size_t)C1_MAX_BLOCKS * cin * kd * 9 * 32 * sizeof(float); }
 
-template <typename T, int KD>
+template <typename T, int KD, int CIN>
 static int c1_wgrad_t(const biu_act* x, const biu_xform* xf, const biu_act* dy, float* dw, void* ws, hipStream_t st) {
-    constexpr int TAPS = KD * 9;
+    constexpr int NCT = CIN * KD * 9;                             // rows of dw[co]: (ci, tap)
+    // 16-channel pieces keep 7 x 16 accumulators per lane: up to 8 waves (256 registers each).  Beyond that (3-D with 3 or 4 input channels:
+    // 12 and 16 waves) the pieces shrink to 8 channels, 7 x 8 accumulators, rather than spill
+    constexpr bool WIDE16 = (NCT + 6) / 7 <= 8;
+    constexpr int TPW8 = CIN == 1 ? 9 : 7;
     const i64 total = nvox(dy);
     int nblk = (int)((total + 64 * 64 - 1) / (64 * 64));          // >= 64 voxels per lane
     if (nblk > C1_MAX_BLOCKS) nblk = C1_MAX_BLOCKS;
@@ -347,27 +416,36 @@ static int c1_wgrad_t(const biu_act* x, const biu_xform* xf, const biu_act* dy, 
     while (co0 < dy->c) {
         const int rem = dy->c - co0;
         int chunk;
-        if (rem >= 32 && dy->w % 4 != 0) {
+        if (CIN == 1 && rem >= 32 && dy->w % 4 != 0) {
             constexpr int TPW = 3; chunk = 32;
-            hipLaunchKernelGGL((k_conv_c1_wgrad<T, 32, KD, TPW>), dim3(nblk), dim3(64 * ((TAPS + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
-        } else if (rem >= 16) {
+            hipLaunchKernelGGL((k_conv_c1_wgrad<T, 32, KD, TPW>), dim3(nblk), dim3(64 * ((NCT + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
+        } else if (WIDE16 && rem >= 16) {
             constexpr int TPW = 7; chunk = 16;
-            if (dy->w % 4 == 0) hipLaunchKernelGGL((k_conv_c1_wgrad4<T, 16, KD, TPW>), dim3(nblk), dim3(64 * ((TAPS + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
-            else hipLaunchKernelGGL((k_conv_c1_wgrad<T, 16, KD, TPW>), dim3(nblk), dim3(64 * ((TAPS + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
+            if (dy->w % 4 == 0) hipLaunchKernelGGL((k_conv_c1_wgrad4<T, 16, KD, TPW, WIDE16 ? CIN : 1>), dim3(nblk), dim3(64 * ((NCT + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
+            else hipLaunchKernelGGL((k_conv_c1_wgrad<T, 16, KD, TPW, WIDE16 ? CIN : 1>), dim3(nblk), dim3(64 * ((NCT + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
         } else {
-            constexpr int TPW = 9; chunk = 8;
-            if (dy->w % 4 == 0) hipLaunchKernelGGL((k_conv_c1_wgrad4<T, 8, KD, TPW>), dim3(nblk), dim3(64 * ((TAPS + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
-            else hipLaunchKernelGGL((k_conv_c1_wgrad<T, 8, KD, TPW>), dim3(nblk), dim3(64 * ((TAPS + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
+            constexpr int TPW = TPW8; chunk = 8;
+            if (dy->w % 4 == 0) hipLaunchKernelGGL((k_conv_c1_wgrad4<T, 8, KD, TPW, CIN>), dim3(nblk), dim3(64 * ((NCT + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
+            else hipLaunchKernelGGL((k_conv_c1_wgrad<T, 8, KD, TPW, CIN>), dim3(nblk), dim3(64 * ((NCT + TPW - 1) / TPW)), 0, st, dact(x), dxf(xf), dact(dy), co0, (float*)ws);
         }
         BIU_CHECK_LAUNCH("conv_c1_wgrad");
-        hipLaunchKernelGGL(k_c1_wgrad_finalize, dim3(TAPS * chunk), dim3(TPB), 0, st, (const float*)ws, nblk, TAPS, chunk, co0, dw);
+        hipLaunchKernelGGL(k_c1_wgrad_finalize, dim3(NCT * chunk), dim3(TPB), 0, st, (const float*)ws, nblk, NCT, chunk, co0, dw);
         BIU_CHECK_LAUNCH("conv_c1_wgrad_finalize");
         co0 += chunk;
     }
     return BIU_OK;
 }
+template <typename T, int KD>
+static int c1_wgrad_t(const biu_act* x, const biu_xform* xf, const biu_act* dy, float* dw, void* ws, hipStream_t st) {
+    switch (x->c) {
+        case 1: return c1_wgrad_t<T, KD, 1>(x, xf, dy, dw, ws, st);
+        case 2: return c1_wgrad_t<T, KD, 2>(x, xf, dy, dw, ws, st);
+        case 3: return c1_wgrad_t<T, KD, 3>(x, xf, dy, dw, ws, st);
+        default: return c1_wgrad_t<T, KD, 4>(x, xf, dy, dw, ws, st);
+    }
+}
 int biu_c1_conv_wgrad(const biu_act* x, const biu_xform* xf, const biu_act* dy, int kd, float* dw, void* ws, size_t ws_bytes, int dtype, hipStream_t st) {
-    BIU_REQUIRE(ws && ws_bytes >= biu_c1_wgrad_workspace(dy->c, kd), BIU_ERR_WORKSPACE, "conv_c1_wgrad: workspace too small");
+    BIU_REQUIRE(ws && ws_bytes >= biu_c1_wgrad_workspace(x->c, dy->c, kd), BIU_ERR_WORKSPACE, "conv_c1_wgrad: workspace too small");
     if (dtype == BIU_BF16) return kd == 3 ? c1_wgrad_t<bf16_t, 3>(x, xf, dy, dw, ws, st) : c1_wgrad_t<bf16_t, 1>(x, xf, dy, dw, ws, st);
     return kd == 3 ? c1_wgrad_t<float, 3>(x, xf, dy, dw, ws, st) : c1_wgrad_t<float, 1>(x, xf, dy, dw, ws, st);
 }

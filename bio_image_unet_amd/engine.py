@@ -381,6 +381,8 @@ class ConvBlockNode(Node):
                                        lambda dst, st, kind=kind: lib.biu_conv_pack(kind, _ptr(w.data), *geom, dt, dst, st), job=(0, kind) + geom)
                                 for kind in (0, 1))
         eng.need_ws(lib.biu_conv_bwd_weight_workspace(*geom, dt))
+        if 2 <= xin.c <= 4 and (self.kh, self.kw, self.dil) == (3, 3, 1):       # a first layer of 2 to 4 channels: the query above is 0 for it
+            eng.need_ws(lib.biu_conv_first_workspace(xin.c, cout, self.kd, dt))
         # scratch of the input-channel split (small fp32 grids): the forward writes y, the data gradient the input's gradient(s).
         # Sized here into the engine's one workspace -- the library owns no memory (include/biu.h, biu_conv_split_workspace)
         eng.need_ws(lib.biu_conv_split_workspace(xin.c, yout.a(), None, self.kd, self.kh, self.kw, self.dil, dt))
@@ -535,8 +537,9 @@ class ConvBlockNode(Node):
             # accumulator workspace, the parameter gradient handed over a node or two later (Engine._flush_deferred)
             check(lib.biu_bn_bwd_apply(*bn_args, y.g(), eng.dtype, st), "bn_bwd_apply")
             if self.wg_ws is None:
-                self.wg_ws = torch.empty(max(lib.biu_conv_bwd_weight_workspace(xin.c, cout, self.kd, self.kh, self.kw, eng.dtype), 16), dtype=torch.uint8,
-                                         device=eng.device)
+                first = lib.biu_conv_first_workspace(xin.c, cout, self.kd, eng.dtype) if 2 <= xin.c <= 4 and (self.kh, self.kw, self.dil) == (3, 3, 1) else 0
+                self.wg_ws = torch.empty(max(lib.biu_conv_bwd_weight_workspace(xin.c, cout, self.kd, self.kh, self.kw, eng.dtype), first, 16),
+                                         dtype=torch.uint8, device=eng.device)
                 self.wg_ev = (torch.cuda.Event(), torch.cuda.Event())
             with eng.fork(side, self.wg_ev, "/wgrad", [(w, dw)]):
                 check(lib.biu_conv_bwd_weight(xin.a(), xin.xf(), y.g(), *k4, _ptr(dw), None, _ptr(self.wg_ws), self.wg_ws.numel(), eng.dtype, _stream()),

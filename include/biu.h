@@ -158,6 +158,12 @@ int biu_convt_bwd_data_bnred(const biu_act* dy, const float* w, const void* pack
 /* dw[co,ci,tap] = sum_v T(x)[v + off(tap), ci] * dy[v, co]  (PyTorch layout fp32, overwritten);
  * dbias[co] = sum_v dy[v,co] (may be NULL).  ws: biu_conv_bwd_weight_workspace() bytes.                 */
 size_t biu_conv_bwd_weight_workspace(int cin, int cout, int kd, int kh, int kw, int dtype);
+/* First layers: 1 to 4 input channels, 3x3(x3), dilation 1, 8 | cout (bf16 with 16 | cout runs on the matrix cores, K = cin x taps).
+ * biu_conv_first_ok: 1 if a first-layer kernel serves this layer (host arithmetic on the descriptors, no device call);
+ * biu_conv_first_workspace: weight-gradient scratch enough for either of its kernels.  biu_conv_bwd_weight_workspace() is 0 for 2..4 input
+ * channels, so a caller sizes ws by the larger of the two; with less, these layers take the any-shape kernel.                          */
+int biu_conv_first_ok(const biu_act* x, const biu_act* y, int kd, int kh, int kw, int dilation, int dtype);
+size_t biu_conv_first_workspace(int cin, int cout, int kd, int dtype);
 int biu_conv_bwd_weight(const biu_act* x, const biu_xform* xf, const biu_act* dy,
                         int kd, int kh, int kw, int dilation,
                         float* dw, float* dbias, void* ws, size_t ws_bytes, int dtype, biu_stream stream);

@@ -125,14 +125,9 @@ SIGNATURES = {
     "biu_upconv_fwd_stats_floats": (_Z, [_A, _A]),
     "biu_upconv_fwd": (_I, [_A, _X, _P, _P, _A, _P, _Z, C.POINTER(C.c_int), _I, _P]),
     "biu_nearest_up_bwd": (_I, [_A, _A, _I, _I, _P]),
-    "biu_bce_dice_blocks": (_I, [C.c_longlong]),
-    "biu_bce_dice_fwd": (_I, [_P, _P, _I, C.c_longlong, _P, _P]),
-    "biu_bce_dice_bwd": (_I, [_P, _P, _I, C.c_longlong, _P, _P, _I, _P]),
     "biu_pair_smooth_l1_blocks": (_I, [C.c_longlong]),
     "biu_pair_smooth_l1_fwd": (_I, [_P, _I, C.c_longlong, _P, _P]),
     "biu_pair_smooth_l1_bwd": (_I, [_P, _I, C.c_longlong, _P, _P, _I, _P]),
-    "biu_seg_loss_finish": (_I, [_P, _I, _I, C.c_longlong, _P, _I, _F, _F, _F, _I, _F, _F, _F, _I, _F, _P, _P]),
-    "biu_seg_loss_coef": (_I, [_P, _P, _I, C.c_longlong, _F, _F, _F, _I, _F, _F, _F, _I, _F, _P, _P, _P]),
     "biu_head_dlogits": (_I, [_P, _P, _P, _I, _I, _I, C.c_longlong, _P, _I, _I, _P]),
     "biu_mo2d_loss_blocks": (_I, [C.c_longlong]),
     "biu_mo2d_loss_fwd": (_I, [_I, _F, _F, _P, _I, _P, _I, _I, _I, _I, _P, _P]),

@@ -207,78 +207,7 @@ extern "C" int biu_xcorr_bwd(const biu_act* cur, const biu_xform* xc, const biu_
     return BIU_OK;
 }
 
-// =====================================================================================================================
-// BCEDiceLoss in one pass over (logits, target), fp32 NC[D]HW as the heads emit them [unet/losses.py:78-112]:
-//   fwd: per sample n the four sums  sum bce(l,t), sum p, sum t, sum p*t   (p = sigmoid(l)), as per-block partials
-//   bwd: dl_i (+)= c_bce * (p_i - t_i) + (c_p[n] + c_pt[n] * t_i) * p_i * (1 - p_i)   with host-made coefficients
-// The reference spends three full-tensor reductions with 4 output rows each (one workgroup per row) on this.
-// =====================================================================================================================
 namespace {
-__global__ __launch_bounds__(256) void k_bce_dice_fwd(const float* __restrict__ lg, const float* __restrict__ tg, i64 per_sample,
-                                                      float* __restrict__ partial /* [n][gridDim.x][4] */) {
-    const int n = blockIdx.y;
-    const float* l = lg + (i64)n * per_sample;
-    const float* t = tg + (i64)n * per_sample;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += (i64)gridDim.x * blockDim.x) {
-        const float x = l[i], y = t[i];
-        const float e = __expf(-fabsf(x));
-        s0 += fmaxf(x, 0.f) - x * y + log1pf(e);
-        const float p = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-        s1 += p;
-        s2 += y;
-        s3 += p * y;
-    }
-    __shared__ float red[16];
-    float* dst = partial + ((i64)n * gridDim.x + blockIdx.x) * 4;
-    float r;
-    r = block_sum(s0, red); if (threadIdx.x == 0) dst[0] = r;
-    r = block_sum(s1, red); if (threadIdx.x == 0) dst[1] = r;
-    r = block_sum(s2, red); if (threadIdx.x == 0) dst[2] = r;
-    r = block_sum(s3, red); if (threadIdx.x == 0) dst[3] = r;
-}
-__global__ __launch_bounds__(256) void k_bce_dice_bwd(const float* __restrict__ lg, const float* __restrict__ tg, i64 per_sample,
-                                                      const float* __restrict__ coef /* [n][3]: c_bce, c_p, c_pt */,
-                                                      float* __restrict__ dl, int accumulate) {
-    const int n = blockIdx.y;
-    const float cb = coef[n * 3 + 0], cp = coef[n * 3 + 1], cpt = coef[n * 3 + 2];
-    const i64 base = (i64)n * per_sample;
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += (i64)gridDim.x * blockDim.x) {
-        const float x = lg[base + i], y = tg[base + i];
-        const float e = __expf(-fabsf(x));
-        const float p = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-        float g = cb * (p - y) + (cp + cpt * y) * p * (1.f - p);
-        if (accumulate) g += dl[base + i];
-        dl[base + i] = g;
-    }
-}
-
-// SmoothL1 (beta = 1, mean) between neighbouring BATCH entries of the logits -- the 3-D trainer's "time" term
-// nn.SmoothL1Loss()(y_logits[1:], y_logits[:-1]) (unet3d/train.py:140-145).  d_i = l[i+1] - l[i] for i < (n-1)*per_sample.
-__device__ __forceinline__ float sl1(float d) { const float a = fabsf(d); return a < 1.f ? 0.5f * d * d : a - 0.5f; }
-__device__ __forceinline__ float dsl1(float d) { return d > 1.f ? 1.f : (d < -1.f ? -1.f : d); }
-__global__ __launch_bounds__(256) void k_pair_sl1_fwd(const float* __restrict__ lg, i64 per_sample, i64 pairs, float* __restrict__ partial) {
-    float s = 0.f;
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < pairs; i += (i64)gridDim.x * blockDim.x) s += sl1(lg[i + per_sample] - lg[i]);
-    __shared__ float red[16];
-    const float r = block_sum(s, red);
-    if (threadIdx.x == 0) partial[blockIdx.x] = r;
-}
-// dl[j] (+)= c * (h'(l[j] - l[j - P]) [j >= P]  -  h'(l[j + P] - l[j]) [j < pairs]),  c = upstream gradient * weight / pairs
-__global__ __launch_bounds__(256) void k_pair_sl1_bwd(const float* __restrict__ lg, i64 per_sample, i64 total, const float* __restrict__ coef,
-                                                      float* __restrict__ dl, int accumulate) {
-    const float c = coef[0];
-    const i64 pairs = total - per_sample;
-    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += (i64)gridDim.x * blockDim.x) {
-        const float x = lg[j];
-        float g = 0.f;
-        if (j >= per_sample) g += dsl1(x - lg[j - per_sample]);
-        if (j < pairs) g -= dsl1(lg[j + per_sample] - x);
-        g *= c;
-        dl[j] = accumulate ? dl[j] + g : g;
-    }
-}
-
 // d loss / d logits of one head from the caller's gradients w.r.t. (logits, activated output), written into channels
 // [c0, c0 + ch) of a [n, ctot, S] buffer (the stacked operand of the multi-head backward): out = g_logits + g_act * f'(.)
 __global__ __launch_bounds__(256) void k_head_dlogits(const float* __restrict__ gl, const float* __restrict__ ga, const float* __restrict__ av,
@@ -299,26 +228,6 @@ __global__ __launch_bounds__(256) void k_head_dlogits(const float* __restrict__ 
 }
 }  // namespace
 
-extern "C" int biu_pair_smooth_l1_blocks(long long pairs) {
-    long long b = (pairs + 256 * 8 - 1) / (256 * 8);
-    return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
-}
-extern "C" int biu_pair_smooth_l1_fwd(const float* logits, int n, long long per_sample, float* partial, biu_stream stream) {
-    BIU_REQUIRE(logits && partial && n > 1 && per_sample > 0, BIU_ERR_SHAPE, "pair_smooth_l1_fwd: needs at least two batch entries");
-    const i64 pairs = (i64)(n - 1) * per_sample;
-    hipLaunchKernelGGL(k_pair_sl1_fwd, dim3(biu_pair_smooth_l1_blocks(pairs)), dim3(256), 0, (hipStream_t)stream, logits, (i64)per_sample, pairs, partial);
-    BIU_CHECK_LAUNCH("pair_smooth_l1_fwd");
-    return BIU_OK;
-}
-extern "C" int biu_pair_smooth_l1_bwd(const float* logits, int n, long long per_sample, const float* coef, float* dlogits, int accumulate,
-                                      biu_stream stream) {
-    BIU_REQUIRE(logits && coef && dlogits && n > 1 && per_sample > 0, BIU_ERR_SHAPE, "pair_smooth_l1_bwd: bad arguments");
-    const i64 total = (i64)n * per_sample;
-    hipLaunchKernelGGL(k_pair_sl1_bwd, dim3(grid_for(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, logits, (i64)per_sample, total, coef,
-                       dlogits, accumulate);
-    BIU_CHECK_LAUNCH("pair_smooth_l1_bwd");
-    return BIU_OK;
-}
 extern "C" int biu_head_dlogits(const float* g_logits, const float* g_act, const float* activated, int act, int n, int ch, long long spatial,
                                 float* dst, int dst_channels, int dst_c0, biu_stream stream) {
     BIU_REQUIRE((g_logits || g_act) && dst && n > 0 && ch > 0 && spatial > 0 && dst_c0 >= 0 && dst_c0 + ch <= dst_channels, BIU_ERR_SHAPE,
@@ -328,129 +237,5 @@ extern "C" int biu_head_dlogits(const float* g_logits, const float* g_act, const
     hipLaunchKernelGGL(k_head_dlogits, dim3(grid_for(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, g_logits, g_act, activated, act, ch,
                        (i64)spatial, dst, dst_channels, dst_c0, total);
     BIU_CHECK_LAUNCH("head_dlogits");
-    return BIU_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The scalar part of the fused segmentation losses (bio_image_unet_amd/losses.py: _FusedSegLoss) in two one-block kernels instead of
-// ~20 tiny torch launches per step: biu_seg_loss_finish merges the per-block partial sums and evaluates the loss, biu_seg_loss_coef
-// turns the incoming gradient into the per-sample coefficients biu_bce_dice_bwd / biu_pair_smooth_l1_bwd take.
-//   saved = { loss, sums[n][4] (BCE, P, T, P.T), den[n], tp, tden, tv }
-// ---------------------------------------------------------------------------------------------------------------------
-struct SegLossCfg { float a_bce, a_dice, smooth; int has_tv; float al, be, sm; int logcosh; float w_time; long long pairs; int nbt; };
-namespace {
-__global__ __launch_bounds__(256) void k_seg_loss_finish(const float* __restrict__ partial, int n, int nb, long long per,
-                                                        const float* __restrict__ pt, SegLossCfg c, float* __restrict__ saved) {
-    __shared__ double red[256];
-    float* sums = saved + 1;
-    // one wave per (sample, quantity) sum, lanes stride over the per-block partials, fixed-order butterfly in fp64 (16 threads walking
-    // 1024 partials each took 0.1 ms at 4 x 128^3)
-    for (int idx = threadIdx.x >> 6; idx < n * 4; idx += 4) {
-        const int i = idx >> 2, k = idx & 3, lane = threadIdx.x & 63;
-        double a = 0.0;
-        for (int b = lane; b < nb; b += 64) a += (double)partial[((size_t)i * nb + b) * 4 + k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
-        if (lane == 0) sums[idx] = (float)a;
-    }
-    __syncthreads();
-    double tsum = 0.0;
-    if (pt)
-        for (int b = threadIdx.x; b < c.nbt; b += 256) tsum += (double)pt[b];
-    red[threadIdx.x] = tsum;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        double loss = 0.0, bce = 0.0, dice = 0.0, tp = 0.0, ps = 0.0, ts = 0.0;
-        float* den = saved + 1 + 4 * n;
-        for (int i = 0; i < n; ++i) {
-            bce += (double)sums[4 * i];
-            ps += (double)sums[4 * i + 1]; ts += (double)sums[4 * i + 2]; tp += (double)sums[4 * i + 3];
-            const float d = sums[4 * i + 1] + sums[4 * i + 2] + c.smooth;
-            den[i] = d;
-            dice += 2.0 * ((double)sums[4 * i + 3] + c.smooth) / (double)d;
-        }
-        if (c.a_bce != 0.f) loss += (double)c.a_bce * bce / ((double)n * (double)per);
-        if (c.a_dice != 0.f) loss += (double)c.a_dice * (1.0 - dice / n);
-        float* tvs = den + n;
-        tvs[0] = tvs[1] = tvs[2] = 0.f;
-        if (c.has_tv) {
-            const double tden = tp + c.al * (ps - tp) + c.be * (ts - tp) + c.sm;
-            const double tv = (tp + c.sm) / tden;
-            tvs[0] = (float)tp; tvs[1] = (float)tden; tvs[2] = (float)tv;
-            loss += c.logcosh ? log(cosh(1.0 - tv)) : (1.0 - tv);
-        }
-        if (pt) loss += (double)c.w_time * red[0] / (double)c.pairs;
-        saved[0] = (float)loss;
-    }
-}
-// coef[n][3]: d loss / d logit_i = c0 (p_i - t_i) + (c1 + c2 t_i) p_i (1 - p_i) per sample; ctime[0]: the time term's factor
-__global__ void k_seg_loss_coef(const float* __restrict__ g, const float* __restrict__ saved, int n, long long per, SegLossCfg c,
-                                float* __restrict__ coef, float* __restrict__ ctime) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const float gv = g[0];
-    if (i == 0 && ctime) ctime[0] = (n > 1) ? gv * (c.w_time / ((float)(n - 1) * (float)per)) : 0.f;
-    if (i >= n) return;
-    const float* sums = saved + 1 + 4 * i;
-    const float den = saved[1 + 4 * n + i];
-    const float* tvs = saved + 1 + 5 * n;
-    float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-    if (c.a_bce != 0.f) c0 = gv * (c.a_bce / ((float)n * (float)per));
-    if (c.a_dice != 0.f) {
-        c1 += gv * (c.a_dice / n) * 2.0f * (sums[3] + c.smooth) / (den * den);
-        c2 += -gv * (c.a_dice / n) * 2.0f / den;
-    }
-    if (c.has_tv) {
-        const float tp = tvs[0], tden = tvs[1], tv = tvs[2];
-        const float outer = -gv * (c.logcosh ? tanhf(1.f - tv) : 1.f);                 // d loss / d Tversky
-        const float d_tp = (tden - (tp + c.sm) * (1.f - c.al - c.be)) / (tden * tden);
-        const float d_ps = -(tp + c.sm) * c.al / (tden * tden);
-        c1 += outer * d_ps;
-        c2 += outer * d_tp;
-    }
-    coef[3 * i] = c0; coef[3 * i + 1] = c1; coef[3 * i + 2] = c2;
-}
-}  // namespace
-
-extern "C" int biu_seg_loss_finish(const float* partial, int n, int nb, long long per_sample, const float* time_partial, int nbt,
-                                   float a_bce, float a_dice, float smooth, int has_tversky, float tv_alpha, float tv_beta, float tv_smooth,
-                                   int logcosh, float w_time, float* saved, biu_stream stream) {
-    BIU_REQUIRE(partial && saved && n > 0 && nb > 0 && per_sample > 0 && (!time_partial || (nbt > 0 && n > 1)), BIU_ERR_SHAPE, "seg_loss_finish: bad arguments");
-    const SegLossCfg c{a_bce, a_dice, smooth, has_tversky, tv_alpha, tv_beta, tv_smooth, logcosh, w_time, (long long)(n - 1) * per_sample, nbt};
-    hipLaunchKernelGGL(k_seg_loss_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, n, nb, per_sample, time_partial, c, saved);
-    BIU_CHECK_LAUNCH("seg_loss_finish");
-    return BIU_OK;
-}
-extern "C" int biu_seg_loss_coef(const float* g, const float* saved, int n, long long per_sample, float a_bce, float a_dice, float smooth,
-                                 int has_tversky, float tv_alpha, float tv_beta, float tv_smooth, int logcosh, float w_time, float* coef,
-                                 float* time_coef, biu_stream stream) {
-    BIU_REQUIRE(g && saved && coef && n > 0 && per_sample > 0, BIU_ERR_SHAPE, "seg_loss_coef: bad arguments");
-    const SegLossCfg c{a_bce, a_dice, smooth, has_tversky, tv_alpha, tv_beta, tv_smooth, logcosh, w_time, (long long)(n - 1) * per_sample, 0};
-    hipLaunchKernelGGL(k_seg_loss_coef, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, g, saved, n, per_sample, c, coef, time_coef);
-    BIU_CHECK_LAUNCH("seg_loss_coef");
-    return BIU_OK;
-}
-
-extern "C" int biu_bce_dice_blocks(long long per_sample) {
-    long long b = (per_sample + 256 * 8 - 1) / (256 * 8);
-    return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
-}
-extern "C" int biu_bce_dice_fwd(const float* logits, const float* target, int n, long long per_sample, float* partial,
-                                biu_stream stream) {
-    BIU_REQUIRE(logits && target && partial && n > 0 && per_sample > 0, BIU_ERR_SHAPE, "bce_dice_fwd: bad arguments");
-    hipLaunchKernelGGL(k_bce_dice_fwd, dim3(biu_bce_dice_blocks(per_sample), n), dim3(256), 0, (hipStream_t)stream, logits, target,
-                       (i64)per_sample, partial);
-    BIU_CHECK_LAUNCH("bce_dice_fwd");
-    return BIU_OK;
-}
-extern "C" int biu_bce_dice_bwd(const float* logits, const float* target, int n, long long per_sample, const float* coef,
-                                float* dlogits, int accumulate, biu_stream stream) {
-    BIU_REQUIRE(logits && target && coef && dlogits && n > 0 && per_sample > 0, BIU_ERR_SHAPE, "bce_dice_bwd: bad arguments");
-    hipLaunchKernelGGL(k_bce_dice_bwd, dim3(biu_bce_dice_blocks(per_sample), n), dim3(256), 0, (hipStream_t)stream, logits, target,
-                       (i64)per_sample, coef, dlogits, accumulate);
-    BIU_CHECK_LAUNCH("bce_dice_bwd");
     return BIU_OK;
 }

@@ -1,19 +1,32 @@
-// The five criteria of the 3-D multi-output trainer (multi_output_unet3d/losses.py) on the tensor the model returned for a head, fp32
-// contiguous [N, C, D, H, W], which the criteria treat as LOGITS (p = sigmoid(x)); all heads of a step as one autograd node:
-//   biu_mo3d_loss_fwd     one launch per head, one pass over (x, t): per-block partial sums, BIU_MO3D_SLOTS floats per row, rows kept per
-//                         sample so that Dice (per sample) and Tversky (whole tensor) follow from one layout; no float atomics
-//   biu_mo3d_loss_finish  one one-block launch per step: merges every head's rows in a fixed order (fp64), evaluates every criterion and
-//                         the weighted total into `saved`
-//   biu_mo3d_loss_coef    one one-block launch: d total (device scalar) -> four coefficients per (head, sample)
-//   biu_mo3d_loss_bwd     one launch per head: dx = c0 (p - t) + (c1 + c2 t) p (1 - p) + ct (sign(x[z] - x[z-1]) - sign(x[z+1] - x[z]))
-// Slots of a partial row: 0 sum BCEWithLogits, 1 sum p, 2 sum t, 3 sum p t, 4 sum |x[z+1] - x[z]| (the temporal kind only).
+// The segmentation criteria on fp32 contiguous LOGITS (p = sigmoid(x)), one implementation for the single-head criteria of
+// bio_image_unet_amd/losses.py (any rank, seen as [N, per]) and the five of the 3-D multi-output trainer (multi_output_unet3d/losses.py,
+// [N, C, D, H, W]); all terms of a step are one autograd node:
+//   biu_mo3d_loss_fwd       one launch per head, one pass over (x, t): per-block partial sums, NS floats per row, rows kept per sample so
+//                           that Dice (per sample) and Tversky (whole tensor) follow from one layout; no float atomics
+//   biu_pair_smooth_l1_fwd  the K_PAIRSL1 term's pass over x: one row per block, the block's sum in slot 0
+//   biu_mo3d_loss_finish    one one-block launch per step: merges every term's rows in a fixed order (fp64), evaluates every criterion and
+//                           the weighted total into `saved`
+//   biu_mo3d_loss_coef      one one-block launch: d total (device scalar) -> four coefficients per (term, sample)
+//   biu_mo3d_loss_bwd       one launch per head: dx = c0 (p - t) + (c1 + c2 t) p (1 - p) + ct (sign(x[z] - x[z-1]) - sign(x[z+1] - x[z]))
+//   biu_pair_smooth_l1_bwd  dx (+)= c0 d sum SmoothL1 / dx, c0 read from the K_PAIRSL1 term's coefficient row
+// Kinds and the (p0, p1, p2) of their biu_mo3d_term:
+//   K_BCEDICE    (alpha, beta, s)     alpha mean BCEWithLogits + beta (1 - mean_n 2 (PT_n + s) / (P_n + T_n + s))
+//   K_TVERSKY    (alpha, beta, s)     1 - Tv, Tv = (TP + s) / (TP + alpha FP + beta FN + s) over the whole tensor
+//   K_LCTVERSKY  (alpha, beta, s)     log cosh(1 - Tv)
+//   K_TEMPORAL   (w0, w1, -)          w0 BCEDice(1, 1) with s = 1 + w1 sum |x[z+1] - x[z]| / pairs; nan when pairs == 0
+//   K_PAIRSL1    (-, -, -)            sum SmoothL1(x[i + per] - x[i]) / pairs between neighbouring BATCH entries, pairs = (N - 1) per; a
+//                                     term with n = 1 and rows = biu_pair_smooth_l1_blocks(pairs), it has no fwd / bwd launch of its own kind
+// Slots of a partial row: 0 sum BCEWithLogits (K_PAIRSL1: sum SmoothL1), 1 sum p, 2 sum t, 3 sum p t, 4 sum |x[z+1] - x[z]| (K_TEMPORAL),
+// 5..7 zero.
+// saved = { total, loss of term 0 .. nterms - 1, 0 ... up to HDR, then a row of NS floats per (term, sample) in table order: the merged
+// slots }; coef = { c0, c1, c2, ct } per (term, sample) in the same order.
 // The temporal term is the L1 between neighbouring z-planes of x (not of p).  Within a sample the element i = ((c D + z) H + y) W + x has
 // z = (i / (H W)) % D and its z-neighbour at i + H W; a pair exists for z < D - 1, so none crosses a channel or a sample.  The neighbour
 // plane is re-read through L2 (another block of the same launch streams it at about the same time); no LDS staging.
 #include "biu_common.h"
 
 namespace {
-enum { K_BCEDICE = 0, K_TVERSKY = 1, K_LCTVERSKY = 2, K_TEMPORAL = 3, K_COUNT = 4 };
+enum { K_BCEDICE = 0, K_TVERSKY = 1, K_LCTVERSKY = 2, K_TEMPORAL = 3, K_COUNT = 4 /* kinds of _fwd / _bwd */, K_PAIRSL1 = BIU_MO3D_PAIR_SL1 };
 constexpr int NS = BIU_MO3D_SLOTS, NACC = 5, HDR = BIU_MO3D_SAVED_HEADER;
 
 struct Args {
@@ -138,17 +151,50 @@ template <bool TEMP, int V> __global__ __launch_bounds__(256) void k_mo3d_bwd(co
     }
 }
 
+// SmoothL1 (beta = 1, mean) between neighbouring BATCH entries of the logits -- the 3-D trainer's "time" term
+// nn.SmoothL1Loss()(y_logits[1:], y_logits[:-1]) (unet3d/train.py:140-145).  d_i = l[i+1] - l[i] for i < (n-1)*per_sample.
+__device__ __forceinline__ float sl1(float d) { const float a = fabsf(d); return a < 1.f ? 0.5f * d * d : a - 0.5f; }
+__device__ __forceinline__ float dsl1(float d) { return d > 1.f ? 1.f : (d < -1.f ? -1.f : d); }
+__global__ __launch_bounds__(256) void k_pair_sl1_fwd(const float* __restrict__ lg, i64 per_sample, i64 pairs, float* __restrict__ partial) {
+    float s = 0.f;
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < pairs; i += (i64)gridDim.x * blockDim.x) s += sl1(lg[i + per_sample] - lg[i]);
+    __shared__ float red[16];
+    const float r = block_sum(s, red);
+    if (threadIdx.x == 0) {
+        float* row = partial + (i64)blockIdx.x * NS;
+        row[0] = r;
+#pragma unroll
+        for (int k = 1; k < NS; ++k) row[k] = 0.f;
+    }
+}
+// dl[j] (+)= c * (h'(l[j] - l[j - P]) [j >= P]  -  h'(l[j + P] - l[j]) [j < pairs]),  c = upstream gradient * weight / pairs
+__global__ __launch_bounds__(256) void k_pair_sl1_bwd(const float* __restrict__ lg, i64 per_sample, i64 total, const float* __restrict__ coef,
+                                                      float* __restrict__ dl, int accumulate) {
+    const float c = coef[0];
+    const i64 pairs = total - per_sample;
+    for (i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += (i64)gridDim.x * blockDim.x) {
+        const float x = lg[j];
+        float g = 0.f;
+        if (j >= per_sample) g += dsl1(x - lg[j - per_sample]);
+        if (j < pairs) g -= dsl1(lg[j + per_sample] - x);
+        g *= c;
+        dl[j] = accumulate ? dl[j] + g : g;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // the scalar part: saved = { total, loss of term 0 .. nterms - 1, 0 ..., then from HDR a row of NS floats per (term, sample):
 //                            the merged sums of the five slots, 0 x 3 }
+// `sm` is the Dice smooth: p2 of a K_BCEDICE term, 1 for K_TEMPORAL.
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct Whole { double bce, ps, ts, tp, dice, tdiff; };
-__device__ __forceinline__ Whole whole_of(const float* s, int n) {      // fixed order over the samples
+__device__ __forceinline__ double dice_smooth(const biu_mo3d_term& t) { return t.kind == K_BCEDICE ? (double)t.p2 : 1.0; }
+__device__ __forceinline__ Whole whole_of(const float* s, int n, double sm) {      // fixed order over the samples
     Whole w = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int i = 0; i < n; ++i) {
         const float* r = s + (i64)i * NS;
         w.bce += (double)r[0]; w.ps += (double)r[1]; w.ts += (double)r[2]; w.tp += (double)r[3]; w.tdiff += (double)r[4];
-        w.dice += 2.0 * ((double)r[3] + 1.0) / ((double)r[1] + (double)r[2] + 1.0);
+        w.dice += 2.0 * ((double)r[3] + sm) / ((double)r[1] + (double)r[2] + sm);
     }
     return w;
 }
@@ -190,13 +236,14 @@ __global__ __launch_bounds__(1024) void k_mo3d_finish(const biu_mo3d_term* __res
     __syncthreads();
     if ((int)threadIdx.x < nterms) {
         const biu_mo3d_term t = tm[threadIdx.x];
-        const Whole w = whole_of(saved + HDR + (i64)first[threadIdx.x] * NS, (int)t.n);
+        const Whole w = whole_of(saved + HDR + (i64)first[threadIdx.x] * NS, (int)t.n, dice_smooth(t));
         const double M = (double)t.n * (double)t.per_sample;
         double loss, den;
         switch (t.kind) {
             case K_BCEDICE: loss = (double)t.p0 * (w.bce / M) + (double)t.p1 * (1.0 - w.dice / (double)t.n); break;
             case K_TVERSKY: loss = 1.0 - tversky(t, w, &den); break;
             case K_LCTVERSKY: loss = log(cosh(1.0 - tversky(t, w, &den))); break;
+            case K_PAIRSL1: loss = w.bce / (double)t.pairs; break;
             default:      // an empty slice (D = 1): l1_loss gives nan, whatever its weight
                 loss = (double)t.p0 * (w.bce / M + 1.0 - w.dice / (double)t.n) + (t.pairs > 0 ? (double)t.p1 * (w.tdiff / (double)t.pairs) : (double)NAN);
                 break;
@@ -221,10 +268,11 @@ __global__ __launch_bounds__(256) void k_mo3d_coef(const biu_mo3d_term* __restri
         const int n = (int)t.n;
         const float* s = saved + HDR + row0 * NS;
         const double gw = (double)g[0] * (double)t.weight, M = (double)t.n * (double)t.per_sample;
+        const double sm = dice_smooth(t);
         double c0 = 0.0, c1 = 0.0, c2 = 0.0, ct = 0.0, dw = 0.0;
         if (t.kind == K_TVERSKY || t.kind == K_LCTVERSKY) {
             double den;
-            const Whole w = whole_of(s, n);
+            const Whole w = whole_of(s, n, 1.0);
             const double tv = tversky(t, w, &den), tps = w.tp + (double)t.p2;
             const double outer = -gw * (t.kind == K_LCTVERSKY ? tanh(1.0 - tv) : 1.0);          // d loss / d Tversky
             c1 = outer * (-tps * (double)t.p0 / (den * den));
@@ -232,6 +280,8 @@ __global__ __launch_bounds__(256) void k_mo3d_coef(const biu_mo3d_term* __restri
         } else if (t.kind == K_BCEDICE) {
             c0 = gw * (double)t.p0 / M;
             dw = gw * (double)t.p1 / (double)t.n;
+        } else if (t.kind == K_PAIRSL1) {
+            c0 = gw / (double)t.pairs;
         } else {
             c0 = gw * (double)t.p0 / M;
             dw = gw * (double)t.p0 / (double)t.n;
@@ -240,9 +290,9 @@ __global__ __launch_bounds__(256) void k_mo3d_coef(const biu_mo3d_term* __restri
         for (int i = threadIdx.x; i < n; i += 256) {
             const float* r = s + (i64)i * NS;
             double a1 = c1, a2 = c2;
-            if (dw != 0.0) {      // 1 - mean_n 2 (I_n + 1) / (P_n + T_n + 1), per sample
-                const double den = (double)r[1] + (double)r[2] + 1.0;
-                a1 = dw * 2.0 * ((double)r[3] + 1.0) / (den * den);
+            if (dw != 0.0) {      // 1 - mean_n 2 (I_n + s) / (P_n + T_n + s), per sample
+                const double den = (double)r[1] + (double)r[2] + sm;
+                a1 = dw * 2.0 * ((double)r[3] + sm) / (den * den);
                 a2 = -dw * 2.0 / den;
             }
             float* c = coef + (row0 + i) * 4;
@@ -320,6 +370,27 @@ extern "C" int biu_mo3d_loss_bwd(int kind, const float* x, const float* target, 
         else hipLaunchKernelGGL((k_mo3d_bwd<false, 1>), grid, dim3(256), 0, st, a);
     }
     BIU_CHECK_LAUNCH("mo3d_loss_bwd");
+    return BIU_OK;
+}
+
+extern "C" int biu_pair_smooth_l1_blocks(long long pairs) {
+    long long b = (pairs + 256 * 8 - 1) / (256 * 8);
+    return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
+}
+extern "C" int biu_pair_smooth_l1_fwd(const float* logits, int n, long long per_sample, float* partial, biu_stream stream) {
+    BIU_REQUIRE(logits && partial && n > 1 && per_sample > 0, BIU_ERR_SHAPE, "pair_smooth_l1_fwd: needs at least two batch entries");
+    const i64 pairs = (i64)(n - 1) * per_sample;
+    hipLaunchKernelGGL(k_pair_sl1_fwd, dim3(biu_pair_smooth_l1_blocks(pairs)), dim3(256), 0, (hipStream_t)stream, logits, (i64)per_sample, pairs, partial);
+    BIU_CHECK_LAUNCH("pair_smooth_l1_fwd");
+    return BIU_OK;
+}
+extern "C" int biu_pair_smooth_l1_bwd(const float* logits, int n, long long per_sample, const float* coef, float* dlogits, int accumulate,
+                                      biu_stream stream) {
+    BIU_REQUIRE(logits && coef && dlogits && n > 1 && per_sample > 0, BIU_ERR_SHAPE, "pair_smooth_l1_bwd: bad arguments");
+    const i64 total = (i64)n * per_sample;
+    hipLaunchKernelGGL(k_pair_sl1_bwd, dim3(grid_for(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, logits, (i64)per_sample, total, coef,
+                       dlogits, accumulate);
+    BIU_CHECK_LAUNCH("pair_smooth_l1_bwd");
     return BIU_OK;
 }
 

@@ -19,6 +19,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .._lib import stream as _stream
+from ..losses import tversky_index
 
 K_BCEDICE, K_TVERSKY, K_LCTVERSKY, K_MSE, K_MAE, K_HUBER, K_DGRAD, K_WDGRAD, K_WVF = range(9)
 MAX_LEVELS, MAX_TERMS, SLOTS = 4, 32, 8
@@ -162,14 +163,6 @@ class BCEDiceLoss(_Criterion):
         return self.bce_weight * self.bce(inputs, targets) + self.dice_weight * dice
 
 
-def _tversky(inputs, targets, alpha, beta, smooth):
-    p, t = inputs.reshape(-1), targets.reshape(-1)
-    tp = (p * t).sum()
-    fp = ((1 - t) * p).sum()
-    fn = (t * (1 - p)).sum()
-    return (tp + smooth) / (tp + alpha * fp + beta * fn + smooth)
-
-
 class TverskyLoss(_Criterion):
     """``1 - (TP + s) / (TP + alpha FP + beta FN + s)`` on probabilities (losses.py:31-49)."""
     kind = K_TVERSKY
@@ -182,7 +175,7 @@ class TverskyLoss(_Criterion):
         return (float(self.alpha), float(self.beta), float(self.smooth))
 
     def _torch(self, inputs, targets):
-        return 1 - _tversky(inputs, targets, self.alpha, self.beta, self.smooth)
+        return 1 - tversky_index(inputs, targets, self.alpha, self.beta, self.smooth)
 
 
 class logcoshTverskyLoss(TverskyLoss):
@@ -190,7 +183,7 @@ class logcoshTverskyLoss(TverskyLoss):
     kind = K_LCTVERSKY
 
     def _torch(self, inputs, targets):
-        return torch.log(torch.cosh(1 - _tversky(inputs, targets, self.alpha, self.beta, self.smooth)))
+        return torch.log(torch.cosh(1 - tversky_index(inputs, targets, self.alpha, self.beta, self.smooth)))
 
 
 # regression -----------------------------------------------------------------------------------------------------------------------

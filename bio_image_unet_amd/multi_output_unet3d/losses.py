@@ -8,7 +8,8 @@ On CUDA fp32 contiguous ``[N, C, D, H, W]`` tensors of equal shape every criteri
 plus a backward launch per head.  The temporal term of ``BCEDiceTemporalLoss`` (L1 between neighbouring z-planes) rides in the same two
 passes, and the validation pass's second activation is applied in the forward kernel's registers.
 
-``bio_image_unet_amd.losses`` holds the per-head form of the same formulas for the other families.
+The single-head criteria of ``bio_image_unet_amd.losses`` (the other families) run on the same plan and the same autograd function, as
+one-term plans; their batch-axis SmoothL1 "time" term (``_Plan(time_weight=...)``) is a term of the table with two launches of its own.
 """
 from __future__ import annotations
 
@@ -18,13 +19,13 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .._lib import stream as _stream
+from .._lib import biu_mo3d_term, check, lib, stream as _stream
+from ..losses import K_BCEDICE, K_LCTVERSKY, K_PAIRSL1, K_TEMPORAL, K_TVERSKY, soft_dice, tversky_index
 
-K_BCEDICE, K_TVERSKY, K_LCTVERSKY, K_TEMPORAL = range(4)
 MAX_TERMS, SLOTS, SAVED_HEADER = 16, 8, 32
 ACT_CODE = {"sigmoid": 1, "tanh": 2, "relu": 3}      # engine._ACT_CODE; anything else is no activation, softmax goes through torch
 
-launches = 0      # biu_mo3d_loss_* calls issued by this module (tests assert the launch plan with it)
+launches = 0      # biu_mo3d_loss_* / biu_pair_smooth_l1_* calls issued by this module (tests assert the launch plan with it)
 
 
 def _fusable(logits, targets):
@@ -35,7 +36,6 @@ def _fusable(logits, targets):
 
 def _call(name, *args):
     global launches
-    from .._lib import check, lib
     launches += 1
     check(getattr(lib, name)(*args), name[4:])
 
@@ -46,10 +46,10 @@ def _p(t, floats=0):
 
 class _Plan:
     """The launch plan of one configuration: per head (criterion, shape, weight) its slice of the partial workspace, its first row of
-    ``saved`` / ``coef``, and the term table ``biu_mo3d_loss_finish`` / ``_coef`` read, uploaded once."""
+    ``saved`` / ``coef``, and the term table ``biu_mo3d_loss_finish`` / ``_coef`` read, uploaded once.  ``time_weight`` appends the
+    K_PAIRSL1 term on the first head's tensor: ``time_weight * SmoothL1(x[1:], x[:-1])`` over the batch axis (n > 1)."""
 
-    def __init__(self, heads, device):
-        from .._lib import biu_mo3d_term, lib
+    def __init__(self, heads, device, time_weight=0.0):
         self.heads, terms, off, row, goff = [], [], 0, 0, 0
         for crit, shape, weight in heads:
             n, c, d, h, w = shape
@@ -61,6 +61,14 @@ class _Plan:
             off += n * rows * SLOTS
             row += n
             goff += (numel + 3) // 4 * 4          # every head's gradient starts 16-byte aligned in the one buffer
+        self.pair = None
+        if time_weight:
+            n, per = heads[0][1][0], self.heads[0][5] // heads[0][1][0]
+            rows = lib.biu_pair_smooth_l1_blocks((n - 1) * per)
+            self.pair = (n, per, off, row)
+            terms.append(biu_mo3d_term(K_PAIRSL1, rows, off, 1, per, (n - 1) * per, 0.0, 0.0, 0.0, float(time_weight)))
+            off += rows * SLOTS
+            row += 1
         self.ws_floats, self.nterms, self.nrows, self.grad_floats = off, len(terms), row, goff
         raw = bytes((biu_mo3d_term * len(terms))(*terms))
         self.terms = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
@@ -79,6 +87,9 @@ class _FusedMo3d(torch.autograd.Function):
         st = _stream()
         for (kind, (n, c, d, h, w), off, _, _, _), x, tg, code in zip(plan.heads, xs, targets, codes):
             _call("biu_mo3d_loss_fwd", kind, code, _p(x), _p(tg), n, c, d, h, w, _p(ws, off), st)
+        if plan.pair:
+            n, per, off, _ = plan.pair
+            _call("biu_pair_smooth_l1_fwd", _p(xs[0]), n, per, _p(ws, off), st)
         _call("biu_mo3d_loss_finish", _p(plan.terms), plan.nterms, _p(ws), _p(saved), st)
         assert not any(codes) or not any(ctx.needs_input_grad), "pre_act is forward only"
         ctx.save_for_backward(*xs)
@@ -93,12 +104,16 @@ class _FusedMo3d(torch.autograd.Function):
         coef = torch.empty(plan.nrows * 4, dtype=torch.float32, device=g.device)
         st = _stream()
         _call("biu_mo3d_loss_coef", _p(plan.terms), plan.nterms, _p(g), _p(saved), _p(coef), st)
-        flat = torch.empty(plan.grad_floats, dtype=torch.float32, device=g.device)          # the gradients of all heads in one go
+        # the gradients of all heads in one go; a single head needs no views
+        flat = torch.empty(plan.grad_floats, dtype=torch.float32, device=g.device) if len(xs) > 1 else None
         grads = []
         for (kind, (n, c, d, h, w), _, row, goff, numel), x, tg in zip(plan.heads, xs, ctx.targets):
-            dx = flat[goff:goff + numel].view(x.shape)
+            dx = flat[goff:goff + numel].view(x.shape) if flat is not None else torch.empty_like(x)
             _call("biu_mo3d_loss_bwd", kind, _p(x), _p(tg), n, c, d, h, w, _p(coef, 4 * row), _p(dx), st)
             grads.append(dx)
+        if plan.pair:
+            n, per, _, row = plan.pair
+            _call("biu_pair_smooth_l1_bwd", _p(xs[0]), n, per, _p(coef, 4 * row), _p(grads[0]), 1, st)
         return (None, None, None) + tuple(grads)
 
 
@@ -122,13 +137,6 @@ class _Criterion(nn.Module):
         return _FusedMo3d.apply(plans[key], (targets,), (0,), logits)
 
 
-def _soft_dice(logits, targets, smooth=1.0):
-    num = targets.size(0)
-    m1, m2 = torch.sigmoid(logits).reshape(num, -1), targets.reshape(num, -1)
-    score = 2. * ((m1 * m2).sum(1) + smooth) / (m1.sum(1) + m2.sum(1) + smooth)
-    return 1 - score.mean()
-
-
 class BCEDiceLoss(_Criterion):
     """``alpha * BCEWithLogits(mean) + beta * (1 - mean_n 2 (sum_n p t + 1) / (sum_n p + sum_n t + 1))`` (losses.py:81-116)."""
     kind = K_BCEDICE
@@ -138,10 +146,10 @@ class BCEDiceLoss(_Criterion):
         self.alpha, self.beta = alpha, beta
 
     def _params(self):
-        return (float(self.alpha), float(self.beta), 0.0)
+        return (float(self.alpha), float(self.beta), 1.0)          # p2: the Dice smooth
 
     def _torch(self, logits, targets):
-        return self.alpha * F.binary_cross_entropy_with_logits(logits, targets) + self.beta * _soft_dice(logits, targets)
+        return self.alpha * F.binary_cross_entropy_with_logits(logits, targets) + self.beta * soft_dice(logits, targets)
 
 
 class DiceLoss(BCEDiceLoss):
@@ -149,14 +157,6 @@ class DiceLoss(BCEDiceLoss):
 
     def __init__(self):
         super().__init__(0, 1)
-
-
-def _tversky(logits, targets, alpha, beta, smooth):
-    p, t = torch.sigmoid(logits).reshape(-1), targets.reshape(-1)
-    tp = (p * t).sum()
-    fp = ((1 - t) * p).sum()
-    fn = (t * (1 - p)).sum()
-    return (tp + smooth) / (tp + alpha * fp + beta * fn + smooth)
 
 
 class TverskyLoss(_Criterion):
@@ -171,7 +171,7 @@ class TverskyLoss(_Criterion):
         return (float(self.alpha), float(self.beta), float(self.smooth))
 
     def _torch(self, inputs, targets):
-        return 1 - _tversky(inputs, targets, self.alpha, self.beta, self.smooth)
+        return 1 - tversky_index(torch.sigmoid(inputs), targets, self.alpha, self.beta, self.smooth)
 
 
 class logcoshTverskyLoss(TverskyLoss):
@@ -179,7 +179,7 @@ class logcoshTverskyLoss(TverskyLoss):
     kind = K_LCTVERSKY
 
     def _torch(self, inputs, targets):
-        return torch.log(torch.cosh(1 - _tversky(inputs, targets, self.alpha, self.beta, self.smooth)))
+        return torch.log(torch.cosh(1 - tversky_index(torch.sigmoid(inputs), targets, self.alpha, self.beta, self.smooth)))
 
 
 class TemporalConsistencyLoss(nn.Module):

@@ -287,34 +287,6 @@ int    biu_upconv_fwd(const biu_act* x, const biu_xform* xf, const void* packed,
  * replaces nn.ConvTranspose2d/3d: unet/unet.py:38-47, unet3d/unet3d.py:40-42
  * w: PyTorch layout (Cin, Cout, kd, 2, 2) fp32 with kd = 2 (3-D) or 1 (2-D).
  * ---------------------------------------------------------------------------------------------- */
-/* BCEDiceLoss (unet/losses.py:78-112) over fp32 NC[D]HW logits / targets as the heads emit them, one pass each way.
- * fwd: partial[n][biu_bce_dice_blocks(per_sample)][4] = per-block sums of (bce(l,t), p, t, p*t), p = sigmoid(l).
- * bwd: dlogits_i (+)= coef[n][0]*(p_i - t_i) + (coef[n][1] + coef[n][2]*t_i) * p_i*(1 - p_i).                        */
-int biu_bce_dice_blocks(long long per_sample);
-int biu_bce_dice_fwd(const float* logits, const float* target, int n, long long per_sample, float* partial, biu_stream stream);
-int biu_bce_dice_bwd(const float* logits, const float* target, int n, long long per_sample, const float* coef, float* dlogits,
-                     int accumulate, biu_stream stream);
-
-/* SmoothL1 (beta 1, mean) between neighbouring BATCH entries of fp32 logits -- nn.SmoothL1Loss()(y_logits[1:], y_logits[:-1]),
- * the "time" term of the 3-D trainer (unet3d/train.py:140-145).  fwd: partial[biu_pair_smooth_l1_blocks(pairs)] block sums of
- * h(l[i + per_sample] - l[i]), pairs = (n - 1) * per_sample.  bwd: dlogits (+)= coef[0] * d sum / d logits (coef on the device).      */
-int biu_pair_smooth_l1_blocks(long long pairs);
-int biu_pair_smooth_l1_fwd(const float* logits, int n, long long per_sample, float* partial, biu_stream stream);
-int biu_pair_smooth_l1_bwd(const float* logits, int n, long long per_sample, const float* coef, float* dlogits, int accumulate,
-                           biu_stream stream);
-/* The scalar arithmetic of the fused segmentation losses in two one-block launches (instead of ~20 element-wise torch kernels on [n, 4]
- * tensors per step).  biu_seg_loss_finish: partial = biu_bce_dice_fwd's [n][nb][4] rows, time_partial = biu_pair_smooth_l1_fwd's nbt
- * sums or NULL -> saved[1 + 4n + n + 3] = { loss, sums[n][4] (BCE, P, T, P.T), den[n] = P + T + smooth, tp, tden, Tversky } with
- *   loss = a_bce * sum BCE / (n per) + a_dice * (1 - mean_n 2 (PT_n + smooth) / den_n)                    (unet/losses.py:78-112)
- *        + [has_tversky] (1 - Tv) or log cosh(1 - Tv),  Tv = (TP + s) / (TP + alpha FP + beta FN + s)     (unet/losses.py:145-239)
- *        + w_time * sum SmoothL1 / ((n - 1) per)                                                          (unet3d/train.py:140-145)
- * biu_seg_loss_coef: g = d / d loss (device scalar) -> coef[n][3] for biu_bce_dice_bwd, time_coef[1] for biu_pair_smooth_l1_bwd.      */
-int biu_seg_loss_finish(const float* partial, int n, int nb, long long per_sample, const float* time_partial, int nbt,
-                        float a_bce, float a_dice, float smooth, int has_tversky, float tv_alpha, float tv_beta, float tv_smooth,
-                        int logcosh, float w_time, float* saved, biu_stream stream);
-int biu_seg_loss_coef(const float* g, const float* saved, int n, long long per_sample, float a_bce, float a_dice, float smooth,
-                      int has_tversky, float tv_alpha, float tv_beta, float tv_smooth, int logcosh, float w_time, float* coef,
-                      float* time_coef, biu_stream stream);
 /* d loss / d logits of one head from the caller's gradients w.r.t. its logits and / or its activated output (act as in
  * biu_head_fwd; multi_output_unet3d.py:97-104), written to channels [dst_c0, dst_c0 + ch) of a fp32 [n, dst_channels, spatial]
  * tensor -- the stacked operand of one biu_head_bwd over all heads that share a trunk.                                    */
@@ -363,28 +335,36 @@ int biu_mo2d_loss_coef(const biu_mo2d_term* terms, int nterms, const float* g, c
 int biu_mo2d_loss_bwd(int kind, float ea, float eb, const float* const* pred, int nlev, const float* target, int n, int c, int h, int w,
                       const float* coef, float* const* dpred, biu_stream stream);
 
-/* The criteria of the 3-D multi-output trainer (multi_output_unet3d/losses.py) on the tensor the model returned for a head: x / target
- * fp32 contiguous [n, c, d, h, w]; the criteria treat x as logits, p = sigmoid(x).  M = n c d h w, sums over one sample carry _n.
+/* The segmentation criteria on logits (p = sigmoid(x)): the single-head criteria of losses.py (unet/losses.py:78-239, any rank, passed as
+ * [n, c, 1, 1, rest]) and those of the 3-D multi-output trainer (multi_output_unet3d/losses.py).  x / target fp32 contiguous
+ * [n, c, d, h, w]; only per = c d h w matters to kinds 0..2.  M = n per, sums over one sample carry _n.
  *   kind                    (p0, p1, p2)            value
- *   0 BCEDiceLoss           (alpha, beta, -)        p0 mean BCEWithLogits(x, t) + p1 (1 - mean_n 2 (sum_n p t + 1) / (sum_n p + sum_n t + 1))
+ *   0 BCEDiceLoss           (alpha, beta, smooth)   p0 mean BCEWithLogits(x, t) + p1 (1 - mean_n 2 (sum_n p t + s) / (sum_n p + sum_n t + s))
  *   1 TverskyLoss           (alpha, beta, smooth)   1 - Tv,  Tv = (TP + s) / (TP + alpha FP + beta FN + s) over the whole tensor
  *   2 logcoshTverskyLoss    (alpha, beta, smooth)   log cosh(1 - Tv)
- *   3 BCEDiceTemporalLoss   (w0, w1, -)             p0 BCEDice(1, 1) + p1 mean |x[:, :, 1:] - x[:, :, :-1]| over pairs = n c (d - 1) h w;
- *                                                   nan when d == 1 (l1_loss over an empty slice)
+ *   3 BCEDiceTemporalLoss   (w0, w1, -)             p0 BCEDice(1, 1) (s = 1) + p1 mean |x[:, :, 1:] - x[:, :, :-1]| over
+ *                                                   pairs = n c (d - 1) h w; nan when d == 1 (l1_loss over an empty slice)
+ *   4 pair SmoothL1         (-, -, -)               sum SmoothL1(x[1:] - x[:-1]) / pairs between neighbouring BATCH entries, the "time" term
+ *                                                   of the 3-D trainer (unet3d/train.py:140-145): a table term only (n = 1, rows =
+ *                                                   biu_pair_smooth_l1_blocks(pairs), pairs = (N - 1) per), refused by _fwd / _bwd
  * biu_mo3d_loss_blocks: rows = the partial rows PER SAMPLE for a tensor of numel elements.
  * biu_mo3d_loss_fwd:    partial[n][rows][BIU_MO3D_SLOTS] per-block sums { BCE, p, t, p t, |x[z+1] - x[z]| (kind 3), 0 x 3 }, no atomics:
  *                       bit-reproducible.  pre_act (0 none, 1 sigmoid, 2 tanh, 3 relu) is applied to x before everything else -- the
  *                       validation pass of the reference, forward only.
- * biu_mo3d_loss_finish: ONE one-block launch for all heads of a step.  terms (device array, nterms <= BIU_MO3D_MAX_TERMS) name each head:
- *                       its partial rows (offset in floats into `workspace`), kind, extents, parameters and head weight ->
+ * biu_pair_smooth_l1_fwd: partial[biu_pair_smooth_l1_blocks(pairs)][BIU_MO3D_SLOTS], the block's sum of SmoothL1 in slot 0, 0 x 7.
+ * biu_mo3d_loss_finish: ONE one-block launch for all terms of a step.  terms (device array, nterms <= BIU_MO3D_MAX_TERMS) name each one:
+ *                       its partial rows (offset in floats into `workspace`), kind, extents, parameters and weight ->
  *                       saved[BIU_MO3D_SAVED_HEADER + BIU_MO3D_SLOTS sum_terms n] = { sum_t weight_t loss_t, loss_0 .. loss_{nterms-1}, 0 ..,
  *                       then per (term, sample) in table order the merged row }.
- * biu_mo3d_loss_coef:   g = d / d total (device scalar) -> coef[sum_terms n][4] = { c0, c1, c2, ct } per (term, sample), table order.
+ * biu_mo3d_loss_coef:   g = d / d total (device scalar) -> coef[sum_terms n][4] = { c0, c1, c2, ct } per (term, sample), table order;
+ *                       kind 4: c0 = g weight / pairs.
  * biu_mo3d_loss_bwd:    dx = c0 (p - t) + (c1 + c2 t) p (1 - p) + ct (sign(x[z] - x[z-1]) - sign(x[z+1] - x[z])) for one head from its coef
  *                       rows (coef + 4 * samples of the terms before it); the missing neighbour's term is dropped at z = 0 and z = d - 1,
  *                       sign(0) = 0.  Takes x as given: a pre-activation under autograd is the caller's.
+ * biu_pair_smooth_l1_bwd: dlogits (+)= coef[0] * d sum SmoothL1 / d logits, coef = the kind-4 term's row of biu_mo3d_loss_coef.
  * 16-byte accesses when every pointer is 16-byte aligned and c d h w % 4 == 0 (kind 3: h w % 4 == 0 too); scalar accesses otherwise.
  * n <= 65535 (one grid row per sample).                                                                                               */
+#define BIU_MO3D_PAIR_SL1 4
 #define BIU_MO3D_MAX_TERMS 16
 #define BIU_MO3D_SLOTS 8
 #define BIU_MO3D_SAVED_HEADER 32
@@ -392,7 +372,7 @@ typedef struct biu_mo3d_term {
     int kind, rows;             /* rows: partial rows per sample (biu_mo3d_loss_blocks)            */
     long long partial_off;      /* floats, into the workspace handed to biu_mo3d_loss_finish       */
     long long n, per_sample;    /* samples, and c d h w                                            */
-    long long pairs;            /* n c (d - 1) h w                                                 */
+    long long pairs;            /* n c (d - 1) h w; kind 4: (N - 1) per                            */
     float p0, p1, p2, weight;
 } biu_mo3d_term;
 int biu_mo3d_loss_blocks(long long numel);
@@ -402,6 +382,10 @@ int biu_mo3d_loss_finish(const biu_mo3d_term* terms, int nterms, const float* wo
 int biu_mo3d_loss_coef(const biu_mo3d_term* terms, int nterms, const float* g, const float* saved, float* coef, biu_stream stream);
 int biu_mo3d_loss_bwd(int kind, const float* x, const float* target, int n, int c, int d, int h, int w, const float* coef, float* dx,
                       biu_stream stream);
+int biu_pair_smooth_l1_blocks(long long pairs);
+int biu_pair_smooth_l1_fwd(const float* logits, int n, long long per_sample, float* partial, biu_stream stream);
+int biu_pair_smooth_l1_bwd(const float* logits, int n, long long per_sample, const float* coef, float* dlogits, int accumulate,
+                           biu_stream stream);
 
 /* Trilinear x2 up-sampling, align_corners = False (F.interpolate(scale_factor=2, mode='trilinear'),
  * unet3d/unet3d.py:82,89,96): out = interp(T(x)); depth is doubled when out->d == 2 * x->d, kept when equal.

@@ -1136,7 +1136,7 @@ def test_depthwise_xcorr(shape, dtype):
 
 @pytest.mark.parametrize("shape", [(4, 1, 8, 16, 16), (2, 3, 33, 17), (1, 40, 40)])
 def test_fused_bce_dice_loss(shape):
-    """BCEDiceLoss through biu_bce_dice_fwd/bwd against the eager expression of unet/losses.py:78-112 (value and gradient)."""
+    """BCEDiceLoss through the fused loss kernels (biu_mo3d_loss_*) against the eager expression of unet/losses.py:78-112 (value and gradient)."""
     from bio_image_unet_amd.losses import BCEDiceLoss, BCELoss2d, SoftDiceLoss
     torch.manual_seed(0)
     lg = (torch.randn(shape) * 3).cuda().requires_grad_(True)

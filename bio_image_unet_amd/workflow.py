@@ -942,15 +942,12 @@ class PredictSiam(_PredictBase):
             pairs = fe.pair_tiles(self._origins(), self.resize_dim, invert=invert)
         self._load_model(model_params)
         stitch = _Stitcher(self.device, 1, (1, max(th, h), max(tw, w)))
-        frames, cur = [], None
+        frames = []
         for i in range(self.tif_len):
             if preprocess == "device":
                 patches = pairs.frame(i, self.N)
             else:                               # the host path normalises and cuts a pair when its turn comes, never the whole movie
-                prev = (movie[0] if self.tif_len == 1 else movie[1]) if i == 0 else cur
-                cur = movie[i]
-                pair = normalise_stack(np.array([prev, cur], dtype=np.float64), normalization_mode, clip_threshold, invert).astype("uint8")
-                patches = self._split(pair)
+                patches = self._pair_patches(movie, i, normalization_mode, clip_threshold, invert)
             stitch.reset()
             for b, both in self._batches(patches, batch_size):                  # uint8 (cur, prev)
                 q = _quantize_u8(self._forward(both[:, 0:1].contiguous(), both[:, 1:2].contiguous())[0])
@@ -969,6 +966,13 @@ class PredictSiam(_PredictBase):
         origins = self._grid_2d(1)
         self.N = self.N_per_img
         return origins
+
+    def _pair_patches(self, movie, i, normalization_mode, clip_threshold, invert):
+        """The host path's patches of frame ``i``: the frame and its predecessor (frame 0 goes with frame 1, or with itself in a one-frame
+        movie, ``siam_unet/predict.py:108-117``), normalised as a two-frame stack, truncated to uint8 and cut."""
+        prev = movie[(0 if self.tif_len == 1 else 1) if i == 0 else i - 1]
+        pair = normalise_stack(np.array([prev, movie[i]], dtype=np.float64), normalization_mode, clip_threshold, invert).astype("uint8")
+        return self._split(pair)
 
     def _split(self, pair):
         """(previous, current) -> patches [N, 2, th, tw] with the current frame in channel 0."""
@@ -1107,9 +1111,14 @@ class PredictMo2d(_PredictBase):
     ``biu_stitch_finish``) with a weight plane of 1 whose ``safe_margin = 20`` rows / columns are zeroed on every side that has a
     neighbour; pixels no patch weights get the (float16) mean of that head's patches (``:279``).
 
-    As upstream, patches are cut on a stride of ``X_start[1]`` / ``Y_start[1]`` (``:180-181``) and stitched at ``X_start`` / ``Y_start``;
-    the first ``N_x x N_y`` windows of that stride are taken.  ``result`` is a dict of arrays per head, or ``None`` when ``result_path``
-    is given and the heads were written to ``result_path + name + '.tif'``.
+    As upstream, patches are cut on a stride of ``X_start[1]`` / ``Y_start[1]`` (``:180-181``) and stitched at ``X_start`` / ``Y_start``.
+    ALL windows of that stride are cut and predicted, rows outermost, and every one counts in the fill mean; the first ``N_x * N_y`` of them
+    are stitched, window ``k`` at ``(X_start[k // N_y], Y_start[k % N_y])``.  Where truncation makes the stride short (``add_tile`` on an extent
+    barely larger than a patch) it yields more windows than tiles: surplus ROWS of windows come last and are only predicted, as upstream's
+    ``[:N_per_img]`` leaves them out (pinned by ``tests/golden/predict_pins_mo2d.npz``, ``row_surplus``).  Surplus COLUMNS shift every later
+    window to another tile in upstream's reshape, which scrambles the image, and with several images upstream's ``N_per_img`` no longer
+    separates them, so patches of one image land in the next: both raise ``ValueError`` here.  ``result`` is a dict of arrays per head, or
+    ``None`` when ``result_path`` is given and the heads were written to ``result_path + name + '.tif'``.
 
     ``preprocess='device'``: as for ``PredictMo3d`` -- fp64 on the device, rounded to float32 once, against numpy float32 on the host; NaN
     raises ``ValueError``."""
@@ -1184,19 +1193,31 @@ class PredictMo2d(_PredictBase):
         return sx, sy
 
     def _origins(self):
-        """The windows ``_split`` takes, as (image, 0, row, column) in the reflect-padded stack: the first ``N_x x N_y`` windows of the
-        stride that fit -- what the device front end cuts."""
+        """The windows ``_split`` takes, as (image, 0, row, column) in the reflect-padded stack: every window of the stride that fits, rows
+        outermost -- what the device front end cuts.  The first ``N_per_img`` are the tiles; a surplus row of windows (one image only)
+        follows them and is predicted without being stitched.  Raises ``ValueError`` where upstream's result is scrambled (class docstring)."""
         sx, sy = self._strides()
         (ph, pw), (H, W) = self.patch_size, self.padded
-        rows = list(range(0, H - ph + 1, sx))[:self.N_x]
-        cols = list(range(0, W - pw + 1, sy))[:self.N_y]
+        rows = list(range(0, H - ph + 1, sx))
+        cols = list(range(0, W - pw + 1, sy))
+        assert len(rows) >= self.N_x and len(cols) >= self.N_y          # a stride truncated downwards never yields fewer windows
+        where = f"images {tuple(self.imgs_shape)}, max_patch_size {tuple(self.max_patch_size)}, add_tile {self.add_tile}"
+        if len(cols) > self.N_y:
+            raise ValueError(f"PredictMo2d: the column stride {sy} yields {len(cols)} windows for N_y = {self.N_y} tiles ({where}); upstream "
+                             "reshapes the longer list to N_x x N_y and scrambles the image.  Use another add_tile or max_patch_size")
+        if len(rows) > self.N_x and self.imgs_shape[0] > 1:
+            raise ValueError(f"PredictMo2d: the row stride {sx} yields {len(rows)} windows for N_x = {self.N_x} tiles ({where}); with several "
+                             "images upstream stitches patches of one image into the next.  Predict the images one by one, or use "
+                             "another add_tile or max_patch_size")
         self.origins = [(i, 0, r, c) for i in range(self.imgs_shape[0]) for r in rows for c in cols]
         return self.origins
 
     def _place(self, k):
         """Window ``k`` of the cut list goes to its image at ``(X_start[j], Y_start[c])``, (j, c) being its place in the image's grid: the
         origin it was cut at wherever the stride ``X_start[1]`` reproduces ``X_start`` (always with up to two tiles per axis), and upstream's
-        choice (``predict.py:252-253``) where truncation makes the two drift apart."""
+        choice (``predict.py:252-253``) where truncation makes the two drift apart.  ``None`` for a surplus window, which is not stitched."""
+        if len(self.origins) > self.N and k >= self.N_per_img:
+            return None
         j, c = divmod(k % self.N_per_img, self.N_y)
         return self.origins[k][0], (0, int(self.X_start[j]), int(self.Y_start[c]))
 
@@ -1221,8 +1242,9 @@ class PredictMo2d(_PredictBase):
                 p16[key] = out[key].to(torch.float16).float()       # the reference keeps patches as float16
                 sums[key] += p16[key].double().sum()
             for i in range(x.shape[0]):
-                img, origin = self._place(b + i)
-                stitch.add({key: p[i].unsqueeze(1) for key, p in p16.items()}, img, origin, divmod((b + i) % self.N_per_img, self.N_y))
+                at = self._place(b + i)
+                if at is not None:                                  # (a surplus window has been counted in the fill mean above, no more)
+                    stitch.add({key: p[i].unsqueeze(1) for key, p in p16.items()}, *at, divmod((b + i) % self.N_per_img, self.N_y))
         result = {}
         for key, cfg in heads.items():
             fill = float(np.float16(float(sums[key]) / (len(patches) * cfg["channels"] * ph * pw)))      # np.mean of a float16 array is float16
